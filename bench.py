@@ -29,6 +29,15 @@ SQ_INSTS_VALU and the clock (GRBM_GUI_ACTIVE) of the same PMC record — and the
 bytes per launch over the launch time). Every kernel with a PMC record also carries `measured_hbm`
 (GB/s and fraction of 8 TB/s the kernel actually moves). `cpu_baseline` times the CPU oracle (a restatement of the
 reference CPUPathTracer; oracle/) on this host, rank 0, N=1 only.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+line: `value`, `ms_per_step` and the timed launches' HIP-event times (`kernel_ms`). `--dump-outputs
+DIR` also writes what the last timed step returned, the accumulated float RGBA image a caller reads
+with spt_read_accum (rank 0's assembled image at N > 1), as DIR/accum.npy (float32, height x width x
+4); the inputs depend on the arguments alone, so two builds can be compared output for output.
+Everything that takes runs of its own is behind `--full`: the counting re-render that the rooflines,
+the segment figures and `lane_utilization` need on the persistent schedules (null without it), the
+CPU baseline and the GPU-vs-oracle parity leg.
 """
 from __future__ import annotations
 
@@ -69,8 +78,13 @@ def parse():
     ap.add_argument("--frames-in-flight", type=int, default=0, help="frames per wavefront pass (0 = auto)")
     ap.add_argument("--frames-per-call", type=int, default=0,
                     help="frames per spt_render call (0 = one call per step)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the counting re-render (rooflines, segment figures), "
+                         "the CPU baseline and the parity leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write the image the last timed step returned as DIR/accum.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity leg")
     ap.add_argument("--save-image", default="", help="rank 0: save the assembled float RGBA image (.npy)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (RCCL, one GPU per rank) or gloo (multi-rank rehearsal, ranks may share a GPU)")
@@ -611,12 +625,20 @@ def main():
         elapsed = float(t.item())
 
     total_frames = args.steps * frames_per_step
-    if rank == 0 and args.save_image:
-        img = image.cpu().numpy() if image is not None else ctx.read_accum()
-        np.save(args.save_image, img.reshape(h, w, 4))
+    if rank == 0 and (args.save_image or args.dump_outputs):
+        img = (image.cpu().numpy() if image is not None else ctx.read_accum()).reshape(h, w, 4)
+        if args.save_image:
+            np.save(args.save_image, img)
+        if args.dump_outputs:  # what the timed path's last step left for its caller
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "accum.npy"), np.ascontiguousarray(img, dtype=np.float32))
     st = stats_diff(st0, ctx.stats())
     specialized = bool(st.specialized)  # the timed launches (the counting re-render below is generic)
-    if st.schedule in (spt.SCHEDULE_PERSISTENT, spt.SCHEDULE_FRAME) and not args.no_profile:
+    persistent = st.schedule in (spt.SCHEDULE_PERSISTENT, spt.SCHEDULE_FRAME)
+    # the persistent schedules count segments only in the re-render below (--full); the wavefront
+    # schedules count in the timed launches themselves
+    counted = not persistent or (args.full and not args.no_profile)
+    if persistent and counted:
         # The timed k_paths / k_frame launches do not count segments (that variant is slower); the rendering
         # is deterministic, so an untimed re-render of the same frames with counters gives the
         # exact segment counts of the timed work (kernel times are kept from the timed run).
@@ -687,7 +709,7 @@ def main():
     frames_per_launch = 1 if st.schedule == spt.SCHEDULE_FRAME else min(chunk, 1024)
     label = pmc_label(args, sim or world, frames_per_launch)
     fams = kernel_rooflines(st, args.bounces, int(st.passes), shard_px, args.pmc_csv, label,
-                            frame_kernel=st.schedule == spt.SCHEDULE_FRAME)
+                            frame_kernel=st.schedule == spt.SCHEDULE_FRAME) if counted else {}
     for name in ("k_paths", "k_frame"):
         if name in fams:
             fams[name]["timing"] = ("one HIP event pair around all timed launches on the integrator's stream "
@@ -736,19 +758,19 @@ def main():
         "cpu_baseline": None,
         "pmc_label": label,
         "kernel_source": kernel_source_hash(),
-        "segments_per_sample": round(seg_total / max(1, st.paths), 4),
+        "segments_per_sample": round(seg_total / max(1, st.paths), 4) if counted else None,
         # traced work beside `value`: the camera ray has no jitter (CPUPathTracer.cpp:62-73), so k_paths
         # traces bounce 0 once per pixel per launch and adds the sky pixels' constant radiance without
         # tracing; `value` counts samples (paths), this counts the segments traced
         "traced_segments_per_s": (round(traced_segments(st, args.bounces, shard_px,
                                                         st.schedule == spt.SCHEDULE_FRAME) / elapsed, 1)
-                                  if st.schedule in (spt.SCHEDULE_PERSISTENT, spt.SCHEDULE_FRAME) and not sim
-                                  and not args.no_profile else None),
+                                  if persistent and counted and not sim else None),
         # paths ended by their camera segment (misses): 1 - bounce-1 segments / paths
         "camera_only_path_frac": (round(1.0 - int(st.segments[1]) / max(1, int(st.segments[0])), 4)
                                   if args.bounces > 1 and st.segments[0] else None),
-        "nee": {"shadow_rays": int(st.shadow_rays), "emitters": int(st.emitters),
-                "shadow_rays_per_sample": round(int(st.shadow_rays) / max(1, st.paths), 4)} if args.nee else None,
+        "nee": {"shadow_rays": int(st.shadow_rays) if counted else None, "emitters": int(st.emitters),
+                "shadow_rays_per_sample": (round(int(st.shadow_rays) / max(1, st.paths), 4) if counted else None)}
+        if args.nee else None,
         "simulate_world": sim_report,
         "schedule": ["split", "fused", "persistent", "frame"][int(st.schedule)],
         "specialized": specialized,
@@ -760,12 +782,13 @@ def main():
         "kernel_ms": {"paths": round(st.persistent_ms, 3), "extend": round(st.extend_ms, 3), "shade": round(st.shade_ms, 3),
                       "trace_tail": round(st.tail_ms, 3), "accumulate": round(st.other_ms, 3)},
         "tail_bounce": int(st.tail_bounce),
-        "per_bounce": [{"segments": int(st.segments[b]), "extend_ms": round(st.extend_ms_bounce[b], 3),
+        "per_bounce": [{"segments": int(st.segments[b]) if counted else None,
+                        "extend_ms": round(st.extend_ms_bounce[b], 3),
                         "shade_ms": round(st.shade_ms_bounce[b], 3)} for b in range(args.bounces)],
         "passes": int(st.passes),
     }
 
-    if rank == 0 and world == 1 and not sim and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not sim and not args.no_cpu_baseline:
         base, cpu_frames, r = cpu_baseline(spt, args, scene_arrays, args.cpu_seconds, total_frames,
                                            flags & spt.FLAG_NEE)
         result["cpu_baseline"] = base

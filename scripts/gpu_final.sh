@@ -12,24 +12,25 @@
 #   PART=c  the App's per-frame pattern with the host hand-off (scripts/app_pattern.py), plain and under
 #           rocprofv3 --kernel-trace --memory-copy-trace --stats
 #   PART=m  the multi-rank rehearsal on one GPU (scripts/gpu_multirank.sh)
-# R names the outputs (gpurun_out/${R}_*); copy what is judged into profiles/.
+# R names the outputs ($OUT/${R}_*); copy what is judged into profiles/.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}  # where this script writes
+mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 R=${R:-r06}
 C4="--scene bunnylike --steps 4 --warmup 1"
 C5="--scene interior1m --width 3840 --height 2160 --steps 1 --warmup 1 --frames-per-step 32"
 case "${PART:-a}" in
 a)
-  timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/${R}_pytest.log 2>&1 || { echo "pytest failed"; tail -40 gpurun_out/${R}_pytest.log; exit 1; }
-  tail -1 gpurun_out/${R}_pytest.log
-  timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${R}_smoke.log 2>&1 || { echo "smoke failed"; tail -20 gpurun_out/${R}_smoke.log; exit 1; }
-  grep smoke gpurun_out/${R}_smoke.log
+  timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/${R}_pytest.log 2>&1 || { echo "pytest failed"; tail -40 $OUT/${R}_pytest.log; exit 1; }
+  tail -1 $OUT/${R}_pytest.log
+  timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${R}_smoke.log 2>&1 || { echo "smoke failed"; tail -20 $OUT/${R}_smoke.log; exit 1; }
+  grep smoke $OUT/${R}_smoke.log
   # (100 timed launches: the rocprof average then weighs the clock ramp of the first ~15 lightly)
   TAG=${R}_c2 BENCH_ARGS="--steps 100 --warmup 5" bash scripts/gpu_round_profile.sh || exit 1
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 > gpurun_out/${R}_bench.json 2> gpurun_out/${R}_bench.err || { echo "bench failed"; tail -20 gpurun_out/${R}_bench.err; exit 1; }
-  tail -1 gpurun_out/${R}_bench.json | cut -c1-400
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err || { echo "bench failed"; tail -20 $OUT/${R}_bench.err; exit 1; }
+  tail -1 $OUT/${R}_bench.json | cut -c1-400
   TAG=${R}_f1 BENCH_ARGS="--frames-per-step 1 --steps 64 --warmup 8" bash scripts/gpu_round_profile.sh || exit 1
   TAG=${R}_app BENCH_ARGS="--scene app --width 512 --height 512 --bounces 4 --frames-per-step 1 --steps 256 --warmup 32" bash scripts/gpu_round_profile.sh || exit 1
   TAG=${R}_nee BENCH_ARGS="--steps 20 --warmup 5 --nee" bash scripts/gpu_round_profile.sh || exit 1
@@ -45,14 +46,14 @@ b|b1|b2)
     for cfg in c2 c4 c5; do
       case $cfg in c2) a="--steps 10 --warmup 3";; c4) a="$C4";; c5) a="$C5";; esac
       if [ "$n" = "${SIM_PMC_N:-8}" ]; then  # the N-GPU line the driver's scaling run is closest to: with PMC
-        TAG=${R}_pmcsim${n}_$cfg BENCH_ARGS="$a --simulate-world $n" bash scripts/gpu_round_profile.sh > gpurun_out/${R}_pmcsim${n}_$cfg.txt 2>&1 || { echo "sim $n $cfg profile failed"; tail -5 gpurun_out/${R}_pmcsim${n}_$cfg.txt; exit 1; }
-        cp gpurun_out/${R}_pmcsim${n}_${cfg}_bench.json gpurun_out/${R}_sim${n}_$cfg.json
+        TAG=${R}_pmcsim${n}_$cfg BENCH_ARGS="$a --simulate-world $n" bash scripts/gpu_round_profile.sh > $OUT/${R}_pmcsim${n}_$cfg.txt 2>&1 || { echo "sim $n $cfg profile failed"; tail -5 $OUT/${R}_pmcsim${n}_$cfg.txt; exit 1; }
+        cp $OUT/${R}_pmcsim${n}_${cfg}_bench.json $OUT/${R}_sim${n}_$cfg.json
       else
-        timeout -k 10 600 python bench.py $a --simulate-world $n --no-cpu-baseline > gpurun_out/${R}_sim${n}_$cfg.json 2> gpurun_out/${R}_sim${n}_$cfg.err || { echo "sim $n $cfg failed"; tail -5 gpurun_out/${R}_sim${n}_$cfg.err; exit 1; }
+        timeout -k 10 600 python bench.py $a --simulate-world $n --no-cpu-baseline > $OUT/${R}_sim${n}_$cfg.json 2> $OUT/${R}_sim${n}_$cfg.err || { echo "sim $n $cfg failed"; tail -5 $OUT/${R}_sim${n}_$cfg.err; exit 1; }
       fi
       python3 -c "
 import json
-d=json.loads(open('gpurun_out/${R}_sim${n}_$cfg.json').read().strip().splitlines()[-1])
+d=json.loads(open('$OUT/${R}_sim${n}_$cfg.json').read().strip().splitlines()[-1])
 s=d.get('simulate_world') or {}
 print('sim $n $cfg', d['value'], {k: s.get(k) for k in ('projected_speedup', 'projected_speedup_matched', 'max_ms_per_step', 'min_ms_per_step', 'slowest_rank')})
 "
@@ -60,9 +61,9 @@ print('sim $n $cfg', d['value'], {k: s.get(k) for k in ('projected_speedup', 'pr
   done
   ;;
 c)
-  timeout -k 10 300 python scripts/app_pattern.py > gpurun_out/${R}_app_pattern.json 2> gpurun_out/${R}_app_pattern.err || { echo "app_pattern failed"; tail -5 gpurun_out/${R}_app_pattern.err; exit 1; }
-  cat gpurun_out/${R}_app_pattern.json
-  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats -d gpurun_out/${R}_app_pattern_rocprof -o run --output-format csv -- python3 scripts/app_pattern.py > gpurun_out/${R}_app_pattern_rocprof.json 2> gpurun_out/${R}_app_pattern_rocprof.err || { echo "app_pattern rocprof failed"; tail -5 gpurun_out/${R}_app_pattern_rocprof.err; exit 1; }
+  timeout -k 10 300 python scripts/app_pattern.py > $OUT/${R}_app_pattern.json 2> $OUT/${R}_app_pattern.err || { echo "app_pattern failed"; tail -5 $OUT/${R}_app_pattern.err; exit 1; }
+  cat $OUT/${R}_app_pattern.json
+  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats -d $OUT/${R}_app_pattern_rocprof -o run --output-format csv -- python3 scripts/app_pattern.py > $OUT/${R}_app_pattern_rocprof.json 2> $OUT/${R}_app_pattern_rocprof.err || { echo "app_pattern rocprof failed"; tail -5 $OUT/${R}_app_pattern_rocprof.err; exit 1; }
   ;;
 m)
   bash scripts/gpu_multirank.sh || exit 1

@@ -102,3 +102,40 @@ def test_traced_segments_accounting():
     assert bench.traced_segments(St, 4, 100, frame_kernel=True) == 400 + 150 + 50 + 7
     assert bench.traced_segments(St, 4, 100, frame_kernel=False) == 400 + 150 + 50 + 3 * 100 + 7
     assert bench.traced_segments(St, 2, 100, frame_kernel=True) == 400 + 7  # only bounces < max_bounces
+
+
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    """A plain run measures its headline figure alone: --full and --dump-outputs are opt-in."""
+    bench = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs == "" and args.steps == 3 and args.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "out"
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_image(tmp_path, spt, ref):
+    """One plain run at a small size: the line carries ms_per_step and none of the --full legs, and
+    DIR/accum.npy is the accumulation the timed steps left (2 steps x 4 frames), bit for bit the oracle's."""
+    import json
+
+    import numpy as np
+
+    w, h, steps, fps = 96, 40, 2, 4
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--width", str(w),
+                        "--height", str(h), "--frames-per-step", str(fps), "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = r.stdout.strip().splitlines()
+    d = json.loads(line)
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["unit"] == "Msamples/s" and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(w * h * fps * steps / (d["ms_per_step"] * steps * 1e-3) / 1e6, rel=1e-2)
+    assert d["cpu_baseline"] is None and "parity" not in d and d["roofline"] is None and d["rooflines"] == {}
+    assert d["schedule"] == "persistent" and d["segments_per_sample"] is None  # counted only by --full's re-render
+    g = np.load(tmp_path / "dump" / "accum.npy")
+    assert g.dtype == np.float32 and g.shape == (h, w, 4)
+    want = ref.RefScene(*spt.build_scene("cornell")).render(w, h, 0, steps * fps, 8, 2, 0)
+    exact = np.all(g.view(np.uint32) == np.ascontiguousarray(want, np.float32).view(np.uint32), axis=-1)
+    assert exact.mean() >= 0.999, exact.mean()
