@@ -20,6 +20,7 @@
 #include "spt.h"
 #include "spt_jit.h"
 #include "spt_kernels.h"
+#include "spt_launch_plan.h"
 
 using namespace spt;
 
@@ -455,15 +456,8 @@ static bool nee_active(const spt_ctx* c) { return c->configured && (c->cfg.flags
 static void prefetch_flat(const spt_ctx* c) {
     if (!(c->has_scene && c->configured && c->n_prims && c->n_nodes == 0 && c->specialize == 0)) return;
     const uint64_t key = flat_jit_key(c);
-    if (nee_active(c)) {  // (the NEE kernels decide the sky at run time: env = 2)
-        jit_prefetch(kJitPathsNee, 2, key);
-        jit_prefetch(kJitFrameNee, 2, key);
-        return;
-    }
-    const int env_variant = c->d_env ? 1 : 0;
-    jit_prefetch(kJitPaths, env_variant, key);
-    jit_prefetch(kJitFrame, env_variant, key);
-    jit_prefetch(kJitPathsChan, env_variant, key);
+    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0);
+    for (int i = 0; i < kinds.n; ++i) jit_prefetch(kinds.k[i].kind, kinds.k[i].env, key);
 }
 
 PassParams base_params(spt_ctx* c) {
@@ -1339,13 +1333,11 @@ int spt_specialize_scene(spt_ctx* c) {
     if (c->n_prims == 0 || c->n_nodes != 0 || c->specialize < 0) return SPT_OK;  // nothing to specialize
     SPT_HIP(c, hipSetDevice(c->device));
     const uint64_t key = flat_jit_key(c);  // (before spt_configure: the shape alone)
-    const int env = c->d_env ? 1 : 0;
     std::string err;
-    const bool nee = nee_active(c);
-    if (nee ? (!jit_function(kJitPathsNee, 2, key, &err) || !jit_function(kJitFrameNee, 2, key, &err))
-            : (!jit_function(kJitPaths, env, key, &err) || !jit_function(kJitFrame, env, key, &err) ||
-               !jit_function(kJitPathsChan, env, key, &err)))
-        return fail(c, SPT_ERR_HIP, ("specialized kernels unavailable (the generic ones run): " + err).c_str());
+    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0);
+    for (int i = 0; i < kinds.n; ++i)
+        if (!jit_function(kinds.k[i].kind, kinds.k[i].env, key, &err))
+            return fail(c, SPT_ERR_HIP, ("specialized kernels unavailable (the generic ones run): " + err).c_str());
     return SPT_OK;
 }
 
@@ -1362,10 +1354,10 @@ int spt_compile_flat_kernels(const spt_prim* prims, uint32_t n_prims, int env_ma
     for (uint32_t g = 0; g + 1 < kFlatKinds; ++g) flat_ends |= ends[g] << (6 * g);
     const uint64_t key = flat_shape_key(flat_ends, n_prims, flat_rect_bits(sorted, ends));
     std::string out;
-    const int env = env_map ? 1 : 0;
-    if (jit_compile(kJitPaths, env, key, &out) && jit_compile(kJitFrame, env, key, &out) &&
-        jit_compile(kJitPathsChan, env, key, &out))
-        return SPT_OK;
+    const JitKindList kinds = jit_kinds_of_scene(false, env_map ? 1 : 0);  // (no emitters known here: the kinds without NEE)
+    int built = 0;
+    while (built < kinds.n && jit_compile(kinds.k[built].kind, kinds.k[built].env, key, &out)) ++built;
+    if (built == kinds.n) return SPT_OK;
     if (log && log_bytes) {
         std::strncpy(log, out.c_str(), log_bytes - 1);
         log[log_bytes - 1] = 0;

@@ -9,13 +9,29 @@
 
 namespace spt {
 
-constexpr int kJitPaths = 0;  // k_paths<false, false, env, shape>
-constexpr int kJitFrame = 1;  // k_frame<false, false, env, shape>
-constexpr int kJitPathsChan = 2;  // k_paths<false, false, env, shape, 0, true> (small row shards)
-constexpr int kJitPathsNee = 3;   // k_paths<false, false, 2, shape, 0, false, true> (SPT_FLAG_NEE; env = 2)
-constexpr int kJitFrameNee = 4;   // k_frame<false, false, 2, shape, false, true> (SPT_FLAG_NEE; env = 2)
-constexpr int kJitFrameRgba = 5;     // k_frame<false, false, env, shape, false, 0, true> (the fused resolve)
-constexpr int kJitFrameNeeRgba = 6;  // k_frame<false, false, 2, shape, false, 1, true>
+// The kernels compiled per flat scene shape: every one is <kStats = false, kBvh = false, env, shape, tail>.
+enum : int { kJitPaths, kJitFrame, kJitPathsChan, kJitPathsNee, kJitFrameNee, kJitFrameRgba, kJitFrameNeeRgba, kJitKinds };
+constexpr int kJitCallersEnv = -1;
+struct JitKindRow {
+    const char* kernel;
+    const char* tail;  // the template arguments after the shape
+    int env;           // the kind's fixed kEnv, or kJitCallersEnv: 0 gradient sky, 1 environment map
+};
+constexpr JitKindRow kJitKindTable[kJitKinds] = {
+    {"k_paths", "", kJitCallersEnv},
+    {"k_frame", "", kJitCallersEnv},
+    {"k_paths", ", 0, true", kJitCallersEnv},        // kChan (small row shards)
+    {"k_paths", ", 0, false, 1", 2},                 // kNee = kNeeAll (SPT_FLAG_NEE)
+    {"k_frame", ", false, 1", 2},                    // kNee = kNeeAll
+    {"k_frame", ", false, 0, true", kJitCallersEnv}, // kRgba (the fused resolve)
+    {"k_frame", ", false, 1, true", 2},              // kNee = kNeeAll, kRgba
+};
+// the name expression hiprtc instantiates for (kind, env, shape)
+inline std::string jit_name_expr(int kind, int env, uint64_t shape) {
+    const JitKindRow& k = kJitKindTable[kind];
+    return std::string("spt::") + k.kernel + "<false, false, " + std::to_string(k.env == kJitCallersEnv ? env : k.env) +
+           ", " + std::to_string((unsigned long long)shape) + "ull" + k.tail + ">";
+}
 
 // Compile the kernel for a flat scene shape (flat_shape_key) without loading it (no device needed);
 // false and the compiler log on failure; `code` (optional) receives the code object. Cached per process.

@@ -211,19 +211,6 @@ void ensure_worker() {
     at_exit = true;
 }
 
-std::string name_expr(int kernel, int env, uint64_t shape) {
-    char buf[160];
-    const bool frame = kernel == kJitFrame || kernel == kJitFrameNee || kernel == kJitFrameRgba || kernel == kJitFrameNeeRgba;
-    const char* tail = kernel == kJitPathsChan ? ", 0, true"
-                       : kernel == kJitPathsNee ? ", 0, false, 1"
-                       : kernel == kJitFrameNee ? ", false, 1"  // (kNee = kNeeAll)
-                       : kernel == kJitFrameRgba ? ", false, 0, true"
-                       : kernel == kJitFrameNeeRgba ? ", false, 1, true" : "";
-    std::snprintf(buf, sizeof buf, "spt::%s<false, false, %d, %lluull%s>", frame ? "k_frame" : "k_paths", env,
-                  (unsigned long long)shape, tail);
-    return buf;
-}
-
 // The device's architecture without its feature suffix ("gfx950:sramecc+:xnack-" -> "gfx950"), queried
 // once per device (a launch asks while the background compile runs).
 std::string device_arch(int device) {
@@ -248,7 +235,7 @@ std::string device_arch(int device) {
 // One hiprtc compile (no lock held).
 Program compile_now(const std::string& arch, int kernel, int env, uint64_t shape) {
     Program out;
-    const std::string expr = name_expr(kernel, env, shape);
+    const std::string expr = jit_name_expr(kernel, env, shape);
     std::vector<const char*> hdr_src, hdr_name;
     for (size_t i = 1; i < kJitSourceCount; ++i) {
         hdr_name.push_back(kJitSources[i].name);

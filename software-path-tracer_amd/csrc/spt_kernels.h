@@ -1,18 +1,6 @@
-// spt_kernels.h — launch interface between the C-ABI (spt_capi.hip) and the wavefront kernels
-// (spt_kernels.hip). Internal.
-//
-// Wavefront layout (SURVEY.md §7 step 4): one pass traces F frames x P shard pixels camera paths.
-//   extend[b]  : closest hit of every queued ray -> hit[]                 (rtcIntersect1, :214-227)
-//                (bounce 0 computes the camera rays of the pass itself,     CPUPathTracer.cpp:57-73)
-//   shade[b]   : miss/sky, emission, albedo, RR, bounce -> queue b+1      (trace_ray body, :229-280)
-//   accumulate : per pixel, add the pass's F frame radiances in frame order (:77-80)
-//
-// Queues are SoA float4 arrays in HBM cut into n_sub block-private sub-queues of capacity sub_cap.
-// Block s of every extend/shade launch owns sub-queue s: it reads segment s of queue b and appends
-// the surviving paths to segment s of queue b+1 (wave ballot + LDS prefix, no global atomics), then
-// publishes the segment length with one plain store. Paths are dealt to the sub-queues in wave-sized
-// chunks round-robin, so every sub-queue samples the whole image and the segment lengths stay
-// balanced bounce after bounce.
+// spt_kernels.h — what the C-ABI (spt_capi.hip), the kernels (spt_kernels.hip, also compiled at run time:
+// spt_jit.hip) and the host's launch planning (spt_launch_plan.h) share: the pass parameters, the
+// constants both the kernels and their launchers size things by, and the host launchers. Internal.
 #pragma once
 
 #ifndef __HIPCC_RTC__
@@ -48,6 +36,18 @@ struct NeeParams {
 constexpr int kNeeAll = 1;
 constexpr int kNeeNoSpheres = 2;
 
+// Wavefront layout (SURVEY.md §7 step 4): one pass traces F frames x P shard pixels camera paths.
+//   extend[b]  : closest hit of every queued ray -> hit[]                 (rtcIntersect1, :214-227)
+//                (bounce 0 computes the camera rays of the pass itself,     CPUPathTracer.cpp:57-73)
+//   shade[b]   : miss/sky, emission, albedo, RR, bounce -> queue b+1      (trace_ray body, :229-280)
+//   accumulate : per pixel, add the pass's F frame radiances in frame order (:77-80)
+//
+// Queues are SoA float4 arrays in HBM cut into n_sub block-private sub-queues of capacity sub_cap.
+// Block s of every extend/shade launch owns sub-queue s: it reads segment s of queue b and appends
+// the surviving paths to segment s of queue b+1 (wave ballot + LDS prefix, no global atomics), then
+// publishes the segment length with one plain store. Paths are dealt to the sub-queues in wave-sized
+// chunks round-robin, so every sub-queue samples the whole image and the segment lengths stay
+// balanced bounce after bounce.
 struct QueueBufs {
     float4* o;  // (origin.xyz, path id bits)
     float4* d;  // (direction.xyz, rng state bits)
@@ -225,6 +225,39 @@ constexpr uint32_t kFrameHitCache = 2;
 // interior, no sky) -1.6 % (below the sky threshold)
 constexpr uint32_t kFrameListsMinSkyDiv = 4;  // lists when sky pixels >= shard pixels / 4
 
+// ---- the persistent kernels (k_paths, k_frame): what the kernels and their launch plans share ----
+constexpr int kBvhSmallWaves = 8;   // BVH k_paths of scenes of <= kBvhSmall primitives (C4 +2.6 % over 7; C5: -5 %)
+constexpr uint32_t kFrameTopPrims = 64;  // k_frame: a BVH scene of <= 64 primitives keeps their records in LDS
+constexpr uint32_t kFrameTopNodes = 64;  // k_frame: LDS copy of the first 64 nodes (4 KB per block)
+constexpr uint32_t kBvhSmall = 256u * 1024u;  // == scene.h bvh_max_leaf's one-primitive-leaf range
+constexpr uint32_t kMaxChunkShift = 5;  // k_paths chunks of at most 32 pixels (LDS: 1.5 KB state per wave)
+// and at least 1: a small row shard of an N-GPU run starts with 4-pixel chunks (N = 8: +2-5 % over 8) and
+// ends with 2- and 1-pixel ones — a chunk runs all frames of a launch (N x 64), so its length, not its
+// pixel count, sets the launch's tail
+constexpr uint32_t kMinChunkShift = 0;
+
+// k_paths work plan: n[i] chunks of 1 << shift[i] pixels starting at pixel start[i] (start[0] = 0).
+// Flat scenes: the first tier's chunks are handed out in `order` (chunk indices, longest first) once a
+// launch has recorded each one's cost in `cost` (launch_paths, k_chunk_order); nullptr: pixel order,
+// no recording.
+struct ChunkPlan {
+    uint32_t n[3];
+    uint32_t start[3];
+    uint32_t shift[3];
+    const uint32_t* order;
+    uint16_t* cost;
+};
+
+constexpr uint32_t kFrameRun = 128;          // k_frame: pixels per work unit, flat scenes
+constexpr uint32_t kFrameRunBvh = 64;        // ... BVH scenes
+constexpr uint32_t kFrameLdsStackMax = 16;   // k_frame kSmall: LDS stack entries per lane at most (8 B each)
+// pixels per work unit of k_frame: BVH scenes take shorter runs (their paths' lengths vary more, so
+// the frame's tail is shorter with finer units: App +4.5 %, C4 one frame per call +11 % at 64 vs 128;
+// flat scenes lose 33 % at 64)
+__host__ __device__ constexpr uint32_t frame_chunk(bool bvh) { return bvh ? kFrameRunBvh : kFrameRun; }
+constexpr int kFrameWavesSmall = 5;  // kSmall: its LDS (tree, primitives, stacks: ~31 KB per block) allows 5
+constexpr uint32_t kFrameSkyPerLane = 4;  // k_frame hit_mode 3: sky pixels per sky-block lane
+
 // persistent kernels' work queue: one head per XCD, each on its own 128-B line
 constexpr uint32_t kWorkHeads = 8;  // power of two, <= 8
 constexpr uint32_t kWorkStride = 32;
@@ -246,9 +279,15 @@ void launch_accumulate(const PassParams& p, hipStream_t s);
 bool launch_paths(const PassParams& p, bool stats, hipStream_t s);
 bool launch_frame(const PassParams& p, bool stats, hipStream_t s);
 // k_frame holds this BVH scene whole in LDS (its kSmall form)
-bool frame_small_scene(const PassParams& p, bool stats);
+inline bool frame_small_scene(const PassParams& p, bool stats) {
+    return p.nodes != nullptr && !stats && p.nee.n_emit == 0u && p.n_dev_nodes <= kFrameTopNodes &&
+           p.n_prims <= kFrameTopPrims && 4u * p.n_prims + 2u * p.n_mats <= 4u * kFrameTopPrims &&
+           p.stack_need <= kFrameLdsStackMax;
+}
 // ... and whether such a scene's one-frame launches take the live-pixel lists (frame_lists_scene)
-bool frame_small_scene_lists(const PassParams& p);
+inline bool frame_small_scene_lists(const PassParams& p) {
+    return p.shard_pixels / kFrameRunBvh > (uint32_t)kFrameWavesSmall * 4u * p.cu_count;
+}
 // the scenes k_frame's compacted lists are built for: all but the BVH scenes it holds in LDS (lists for
 // every scene measured slower)
 inline bool frame_lists_scene(const PassParams& p, bool stats) {

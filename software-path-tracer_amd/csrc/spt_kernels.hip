@@ -1266,18 +1266,9 @@ constexpr uint32_t kFlatPxRecs = 3;
 constexpr int kPathsWaves = 6;      // __launch_bounds__ waves per SIMD: flat k_frame, NEE k_paths
 constexpr int kPathsWavesFlat = 7;  // flat k_paths
 constexpr int kPathsWavesBvh = 7;   // BVH k_paths / k_frame: the latency-bound traversal (C4 +4 %, C5 +6.5 % vs 6)
-constexpr int kBvhSmallWaves = 8;   // BVH k_paths of scenes of <= kBvhSmall primitives (C4 +2.6 % over 7; C5: -5 %)
-constexpr uint32_t kFrameTopPrims = 64;  // k_frame: a BVH scene of <= 64 primitives keeps their records in LDS
-constexpr uint32_t kFrameTopNodes = 64;  // k_frame: LDS copy of the first 64 nodes (4 KB per block)
 constexpr uint32_t kBvhTopNodes = 53;    // k_paths (7 waves/SIMD): LDS copy of the top 3 levels of the 4-wide tree and
                                          // half of the 4th (the LDS left at 7 blocks per CU: C5 +1.7 %, r05_zb)
 constexpr uint32_t kBvhTopNodes8 = 5;    // ... with 8 waves/SIMD (less LDS per block): the top 2 levels
-constexpr uint32_t kBvhSmall = 256u * 1024u;  // == scene.h bvh_max_leaf's one-primitive-leaf range
-constexpr uint32_t kMaxChunkShift = 5;  // k_paths chunks of at most 32 pixels (LDS: 1.5 KB state per wave)
-// and at least 1: a small row shard of an N-GPU run starts with 4-pixel chunks (N = 8: +2-5 % over 8) and
-// ends with 2- and 1-pixel ones — a chunk runs all frames of a launch (N x 64), so its length, not its
-// pixel count, sets the launch's tail
-constexpr uint32_t kMinChunkShift = 0;
 
 // Static profile builds (-DSPT_STATIC_PROFILE): asm comments between the sections of a k_paths step,
 // counted by scripts/static_profile.py (the markers constrain scheduling a little; analysis only)
@@ -1342,18 +1333,6 @@ __device__ __forceinline__ uint32_t pull_unit(uint32_t* __restrict__ work, uint3
 // measurement builds only (scripts/k_paths_timeline.py): every wave's start, last chunk and end
 __device__ unsigned long long g_tl[8192 * 4];
 #endif
-
-// k_paths work plan: n[i] chunks of 1 << shift[i] pixels starting at pixel start[i] (start[0] = 0).
-// Flat scenes: the first tier's chunks are handed out in `order` (chunk indices, longest first) once a
-// launch has recorded each one's cost in `cost` (launch_paths, k_chunk_order); nullptr: pixel order,
-// no recording.
-struct ChunkPlan {
-    uint32_t n[3];
-    uint32_t start[3];
-    uint32_t shift[3];
-    const uint32_t* order;
-    uint16_t* cost;
-};
 
 // BVH scenes: lanes advance their rays through the tree (trav_step) until this many lanes of the
 // wave wait — ray done, or no path while new slots are free — then those are shaded and refilled
@@ -1487,7 +1466,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             pxs = plan.shift[2];
             pix0 = plan.start[2] + ((chunk - plan.n[0] - plan.n[1]) << pxs);
         }
-        const uint32_t px = 1u << pxs;  // pixels of this chunk (4 to 32)
+        const uint32_t px = 1u << pxs;  // pixels of this chunk (1 to 32)
         const uint32_t npx = min(px, cam.shard_pixels - pix0);
         // Bounce 0 of every pixel, once per chunk. A pixel whose camera ray ends its path without an
         // RNG draw — a miss (the sky), or any hit when max_bounces <= 1 — is a *constant* pixel: every
@@ -2074,21 +2053,13 @@ __device__ __forceinline__ uint32_t rgba8(float4 a, float frames, float exposure
 // camera ray is traced as an ordinary segment. Lanes take pixels one at a time from the wave's
 // current run of frame_chunk() pixels, which the wave pulls from the per-XCD work heads.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t kFrameRun = 128;          // k_frame: pixels per work unit, flat scenes
-constexpr uint32_t kFrameRunBvh = 64;        // ... BVH scenes
 constexpr uint32_t kFrameBvhBatch = 24;        // k_frame: BVH lanes waiting before a shading round
 constexpr uint32_t kFrameBvhBatchLds = 64;   // ... for a scene held whole in LDS: one round per segment
-constexpr uint32_t kFrameLdsStackMax = 16;   // k_frame kSmall: LDS stack entries per lane at most (8 B each)
-// pixels per work unit of k_frame: BVH scenes take shorter runs (their paths' lengths vary more, so
-// the frame's tail is shorter with finer units: App +4.5 %, C4 one frame per call +11 % at 64 vs 128;
-// flat scenes lose 33 % at 64)
-__host__ __device__ constexpr uint32_t frame_chunk(bool bvh) { return bvh ? kFrameRunBvh : kFrameRun; }
 
 // kSmall (BVH scenes of <= kFrameTopNodes nodes and <= kFrameTopPrims primitives, the App's):
 // the whole scene and every lane's traversal stack live in LDS (the stack in the dynamic LDS, sized by
 // the host from the tree's deepest stack), so a traversal step touches no global memory: its LDS loads
 // no longer wait on the global stack's stores and reads (one vector-memory counter for both).
-constexpr int kFrameWavesSmall = 5;  // kSmall: its LDS (tree, primitives, stacks: ~31 KB per block) allows 5
 // kNee: next-event estimation (SPT_FLAG_NEE; the shadow ray is the lane's next segment, as in k_paths;
 // kNeeAll / kNeeNoSpheres as in k_paths);
 // run with kEnv = 2.
@@ -2577,7 +2548,10 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(const float4* __restri
 // host launchers
 #ifndef __HIPCC_RTC__
 }  // namespace spt
-#include "spt_jit.h"
+#include <cassert>
+#include <type_traits>
+
+#include "spt_launch_plan.h"
 namespace spt {
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -2586,24 +2560,34 @@ CameraParams camera_params(const PassParams& p) {
                         p.first_frame, p.n_sub, p.inv_w,       p.inv_h,        p.aspect, p.hit_cache, p.hit_mode,
                         p.live_rec, p.sky_pix, p.list_counts, 0u, p.rgba, p.rgba_frames, p.rgba_exposure};
 }
+// (the fields after env_h are read by k_paths and k_frame only)
+ShadeParams shade_params(const PassParams& p, uint32_t bounce) {
+    return ShadeParams{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, bounce, p.n_prims, p.n_mats,
+                       p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h, p.n_dev_nodes, p.stack,
+                       p.stack_stride, p.stack_tb};
+}
+
+// f(std::bool_constant<b>...) of run-time bools: for the kernels instantiated for every combination
+template <class F>
+void with_bools(F&& f) {
+    f();
+}
+template <class F, class... Bs>
+void with_bools(F&& f, bool b, Bs... rest) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 }  // namespace
 
 void launch_extend(const PassParams& p, uint32_t bounce, hipStream_t s) {
     const QueueBufs& q = p.q[bounce & 1u];
     const CameraParams cam = camera_params(p);
     const uint32_t* counts = p.counts + bounce * p.n_sub;
-    const dim3 grid(p.n_sub), block(kBlock);
-    if (bounce == 0) {
-        if (p.nodes)
-            k_extend<true, true><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, counts, p.sub_cap, cam);
-        else
-            k_extend<false, true><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, counts, p.sub_cap, cam);
-    } else {
-        if (p.nodes)
-            k_extend<true, false><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, counts, p.sub_cap, cam);
-        else
-            k_extend<false, false><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, counts, p.sub_cap, cam);
-    }
+    with_bools(
+        [&](auto bvh, auto primary) {
+            k_extend<bvh(), primary()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, counts, p.sub_cap, cam);
+        },
+        p.nodes != nullptr, bounce == 0);
 }
 
 void launch_extend_sorted(const PassParams& p, uint32_t bounce, hipStream_t s) {
@@ -2617,66 +2601,41 @@ void launch_extend_sorted(const PassParams& p, uint32_t bounce, hipStream_t s) {
     k_bin_count<<<p.n_sub, kBlock, 0, s>>>(q.o, q.d, counts, p.sub_cap, p.ray_keys, p.ray_bins, bp);
     k_bin_scan<<<1, kBlock, 0, s>>>(p.ray_bins, p.ray_cursor);
     k_bin_scatter<<<p.n_sub, kBlock, 0, s>>>(p.ray_keys, counts, p.sub_cap, p.ray_cursor, p.ray_perm);
-    if (p.nodes)
-        k_extend_sorted<true><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, p.ray_perm, p.ray_cursor);
-    else
-        k_extend_sorted<false><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, p.ray_perm, p.ray_cursor);
+    with_bools(
+        [&](auto bvh) {
+            k_extend_sorted<bvh()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, q.o, q.d, p.hit, p.ray_perm, p.ray_cursor);
+        },
+        p.nodes != nullptr);
 }
 
-void launch_shade(const PassParams& p, uint32_t bounce, hipStream_t s) {
-    const ShadeParams sp{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, bounce, p.n_prims, p.n_mats, p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h};
+namespace {
+// kBvh here only selects where the shading gathers read from: the LDS copy of a flat scene, or
+// global memory for a BVH scene (too many records to stage)
+void launch_shade_kernel(const PassParams& p, uint32_t bounce, bool fused, hipStream_t s) {
+    const ShadeParams sp = shade_params(p, bounce);
     const QueueBufs& cur = p.q[bounce & 1u];
     const QueueBufs& nxt = p.q[(bounce + 1u) & 1u];
-    const dim3 grid(p.n_sub), block(kBlock);
     const CameraParams cam = camera_params(p);
-#define SPT_SHADE(P, F, B)                                                                                          \
-    do {                                                                                                            \
-        if (p.nee.n_emit)                                                                                           \
-            k_shade<P, F, B, true><<<grid, block, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.hit, cur, nxt,     \
-                                                          p.radiance, p.counts, sp, cam, p.nee);                    \
-        else                                                                                                        \
-            k_shade<P, F, B><<<grid, block, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.hit, cur, nxt, p.radiance, \
-                                                    p.counts, sp, cam, p.nee);                                      \
-    } while (0)
-    // kBvh here only selects where the shading gathers read from: the LDS copy of a flat scene, or
-    // global memory for a BVH scene (too many records to stage)
-    if (p.nodes) {
-        if (bounce == 0) SPT_SHADE(true, false, true);
-        else SPT_SHADE(false, false, true);
-    } else {
-        if (bounce == 0) SPT_SHADE(true, false, false);
-        else SPT_SHADE(false, false, false);
-    }
+    with_bools(
+        [&](auto primary, auto fused_c, auto bvh, auto nee) {
+            k_shade<primary(), fused_c(), bvh(), nee()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.hit, cur, nxt,
+                                                                                p.radiance, p.counts, sp, cam, p.nee);
+        },
+        bounce == 0, fused, p.nodes != nullptr, p.nee.n_emit != 0u);
 }
+}  // namespace
 
-void launch_bounce(const PassParams& p, uint32_t bounce, hipStream_t s) {
-    const ShadeParams sp{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, bounce, p.n_prims, p.n_mats, p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h};
-    const QueueBufs& cur = p.q[bounce & 1u];
-    const QueueBufs& nxt = p.q[(bounce + 1u) & 1u];
-    const dim3 grid(p.n_sub), block(kBlock);
-    const CameraParams cam = camera_params(p);
-    if (p.nodes) {
-        if (bounce == 0) SPT_SHADE(true, true, true);
-        else SPT_SHADE(false, true, true);
-    } else {
-        if (bounce == 0) SPT_SHADE(true, true, false);
-        else SPT_SHADE(false, true, false);
-    }
-#undef SPT_SHADE
-}
+void launch_shade(const PassParams& p, uint32_t bounce, hipStream_t s) { launch_shade_kernel(p, bounce, false, s); }
+void launch_bounce(const PassParams& p, uint32_t bounce, hipStream_t s) { launch_shade_kernel(p, bounce, true, s); }
 
 void launch_trace_tail(const PassParams& p, uint32_t bounce, hipStream_t s) {
-    const ShadeParams sp{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, bounce, p.n_prims, p.n_mats, p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h};
+    const ShadeParams sp = shade_params(p, bounce);
     const QueueBufs& cur = p.q[bounce & 1u];
-    const dim3 grid(p.n_sub), block(kBlock);
-    if (p.nodes && p.nee.n_emit)
-        k_trace_tail<true, true><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
-    else if (p.nee.n_emit)
-        k_trace_tail<false, true><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
-    else if (p.nodes)
-        k_trace_tail<true><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
-    else
-        k_trace_tail<false><<<grid, block, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
+    with_bools(
+        [&](auto bvh, auto nee) {
+            k_trace_tail<bvh(), nee()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
+        },
+        p.nodes != nullptr, p.nee.n_emit != 0u);
 }
 
 // The first tier's chunks of a flat k_paths launch, longest first: chunk indices sorted by decreasing
@@ -2718,78 +2677,102 @@ __global__ __launch_bounds__(128) void k_chunk_order(const uint16_t* __restrict_
     for (uint32_t i = b0; i < b1; ++i) order[h[bucket(cost[i])][t]++] = i;
 }
 
+namespace {
+template <class K>
+const void* kp(K* kernel) {
+    return (const void*)kernel;
+}
+
+// The offline-compiled k_paths of a variant: every instantiation the library holds is named here, once.
+// nullptr: no such kernel (paths_variant never asks for one).
+const void* paths_kernel(const PathsVariant& v) {
+    const bool env = v.env == 1;
+    if (v.nee) {  // the sky's kind decided at run time (kEnv 2); BVH: the sphere sample compiled in only when needed
+        if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee != kNeeAll)) return nullptr;
+        if (!v.bvh) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll>);
+        if (v.nee == kNeeAll) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll>);
+        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres>);
+    }
+    if (v.env > 1) return nullptr;
+    if (v.simd_waves) {  // small BVH scenes: 8 waves per SIMD
+        if (v.simd_waves != kBvhSmallWaves || !v.bvh || v.stats || v.chan) return nullptr;
+        return env ? kp(k_paths<false, true, 1, 0, kBvhSmallWaves>) : kp(k_paths<false, true, 0, 0, kBvhSmallWaves>);
+    }
+    if (v.chan) {  // flat scenes, chunks of <= 16 pixels: the channel-lane kernel
+        if (v.bvh || v.stats) return nullptr;
+        return env ? kp(k_paths<false, false, 1, 0, 0, true>) : kp(k_paths<false, false, 0, 0, 0, true>);
+    }
+    if (v.stats) return v.bvh ? (env ? kp(k_paths<true, true, 1>) : kp(k_paths<true, true, 0>))
+                              : (env ? kp(k_paths<true, false, 1>) : kp(k_paths<true, false, 0>));
+    return v.bvh ? (env ? kp(k_paths<false, true, 1>) : kp(k_paths<false, true, 0>))
+                 : (env ? kp(k_paths<false, false, 1>) : kp(k_paths<false, false, 0>));
+}
+
+// ... and k_frame's: 16 without the fused resolve, 9 with it (kRgba has no stats form)
+const void* frame_kernel(const FrameVariant& v) {
+    const bool env = v.env == 1;
+    if (v.nee ? (v.env != 2 || v.small || (!v.bvh && v.nee != kNeeAll)) : v.env > 1) return nullptr;
+    if (v.small && (!v.bvh || v.stats)) return nullptr;
+    if (v.rgba) {
+        if (v.stats) return nullptr;
+        if (v.nee == kNeeNoSpheres) return kp(k_frame<false, true, 2, 0, false, kNeeNoSpheres, true>);
+        if (v.nee) return v.bvh ? kp(k_frame<false, true, 2, 0, false, kNeeAll, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, true>);
+        if (v.small) return env ? kp(k_frame<false, true, 1, 0, true, 0, true>) : kp(k_frame<false, true, 0, 0, true, 0, true>);
+        return v.bvh ? (env ? kp(k_frame<false, true, 1, 0, false, 0, true>) : kp(k_frame<false, true, 0, 0, false, 0, true>))
+                     : (env ? kp(k_frame<false, false, 1, 0, false, 0, true>) : kp(k_frame<false, false, 0, 0, false, 0, true>));
+    }
+    if (v.nee == kNeeNoSpheres) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeNoSpheres>) : kp(k_frame<false, true, 2, 0, false, kNeeNoSpheres>);
+    if (v.nee && v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeAll>) : kp(k_frame<false, true, 2, 0, false, kNeeAll>);
+    if (v.nee) return v.stats ? kp(k_frame<true, false, 2, 0, false, kNeeAll>) : kp(k_frame<false, false, 2, 0, false, kNeeAll>);
+    if (v.small) return env ? kp(k_frame<false, true, 1, 0, true>) : kp(k_frame<false, true, 0, 0, true>);
+    if (v.stats) return v.bvh ? (env ? kp(k_frame<true, true, 1>) : kp(k_frame<true, true, 0>))
+                              : (env ? kp(k_frame<true, false, 1>) : kp(k_frame<true, false, 0>));
+    return v.bvh ? (env ? kp(k_frame<false, true, 1>) : kp(k_frame<false, true, 0>))
+                 : (env ? kp(k_frame<false, false, 1>) : kp(k_frame<false, false, 0>));
+}
+
+// the specialized kernel of a variant on the current device, or nullptr: none, not compiled yet, or not buildable
+hipFunction_t jit_kernel(JitKind k, const PassParams& p) {
+    return k.kind < 0 ? nullptr : jit_function(k.kind, k.env, p.jit_shape, nullptr, p.jit_wait != 0u);
+}
+// blocks resident per CU of the specialized kernel if there is one, else of `kernel`
+int blocks_per_cu(hipFunction_t fn, const void* kernel, size_t lds) {
+    int per_cu = 0;
+    const hipError_t occ = fn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds);
+    return occ != hipSuccess || per_cu < 1 ? 1 : per_cu;
+}
+// Launch the specialized kernel, or `kernel` if there is none or its launch fails; true: the specialized one ran.
+// (A launch error stays in the runtime's last-error state: spt_render reports it.)
+bool launch_persistent(hipFunction_t fn, const void* kernel, uint32_t grid, size_t lds, void** args, hipStream_t s) {
+    if (fn && hipModuleLaunchKernel(fn, grid, 1, 1, kBlock, 1, 1, (unsigned)lds, s, args, nullptr) == hipSuccess) return true;
+    assert(kernel && "no such instantiation");
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(kBlock), args, lds, s);
+    return false;
+}
+}  // namespace
+
 bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
-    const ShadeParams sp{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, 0u, p.n_prims, p.n_mats, p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h, p.n_dev_nodes, p.stack, p.stack_stride, p.stack_tb};
-    const CameraParams cam = camera_params(p);
+    ShadeParams sp = shade_params(p, 0u);
+    CameraParams cam = camera_params(p);
     const bool bvh = p.nodes != nullptr;
     const size_t lds_scene = bvh ? 0 : sizeof(float4) * 3u * p.n_prims;  // make_shade_recs
-    const int env = p.env ? 1 : 0;
-    const void* kernels[2][2][2] = {
-        {{(const void*)k_paths<false, false, 0>, (const void*)k_paths<false, false, 1>},
-         {(const void*)k_paths<false, true, 0>, (const void*)k_paths<false, true, 1>}},
-        {{(const void*)k_paths<true, false, 0>, (const void*)k_paths<true, false, 1>},
-         {(const void*)k_paths<true, true, 0>, (const void*)k_paths<true, true, 1>}}};
-    // NEE (p.nee.n_emit > 0): the kNee instantiations, the sky's kind decided at run time (kEnv 2)
-    const bool nee = p.nee.n_emit != 0u;
-    const bool nee_bvh_all = p.nee.spheres != 0u;  // BVH: the sphere sample compiled in only when needed
-    const void* nee_kernels[2][2] = {{(const void*)k_paths<false, false, 2, 0, 0, false, kNeeAll>,
-                                      nee_bvh_all ? (const void*)k_paths<false, true, 2, 0, 0, false, kNeeAll>
-                                                  : (const void*)k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres>},
-                                     {(const void*)k_paths<true, false, 2, 0, 0, false, kNeeAll>,
-                                      nee_bvh_all ? (const void*)k_paths<true, true, 2, 0, 0, false, kNeeAll>
-                                                  : (const void*)k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres>}};
-    // small BVH scenes: the 8-wave variant (k_paths kSimdWaves)
-    const bool bvh8 = bvh && !stats && !nee && p.n_prims <= kBvhSmall;
-    const void* kernel = nee ? nee_kernels[stats ? 1 : 0][bvh ? 1 : 0]
-                         : bvh8 ? (env ? (const void*)k_paths<false, true, 1, 0, kBvhSmallWaves> : (const void*)k_paths<false, true, 0, 0, kBvhSmallWaves>)
-                              : kernels[stats ? 1 : 0][bvh ? 1 : 0][env];
-    // a flat scene's kernel compiled for its shape (spt_jit.hip), unless it cannot be built
-    hipFunction_t fn = (p.jit_shape && !bvh && !stats)
-                           ? jit_function(nee ? kJitPathsNee : kJitPaths, nee ? 2 : env, p.jit_shape, nullptr, p.jit_wait != 0u)
-                           : nullptr;
-    // persistent grid: as many blocks as are resident at once (the waves then pull chunks)
-    int per_cu = 0;
-    const hipError_t occ = fn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds_scene)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds_scene);
-    if (occ != hipSuccess || per_cu < 1) per_cu = 1;
-    const uint32_t resident_waves = (uint32_t)per_cu * p.cu_count * (kBlock / 64u);
-    // chunk plan: the largest chunks (32/16/8 pixels) that still give every resident wave >= 8, then
-    // ~chunks_per_wave chunks per wave of each smaller size at the end (a wave's last chunk is the
-    // launch's tail). A small row shard of a multi-GPU run gets small chunks, which it needs to fill
-    // the GPU at all. spt_tuning.px_shift forces one size.
-    ChunkPlan plan{};
-    const uint32_t P = p.shard_pixels;
-    uint32_t s0 = kMaxChunkShift;
-    while (s0 > kMinChunkShift && ((uint64_t)P >> s0) < 8ull * resident_waves) --s0;
-    if (p.px_shift) s0 = std::max(kMinChunkShift, std::min(p.px_shift, kMaxChunkShift));
-    const uint32_t s1 = std::max(kMinChunkShift, s0 - 1u), s2 = std::max(kMinChunkShift, s0 - 2u);
-    plan.shift[0] = s0;
-    plan.shift[1] = s1;
-    plan.shift[2] = s2;
-    if (p.px_shift || s0 == kMinChunkShift) {
-        plan.n[0] = (P + (1u << s0) - 1u) >> s0;
-    } else {
-        const uint64_t tail = (uint64_t)p.chunks_per_wave * resident_waves;  // chunks per small tier
-        const uint32_t c_px = (uint32_t)std::min<uint64_t>(P, tail << s2);
-        const uint32_t b_px = (uint32_t)std::min<uint64_t>(P - c_px, tail << s1) & ~((1u << s1) - 1u);
-        const uint32_t a_px = (P - c_px - b_px) & ~((1u << s0) - 1u);
-        plan.n[0] = a_px >> s0;
-        plan.n[1] = b_px >> s1;
-        plan.start[1] = a_px;
-        plan.start[2] = a_px + b_px;
-        plan.n[2] = (P - a_px - b_px + (1u << s2) - 1u) >> s2;
-    }
-    const uint32_t chunks = plan.n[0] + plan.n[1] + plan.n[2];
+    // The channel-lane kernel (kChan) is chosen by the plan's first chunk size, and the plan is made from
+    // the occupancy: so the occupancy asked here, which sizes the plan AND the grid, is that of the kernel
+    // without kChan (first_shift = kMaxChunkShift), also when the kChan kernel then runs. Whether asking
+    // the launched kernel for the grid would be better is not measured.
+    PathsVariant v = paths_variant(p, stats, kMaxChunkShift);
+    hipFunction_t fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    const int per_cu = blocks_per_cu(fn, paths_kernel(v), lds_scene);
+    ChunkPlan plan = make_chunk_plan(p.shard_pixels, resident_waves(per_cu, p.cu_count), p.chunks_per_wave, p.px_shift);
     // A launch records each first-tier chunk's cost, k_chunk_order sorts them behind it (stream order),
     // and the launches of the same plan that follow hand the first tier out longest first (C2 +4 %, with
     // NEE +3 %, the simulated N = 8 shard +5 %: profiles/r05_n_ab_chunk_order.txt; BVH scenes since
     // round 6: C4 +4.5 %, C4 NEE +8 %, profiles/r06_j_ab_bvh_chunk_order.txt, r06_p_ab_bvh_nee_cost.txt).
-    // The key names the plan (first-tier chunks, pixels, chunk size); a scene or configuration change
-    // clears it (spt_capi.hip). The order changes which wave traces a chunk, never a result.
-    plan.order = nullptr;
-    plan.cost = nullptr;
+    // The key names the plan; a scene or configuration change clears it (spt_capi.hip). The order
+    // changes which wave traces a chunk, never a result.
     bool record = false;
-    const uint64_t order_key = ((uint64_t)plan.n[0] << 37) | ((uint64_t)P << 5) | plan.shift[0];
+    const uint64_t order_key = chunk_order_key(plan, p.shard_pixels);
     if (!p.px_shift && p.chunk_cost && p.chunk_order && plan.n[0] > 1u) {
         if (*p.chunk_order_key == order_key) {
             plan.order = p.chunk_order;
@@ -2798,197 +2781,38 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
             record = true;
         }
     }
-    auto after = [&]() {
-        if (!record) return;
+    v = paths_variant(p, stats, plan.shift[0]);
+    if (v.chan) fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    const uint32_t grid = paths_grid(plan, bvh, per_cu, p.cu_count);
+    void* args[] = {(void*)&p.prims, (void*)&p.mats, (void*)&p.nodes, (void*)&p.n_prims, (void*)&p.accum, (void*)&p.totals,
+                    (void*)&p.work, (void*)&p.work_next, &sp, &cam, (void*)&p.n_frames, &plan, (void*)&p.nee};
+    const bool specialized = launch_persistent(fn, paths_kernel(v), grid, lds_scene, args, s);
+    if (record) {
         k_chunk_order<<<1, 128, 0, s>>>(p.chunk_cost, plan.n[0], p.chunk_order);
         // the order is only valid once both launches were enqueued (peek: spt_render reports the error)
         if (hipPeekAtLastError() == hipSuccess) *p.chunk_order_key = order_key;
-    };
-    const uint32_t needed = (chunks + kBlock / 64u - 1u) / (kBlock / 64u);
-    // a flat scene whose chunks are all <= 16 pixels (a small row shard): the channel-lane kernel
-    const bool chan = !bvh && !stats && !nee && plan.shift[0] < kMaxChunkShift;
-    if (chan) fn = p.jit_shape ? jit_function(kJitPathsChan, env, p.jit_shape, nullptr, p.jit_wait != 0u) : nullptr;
-    // (a BVH scene's global traversal stacks are sized for kMaxResidentWaves per CU)
-    if (bvh) per_cu = std::min<int>(per_cu, (int)(kMaxResidentWaves / (kBlock / 64u)));
-    const uint32_t grid = std::min<uint32_t>(needed, (uint32_t)per_cu * p.cu_count);
-    if (fn) {
-        const float4 *prims = p.prims, *mats = p.mats, *nodes = p.nodes;
-        uint32_t n_prims = p.n_prims, n_frames = p.n_frames;
-        float4* accum = p.accum;
-        unsigned long long* totals = p.totals;
-        uint32_t *work = p.work, *work_next = p.work_next;
-        ShadeParams sp_arg = sp;
-        CameraParams cam_arg = cam;
-        NeeParams nee_arg = p.nee;
-        void* args[] = {&prims, &mats, &nodes, &n_prims, &accum, &totals, &work, &work_next,
-                        &sp_arg, &cam_arg, &n_frames, &plan, &nee_arg};
-        if (hipModuleLaunchKernel(fn, grid, 1, 1, kBlock, 1, 1, (unsigned)lds_scene, s, args, nullptr) == hipSuccess) {
-            after();
-            return true;
-        }
     }
-#define SPT_PATHS(S, B, E)                                                                                          \
-    k_paths<S, B, E><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, \
-                                                     cam, p.n_frames, plan, p.nee)
-#define SPT_PATHS_NEE(S, B, N) \
-    k_paths<S, B, 2, 0, 0, false, N><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.n_frames, plan, p.nee)
-#define SPT_PATHS_ENV(S, B)      \
-    do {                         \
-        if (env) SPT_PATHS(S, B, 1); \
-        else SPT_PATHS(S, B, 0); \
-    } while (0)
-    if (nee) {
-        if (stats && bvh && nee_bvh_all) SPT_PATHS_NEE(true, true, kNeeAll);
-        else if (stats && bvh) SPT_PATHS_NEE(true, true, kNeeNoSpheres);
-        else if (stats) SPT_PATHS_NEE(true, false, kNeeAll);
-        else if (bvh && nee_bvh_all) SPT_PATHS_NEE(false, true, kNeeAll);
-        else if (bvh) SPT_PATHS_NEE(false, true, kNeeNoSpheres);
-        else SPT_PATHS_NEE(false, false, kNeeAll);
-    } else if (bvh8) {
-        if (env) k_paths<false, true, 1, 0, kBvhSmallWaves><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.n_frames, plan, p.nee);
-        else k_paths<false, true, 0, 0, kBvhSmallWaves><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.n_frames, plan, p.nee);
-    } else if (bvh) {
-        if (stats) SPT_PATHS_ENV(true, true);
-        else SPT_PATHS_ENV(false, true);
-    } else if (chan) {
-        if (env) k_paths<false, false, 1, 0, 0, true><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.n_frames, plan, p.nee);
-        else k_paths<false, false, 0, 0, 0, true><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.n_frames, plan, p.nee);
-    } else {
-        if (stats) SPT_PATHS_ENV(true, false);
-        else SPT_PATHS_ENV(false, false);
-    }
-    after();
-#undef SPT_PATHS_ENV
-#undef SPT_PATHS_NEE
-#undef SPT_PATHS
-    return false;
-}
-
-constexpr uint32_t kFrameSkyPerLane = 4;  // k_frame hit_mode 3: sky pixels per sky-block lane
-
-bool frame_small_scene(const PassParams& p, bool stats) {
-    return p.nodes != nullptr && !stats && p.nee.n_emit == 0u && p.n_dev_nodes <= kFrameTopNodes &&
-           p.n_prims <= kFrameTopPrims && 4u * p.n_prims + 2u * p.n_mats <= 4u * kFrameTopPrims &&
-           p.stack_need <= kFrameLdsStackMax;
-}
-
-bool frame_small_scene_lists(const PassParams& p) {
-    return p.shard_pixels / kFrameRunBvh > (uint32_t)kFrameWavesSmall * 4u * p.cu_count;
-}
-
-template <bool kRgba>
-bool launch_frame_t(const PassParams& p, bool stats, hipStream_t s) {
-    const ShadeParams sp{p.sky_enabled, p.flags, p.max_bounces, p.rr_depth, p.sub_cap, 0u, p.n_prims, p.n_mats, p.flat_ends, p.horizon, p.zenith, p.env, p.env_w, p.env_h, p.n_dev_nodes, p.stack, p.stack_stride, p.stack_tb};
-    CameraParams cam = camera_params(p);
-    const bool bvh = p.nodes != nullptr;
-    // a BVH scene held whole in LDS, with every lane's traversal stack (k_frame kSmall)
-    const bool nee = p.nee.n_emit != 0u;  // the kNee instantiations (kEnv 2, no LDS-only small-scene form)
-    const bool nee_bvh_all = p.nee.spheres != 0u;  // (k_paths)
-    const bool small = frame_small_scene(p, stats);
-    const size_t lds_scene = bvh ? (small ? sizeof(uint2) * kBlock * std::max(1u, p.stack_need) : 0)
-                                 : sizeof(float4) * 3u * p.n_prims;  // LDS stacks / make_shade_recs
-    const int env = p.env ? 1 : 0;
-    const void* kernels[2][2][2] = {
-        {{(const void*)k_frame<false, false, 0>, (const void*)k_frame<false, false, 1>},
-         {(const void*)k_frame<false, true, 0>, (const void*)k_frame<false, true, 1>}},
-        {{(const void*)k_frame<true, false, 0>, (const void*)k_frame<true, false, 1>},
-         {(const void*)k_frame<true, true, 0>, (const void*)k_frame<true, true, 1>}}};
-    const void* nee_kernels[2][2] = {{(const void*)k_frame<false, false, 2, 0, false, kNeeAll>,
-                                      nee_bvh_all ? (const void*)k_frame<false, true, 2, 0, false, kNeeAll>
-                                                  : (const void*)k_frame<false, true, 2, 0, false, kNeeNoSpheres>},
-                                     {(const void*)k_frame<true, false, 2, 0, false, kNeeAll>,
-                                      nee_bvh_all ? (const void*)k_frame<true, true, 2, 0, false, kNeeAll>
-                                                  : (const void*)k_frame<true, true, 2, 0, false, kNeeNoSpheres>}};
-    hipFunction_t fn = (p.jit_shape && !bvh && !stats)
-                           ? jit_function(kRgba ? (nee ? kJitFrameNeeRgba : kJitFrameRgba) : (nee ? kJitFrameNee : kJitFrame),
-                                          nee ? 2 : env, p.jit_shape, nullptr, p.jit_wait != 0u)
-                           : nullptr;
-    int per_cu = 0;
-    const hipError_t occ =
-        fn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds_scene)
-           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu,
-                                                          nee ? nee_kernels[stats ? 1 : 0][bvh ? 1 : 0]
-                                                          : small ? (env ? (const void*)k_frame<false, true, 1, 0, true>
-                                                                       : (const void*)k_frame<false, true, 0, 0, true>)
-                                                                : kernels[stats ? 1 : 0][bvh ? 1 : 0][env],
-                                                          kBlock, lds_scene);
-    if (occ != hipSuccess || per_cu < 1) per_cu = 1;
-    // persistent grid, but no more waves than runs of frame_chunk() pixels
-    // (hit_mode 3: the live pixels are the work units; the sky pixels go to blocks of their own, below)
-    const bool lists = p.hit_mode == 3u;
-    const uint32_t units = lists ? p.live_pixels : p.shard_pixels;
-    const uint32_t runs = (units + frame_chunk(bvh) - 1u) / frame_chunk(bvh);
-    constexpr uint32_t kFrameRunsPerWave = 4;
-    // Flat scenes: a one-frame launch is bound by its lanes' longest chains of path segments, not by
-    // throughput (VALU issue ~0.34), so fewer resident waves, each taking ~kFrameRunsPerWave
-    // runs, finish the frame sooner than full occupancy (Cornell one frame per call: 720p 90 -> 67 us,
-    // 1080p 113 -> 98 us, 4K 238 -> 234 us). BVH scenes keep full occupancy (their latency-bound
-    // traversal needs the waves: C4 -4 % with the rule).
-    constexpr uint32_t kFrameListsRpw = 2;  // flat scenes with lists: runs per wave, counted over the whole image's runs
-    if (!bvh) {
-        // with lists (hit_mode 3) the rule counts the whole image's runs, so a wave takes about
-        // kFrameListsRpw x the live fraction runs of live pixels
-        const uint32_t rule_runs = lists ? (p.shard_pixels + frame_chunk(bvh) - 1u) / frame_chunk(bvh) : runs;
-        const uint32_t rpw = lists ? kFrameListsRpw : kFrameRunsPerWave;
-        const uint32_t want_blocks = rule_runs / (rpw * (kBlock / 64u));
-        per_cu = std::max(1, std::min(per_cu, (int)((want_blocks + p.cu_count / 2u) / std::max(1u, p.cu_count))));
-    }
-    const uint32_t needed = (runs + kBlock / 64u - 1u) / (kBlock / 64u);
-    if (bvh) per_cu = std::min<int>(per_cu, (int)(kMaxResidentWaves / (kBlock / 64u)));  // global stacks' sizing
-    const uint32_t path_grid = std::max(1u, std::min<uint32_t>(needed, (uint32_t)per_cu * p.cu_count));
-    // hit_mode 3: the sky pixels' blocks, kFrameSkyPerLane pixels per lane, launched ahead of the
-    // tracing blocks (k_frame: blockIdx < sky_blocks)
-    const uint32_t n_sky = lists ? p.shard_pixels - p.live_pixels : 0u;
-    cam.sky_blocks = (n_sky + kBlock * kFrameSkyPerLane - 1u) / (kBlock * kFrameSkyPerLane);
-    const uint32_t grid = path_grid + cam.sky_blocks;
-    if (fn) {
-        const float4 *prims = p.prims, *mats = p.mats, *nodes = p.nodes;
-        uint32_t n_prims = p.n_prims;
-        float4* accum = p.accum;
-        unsigned long long* totals = p.totals;
-        uint32_t *work = p.work, *work_next = p.work_next;
-        ShadeParams sp_arg = sp;
-        CameraParams cam_arg = cam;
-        NeeParams nee_arg = p.nee;
-        void* args[] = {&prims, &mats, &nodes, &n_prims, &accum, &totals, &work, &work_next, &sp_arg, &cam_arg, &nee_arg};
-        if (hipModuleLaunchKernel(fn, grid, 1, 1, kBlock, 1, 1, (unsigned)lds_scene, s, args, nullptr) == hipSuccess)
-            return true;
-    }
-    // (kRgba: launch_frame passes stats = false, and S && !kRgba keeps the stats kernels single)
-#define SPT_FRAME(S, B, E) \
-    k_frame<(S) && !kRgba, B, E, 0, false, 0, kRgba><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.nee)
-#define SPT_FRAME_NEE(S, B, N) \
-    k_frame<(S) && !kRgba, B, 2, 0, false, N, kRgba><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.nee)
-#define SPT_FRAME_ENV(S, B)          \
-    do {                             \
-        if (env) SPT_FRAME(S, B, 1); \
-        else SPT_FRAME(S, B, 0);     \
-    } while (0)
-    if (nee) {
-        if (stats && bvh && nee_bvh_all) SPT_FRAME_NEE(true, true, kNeeAll);
-        else if (stats && bvh) SPT_FRAME_NEE(true, true, kNeeNoSpheres);
-        else if (stats) SPT_FRAME_NEE(true, false, kNeeAll);
-        else if (bvh && nee_bvh_all) SPT_FRAME_NEE(false, true, kNeeAll);
-        else if (bvh) SPT_FRAME_NEE(false, true, kNeeNoSpheres);
-        else SPT_FRAME_NEE(false, false, kNeeAll);
-    } else if (small) {
-        if (env) k_frame<false, true, 1, 0, true, 0, kRgba><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.nee);
-        else k_frame<false, true, 0, 0, true, 0, kRgba><<<grid, kBlock, lds_scene, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.accum, p.totals, p.work, p.work_next, sp, cam, p.nee);
-    } else if (bvh) {
-        if (stats) SPT_FRAME_ENV(true, true);
-        else SPT_FRAME_ENV(false, true);
-    } else {
-        if (stats) SPT_FRAME_ENV(true, false);
-        else SPT_FRAME_ENV(false, false);
-    }
-#undef SPT_FRAME_ENV
-#undef SPT_FRAME_NEE
-#undef SPT_FRAME
-    return false;
+    return specialized;
 }
 
 bool launch_frame(const PassParams& p, bool stats, hipStream_t s) {
-    return p.rgba ? launch_frame_t<true>(p, false, s) : launch_frame_t<false>(p, stats, s);
+    ShadeParams sp = shade_params(p, 0u);
+    CameraParams cam = camera_params(p);
+    const FrameVariant v = frame_variant(p, stats);
+    const size_t lds_scene = v.bvh ? (v.small ? sizeof(uint2) * kBlock * std::max(1u, p.stack_need) : 0)
+                                   : sizeof(float4) * 3u * p.n_prims;  // LDS stacks / make_shade_recs
+    const hipFunction_t fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    // Without a specialized kernel the occupancy asked is that of the variant WITHOUT the fused resolve
+    // (kRgba), also when the kRgba kernel then runs: its grid is sized as the plain frame's. Whether
+    // asking the launched kernel would be better is not measured.
+    FrameVariant asked = v;
+    asked.rgba = false;
+    const int per_cu = blocks_per_cu(fn, frame_kernel(asked), lds_scene);
+    const FrameGrid g = frame_grid(p.shard_pixels, p.live_pixels, p.hit_mode, v.bvh, per_cu, p.cu_count);
+    cam.sky_blocks = g.sky_blocks;
+    void* args[] = {(void*)&p.prims, (void*)&p.mats, (void*)&p.nodes, (void*)&p.n_prims, (void*)&p.accum, (void*)&p.totals,
+                    (void*)&p.work, (void*)&p.work_next, &sp, &cam, (void*)&p.nee};
+    return launch_persistent(fn, frame_kernel(v), g.path_grid + g.sky_blocks, lds_scene, args, s);
 }
 
 void launch_accumulate(const PassParams& p, hipStream_t s) {

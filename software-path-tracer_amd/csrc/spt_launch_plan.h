@@ -1,0 +1,155 @@
+// spt_launch_plan.h — what launch_paths / launch_frame decide before they launch: which instantiation
+// of k_paths / k_frame runs, its run-time compiled form (spt_jit.h), the chunk plan and the grids.
+// Pure host functions, no HIP runtime calls: tests/cpp/test_launch_plan.cpp checks them without a
+// GPU. Every variant computes the same image bits, so a wrong choice here shows only as lost speed.
+// Not part of the kernel source compiled at run time. Internal.
+#pragma once
+
+#include <algorithm>
+
+#include "spt_jit.h"
+#include "spt_kernels.h"
+
+namespace spt {
+
+// k_paths<stats, bvh, env, shape, simd_waves, chan, nee> / k_frame<stats, bvh, env, shape, small, nee, rgba>
+struct PathsVariant {
+    bool stats, bvh;
+    int env;         // 0 gradient sky, 1 environment map, 2 decided at run time (the NEE kernels)
+    int simd_waves;  // 0, or kBvhSmallWaves: the 8-wave kernel of small BVH scenes
+    bool chan;       // the channel-lane kernel of flat scenes whose chunks are all <= 16 pixels (a small row shard)
+    int nee;         // 0, kNeeAll, or kNeeNoSpheres (a BVH scene without sphere lights)
+};
+struct FrameVariant {
+    bool stats, bvh;
+    int env;
+    bool small;  // a BVH scene held whole in LDS (frame_small_scene)
+    int nee;
+    bool rgba;   // the resolve fused into the frame; it has no stats form
+};
+
+inline int nee_variant(const PassParams& p) {
+    if (p.nee.n_emit == 0u) return 0;
+    return p.nodes != nullptr && p.nee.spheres == 0u ? kNeeNoSpheres : kNeeAll;
+}
+// first_shift: the chunk plan's shift[0]
+inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t first_shift) {
+    const bool bvh = p.nodes != nullptr;
+    const int nee = nee_variant(p);
+    PathsVariant v{stats, bvh, nee ? 2 : (p.env ? 1 : 0), 0, false, nee};
+    if (bvh && !stats && !nee && p.n_prims <= kBvhSmall) v.simd_waves = kBvhSmallWaves;
+    v.chan = !bvh && !stats && !nee && first_shift < kMaxChunkShift;
+    return v;
+}
+inline FrameVariant frame_variant(const PassParams& p, bool stats) {
+    const bool rgba = p.rgba != nullptr;
+    stats = stats && !rgba;
+    const int nee = nee_variant(p);
+    return FrameVariant{stats, p.nodes != nullptr, nee ? 2 : (p.env ? 1 : 0), frame_small_scene(p, stats), nee, rgba};
+}
+
+// The variant's kernel compiled for a flat scene's shape (spt_jit.h), and the env to ask for it with;
+// kind < 0: there is none (a BVH scene, statistics, or no shape), the offline-compiled kernel runs.
+struct JitKind {
+    int kind, env;
+};
+constexpr JitKind kJitNone{-1, 0};
+inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
+    if (!shape || v.bvh || v.stats) return kJitNone;
+    return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
+}
+inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
+    if (!shape || v.bvh || v.stats) return kJitNone;
+    return JitKind{v.rgba ? (v.nee ? kJitFrameNeeRgba : kJitFrameRgba) : (v.nee ? kJitFrameNee : kJitFrame), v.env};
+}
+// The kinds a flat scene's renders may ask for: compiled ahead by spt_set_scene, waited for by
+// spt_specialize_scene. (The two kRgba kinds are not in the list: a fused resolve compiles its kernel
+// on first use. Adding them here is the whole change, but it changes what a scene change compiles.)
+struct JitKindList {
+    int n;
+    JitKind k[3];
+};
+inline JitKindList jit_kinds_of_scene(bool nee, int env) {
+    if (nee) return {2, {{kJitPathsNee, 2}, {kJitFrameNee, 2}}};
+    return {3, {{kJitPaths, env}, {kJitFrame, env}, {kJitPathsChan, env}}};
+}
+
+// k_paths chunk plan (order and cost unset): the largest chunks (32/16/8 ... pixels) that still give
+// every resident wave >= 8, then ~chunks_per_wave chunks per wave of each smaller size at the end (a
+// wave's last chunk is the launch's tail). A small row shard of a multi-GPU run gets small chunks,
+// which it needs to fill the GPU at all. px_shift (spt_tuning) forces one size.
+inline ChunkPlan make_chunk_plan(uint32_t P, uint32_t resident_waves, uint32_t chunks_per_wave, uint32_t px_shift) {
+    ChunkPlan plan{};
+    uint32_t s0 = kMaxChunkShift;
+    while (s0 > kMinChunkShift && ((uint64_t)P >> s0) < 8ull * resident_waves) --s0;
+    if (px_shift) s0 = std::max(kMinChunkShift, std::min(px_shift, kMaxChunkShift));
+    const uint32_t s1 = s0 > kMinChunkShift ? s0 - 1u : kMinChunkShift, s2 = s1 > kMinChunkShift ? s1 - 1u : kMinChunkShift;
+    plan.shift[0] = s0;
+    plan.shift[1] = s1;
+    plan.shift[2] = s2;
+    if (px_shift || s0 == kMinChunkShift) {
+        plan.n[0] = (uint32_t)(((uint64_t)P + (1u << s0) - 1u) >> s0);
+        return plan;
+    }
+    const uint64_t tail = (uint64_t)chunks_per_wave * resident_waves;  // chunks per small tier
+    const uint32_t c_px = (uint32_t)std::min<uint64_t>(P, tail << s2);
+    const uint32_t b_px = (uint32_t)std::min<uint64_t>(P - c_px, tail << s1) & ~((1u << s1) - 1u);
+    const uint32_t a_px = (P - c_px - b_px) & ~((1u << s0) - 1u);
+    plan.n[0] = a_px >> s0;
+    plan.n[1] = b_px >> s1;
+    plan.start[1] = a_px;
+    plan.start[2] = a_px + b_px;
+    plan.n[2] = (P - a_px - b_px + (1u << s2) - 1u) >> s2;
+    return plan;
+}
+// names the plan a recorded first-tier order belongs to (first-tier chunks, pixels, chunk size)
+inline uint64_t chunk_order_key(const ChunkPlan& plan, uint32_t P) {
+    return ((uint64_t)plan.n[0] << 37) | ((uint64_t)P << 5) | plan.shift[0];
+}
+
+constexpr uint32_t kBlockWaves = kBlock / 64u;
+// waves resident at once, from the occupancy query's blocks per CU
+inline uint32_t resident_waves(int per_cu, uint32_t cu_count) { return (uint32_t)per_cu * cu_count * kBlockWaves; }
+// k_paths: a persistent grid, as many blocks as are resident at once (the waves then pull chunks), but
+// no more waves than chunks (a BVH scene's global traversal stacks are sized for kMaxResidentWaves per CU)
+inline uint32_t paths_grid(const ChunkPlan& plan, bool bvh, int per_cu, uint32_t cu_count) {
+    const uint32_t chunks = plan.n[0] + plan.n[1] + plan.n[2];
+    const uint32_t needed = (chunks + kBlockWaves - 1u) / kBlockWaves;
+    if (bvh) per_cu = std::min<int>(per_cu, (int)(kMaxResidentWaves / kBlockWaves));
+    return std::min<uint32_t>(needed, (uint32_t)per_cu * cu_count);
+}
+
+// k_frame: a persistent grid, but no more waves than runs of frame_chunk() pixels (hit_mode 3: the live
+// pixels are the work units; the sky pixels go to blocks of their own, kFrameSkyPerLane pixels per lane,
+// launched ahead of the tracing blocks: blockIdx < sky_blocks).
+// Flat scenes: a one-frame launch is bound by its lanes' longest chains of path segments, not by
+// throughput (VALU issue ~0.34), so fewer resident waves, each taking ~kFrameRunsPerWave
+// runs, finish the frame sooner than full occupancy (Cornell one frame per call: 720p 90 -> 67 us,
+// 1080p 113 -> 98 us, 4K 238 -> 234 us). BVH scenes keep full occupancy (their latency-bound
+// traversal needs the waves: C4 -4 % with the rule).
+constexpr uint32_t kFrameRunsPerWave = 4;
+constexpr uint32_t kFrameListsRpw = 2;  // flat scenes with lists: runs per wave, counted over the whole image's runs
+struct FrameGrid {
+    uint32_t path_grid, sky_blocks;
+};
+inline FrameGrid frame_grid(uint32_t shard_pixels, uint32_t live_pixels, uint32_t hit_mode, bool bvh, int per_cu,
+                            uint32_t cu_count) {
+    const bool lists = hit_mode == 3u;
+    const uint32_t units = lists ? live_pixels : shard_pixels;
+    const uint32_t runs = (units + frame_chunk(bvh) - 1u) / frame_chunk(bvh);
+    if (!bvh) {
+        // with lists (hit_mode 3) the rule counts the whole image's runs, so a wave takes about
+        // kFrameListsRpw x the live fraction runs of live pixels
+        const uint32_t rule_runs = lists ? (shard_pixels + frame_chunk(bvh) - 1u) / frame_chunk(bvh) : runs;
+        const uint32_t rpw = lists ? kFrameListsRpw : kFrameRunsPerWave;
+        const uint32_t want_blocks = rule_runs / (rpw * kBlockWaves);
+        per_cu = std::max(1, std::min(per_cu, (int)((want_blocks + cu_count / 2u) / std::max(1u, cu_count))));
+    }
+    const uint32_t needed = (runs + kBlockWaves - 1u) / kBlockWaves;
+    if (bvh) per_cu = std::min<int>(per_cu, (int)(kMaxResidentWaves / kBlockWaves));  // global stacks' sizing
+    const uint32_t n_sky = lists ? shard_pixels - live_pixels : 0u;
+    return FrameGrid{std::max(1u, std::min<uint32_t>(needed, (uint32_t)per_cu * cu_count)),
+                     (n_sky + kBlock * kFrameSkyPerLane - 1u) / (kBlock * kFrameSkyPerLane)};
+}
+
+}  // namespace spt

@@ -78,6 +78,17 @@ def test_stack_entry_code_is_a_lower_bound(exe):
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
 
 
+def test_launch_plan_picks_the_kernels_and_grids(exe):
+    """spt_launch_plan.h on the host: k_paths' chunk plan (tiling invariants over a sweep, exact tiers of
+    the benchmark shapes), the k_paths / k_frame variant and run-time compiled kind each kind of scene
+    runs, k_frame's grid rule, and the run-time compiled kinds' name expressions (spt_jit.h). Every
+    variant gives the same image, so no parity test sees a wrong choice."""
+    r = subprocess.run([os.path.join(ROOT, "tests", "cpp", "test_launch_plan")], capture_output=True, text=True,
+                       timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
+
+
 def test_device_sincos_matches_glibc(exe):
     """spt_device.h sincos_2pi (host build) vs glibc cos/sin on 2e7 reference-RNG draws: the float
     products the integrator uses must be identical."""
