@@ -221,9 +221,10 @@ int spt_get_frame_count(const spt_ctx* ctx, uint32_t* frame_count);
 /* Traces frames [first_frame, first_frame + n_frames): frame k is seeded with k + 1 exactly as
  * get_rng_state(.., m_frameCount + 1) (:61, :192-195), and adds each frame's radiance to the
  * accumulation buffer in frame order (:77-80). Asynchronous on the ctx stream, with one exception:
- * the first one-frame call after spt_set_scene / spt_update_prims / spt_configure stores the pixels'
- * camera hits and, for scenes that use the compacted live-pixel lists, waits for that frame to read
- * the live-pixel count back (once per change). The progressive renderer calls
+ * the first one-frame call after spt_set_scene / spt_update_prims / spt_configure / spt_set_camera
+ * stores the pixels' camera hits and, for scenes that use the compacted live-pixel lists, waits for that
+ * frame to read the live-pixel count back (once per change). A camera with SPT_CAMERA_JITTER has no
+ * such cache (its camera segments differ from frame to frame) and never waits. The progressive renderer calls
  * spt_render(ctx, frame_count, 1) once per App frame. */
 int spt_render(spt_ctx* ctx, uint32_t first_frame, uint32_t n_frames);
 int spt_synchronize(spt_ctx* ctx);
@@ -265,6 +266,42 @@ int spt_render_resolve_rgba8(spt_ctx* ctx, uint32_t first_frame, uint32_t n_fram
  * ceil(height/shard_count)*width RGBA pixels, in rank order (the layout of an all-gather /
  * gather into one tensor). Writes the full width*height RGBA image to `out` (device). */
 int spt_assemble_rows(spt_ctx* ctx, const void* gathered, void* out);
+
+/* ---- camera (superset: the reference's camera is the pinhole hard-coded in CPUPathTracer.cpp:53-73,
+ * at the origin, looking down +z, 90 degrees of vertical field of view, rays through the pixels'
+ * corners; its Camera.h is dead code) -------------------------------------------------------------
+ * A camera is an origin and three vectors: u, the image plane's right, and v, its up, both scaled by
+ * tan(vfov / 2), and w, forward. The ray of pixel (x, y) — y the full-image row — with jitter (jx, jy),
+ * all in fp32 without contraction, inv_w = 1.0f / W, inv_h = 1.0f / H, aspect = (float)W / (float)H:
+ *   px = (float)x + jx;  py = (float)y + jy;  u_ = px * inv_w;  v_ = 1.0f - py * inv_h;
+ *   sx = (u_ * 2.0f - 1.0f) * aspect;  sy = v_ * 2.0f - 1.0f;
+ *   p.c = (sx * u.c + sy * v.c) + w.c;  len = sqrtf((p.x*p.x + p.y*p.y) + p.z*p.z);  d.c = p.c / len
+ * from `origin`. Without SPT_CAMERA_JITTER jx = jy = 0 (the pixel's corner, as the reference). With it
+ * every path draws jx = random_float(rng), jy = random_float(rng) first, from the state the reference
+ * seeds it with (get_rng_state(x, y, W, frame + 1)), and trace_ray continues with that state: the ray
+ * goes through a uniform point of the pixel [x, x+1] x [y, y+1], which anti-aliases the image.
+ * u = (1,0,0), v = (0,1,0), w = (0,0,1) at the origin is the reference's camera. */
+#define SPT_CAMERA_JITTER 1u
+typedef struct spt_camera {
+    float origin[3], u[3], v[3], w[3];   /* w = forward                          */
+    uint32_t flags;                      /* SPT_CAMERA_JITTER                    */
+    uint32_t reserved[3];                /* must be 0                            */
+} spt_camera;
+/* Set the camera of later spt_render calls (copied); NULL restores the reference's camera, bit for bit
+ * what a ctx that never had one renders. SPT_ERR_INVALID for a non-finite value, a zero w, an unknown
+ * flag or a non-zero reserved word. Resets the progressive accumulation like spt_set_env_map, and the
+ * one-frame kernel's camera-hit cache. Valid before or after spt_configure; kept across spt_configure. */
+int spt_set_camera(spt_ctx* ctx, const spt_camera* camera);
+/* Host only: the camera at `eye` looking at `target`, computed in double and rounded once:
+ * f = normalize(target - eye), r = normalize(cross(up, f)), t = cross(f, r), h = tan(vfov / 2);
+ * u = r * h, v = t * h, w = f, flags 0. SPT_ERR_INVALID for eye == target, up parallel to the view
+ * direction, or vfov_degrees outside (0, 180). */
+int spt_camera_look_at(const float eye[3], const float target[3], const float up[3], float vfov_degrees,
+                       spt_camera* out);
+/* Host only: the ray (o, d) of pixel (x, y) of a width x height image with jitter (jx, jy), by the
+ * function the kernels compile (csrc/spt_device.h camera_ray_dir): the same bits. */
+int spt_camera_ray(const spt_camera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                   float jx, float jy, float o[3], float d[3]);
 
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */

@@ -87,6 +87,19 @@ class SptConfig(ctypes.Structure):
     ]
 
 
+class SptCamera(ctypes.Structure):
+    """spt_camera: origin, image-plane right u and up v (scaled by tan(vfov / 2)), forward w; 64 bytes."""
+    _fields_ = [
+        ("origin", ctypes.c_float * 3),
+        ("u", ctypes.c_float * 3),
+        ("v", ctypes.c_float * 3),
+        ("w", ctypes.c_float * 3),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+
+CAMERA_JITTER = 1  # SPT_CAMERA_JITTER
 SPT_MAX_BOUNCES = 32
 
 
@@ -147,6 +160,7 @@ EXPORTED_SYMBOLS = (
     "spt_comm_available", "spt_comm_unique_id", "spt_comm_init", "spt_gather_image", "spt_gather_image_overlapped", "spt_gather_wait",
     "spt_comm_destroy", "spt_set_tuning",
     "spt_specialize_scene", "spt_compile_flat_kernels", "spt_update_prims",
+    "spt_set_camera", "spt_camera_look_at", "spt_camera_ray",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -228,6 +242,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_specialize_scene": ([P], I),
         "spt_update_prims": ([P, P, P, U32], I),
         "spt_compile_flat_kernels": ([P, U32, I, ctypes.c_char_p, ctypes.c_size_t], I),
+        "spt_set_camera": ([P, ctypes.POINTER(SptCamera)], I),
+        "spt_camera_look_at": ([ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(SptCamera)], I),
+        "spt_camera_ray": ([ctypes.POINTER(SptCamera), U32, U32, U32, U32, ctypes.c_float, ctypes.c_float,
+                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -278,6 +297,32 @@ def synthetic_env_map(size: int = 512, seed: int = 0x5eed) -> np.ndarray:
     noise = np.random.default_rng(seed).uniform(0.0, 0.05, size=(h, w, 1))
     equirect = np.maximum(base + sun + ground + noise, 0.0).astype(np.float32)
     return env_octa_from_equirect(equirect, size, size)
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0), vfov: float = 90.0, jitter: bool = False) -> SptCamera:
+    """spt_camera_look_at (host only): the camera at `eye` looking at `target` with a vertical field of
+    view of `vfov` degrees; jitter sets SPT_CAMERA_JITTER (a uniform point of the pixel per sample)."""
+    f3 = ctypes.c_float * 3
+    cam = SptCamera()
+    rc = load_library().spt_camera_look_at(f3(*eye), f3(*target), f3(*up), float(vfov), ctypes.byref(cam))
+    if rc != SPT_OK:
+        raise SptError(f"spt_camera_look_at -> {SPT_ERR.get(rc, rc)}")
+    if jitter:
+        cam.flags |= CAMERA_JITTER
+    return cam
+
+
+def camera_ray(cam: SptCamera, width: int, height: int, x: int, y: int, jx: float = 0.0, jy: float = 0.0):
+    """spt_camera_ray (host only): origin and direction (two float32 arrays of 3) of pixel (x, y) with
+    jitter (jx, jy), from the function the kernels compile: the same bits."""
+    o = np.zeros(3, dtype=np.float32)
+    d = np.zeros(3, dtype=np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    rc = load_library().spt_camera_ray(ctypes.byref(cam), width, height, x, y, float(jx), float(jy),
+                                       o.ctypes.data_as(fp), d.ctypes.data_as(fp))
+    if rc != SPT_OK:
+        raise SptError(f"spt_camera_ray -> {SPT_ERR.get(rc, rc)}")
+    return o, d
 
 
 def build_scene(scene: "int | str") -> Tuple[np.ndarray, np.ndarray, SptEnv]:
@@ -505,6 +550,11 @@ class Context:
         self._env_keep = a
         self._check(self.lib.spt_set_env_map(self.h, a.ctypes.data, a.shape[1], a.shape[0]), "spt_set_env_map")
 
+    def set_camera(self, cam: Optional[SptCamera]) -> None:
+        """spt_set_camera: the camera of later renders (look_at), or None for the reference's pinhole at
+        the origin; resets the accumulation."""
+        self._check(self.lib.spt_set_camera(self.h, ctypes.byref(cam) if cam is not None else None), "spt_set_camera")
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -706,9 +756,17 @@ class HIPPathTracer(PathTracer):
         self._frame_count = 0
         self._max_bounces, self._rr_depth, self._flags = max_bounces, rr_depth, flags
         self._settings_mode = settings_mode
+        self._camera: Optional[SptCamera] = None
+        self._camera_dirty = False
 
     def set_scene(self, scene: Scene) -> None:
         self._scene = scene
+
+    def set_camera(self, cam: Optional[SptCamera]) -> None:
+        """Not in the reference interface: the camera (look_at) of the next render() on, or None for the
+        reference's; the accumulation restarts there."""
+        self._camera = cam
+        self._camera_dirty = True
 
     def set_settings(self, settings: RenderSettings) -> None:
         self._settings = settings
@@ -741,6 +799,10 @@ class HIPPathTracer(PathTracer):
             if self._settings_mode:
                 bounces, rr = self._settings.getMaxBounces(), self._settings.getRussianRouletteDepth()
             self._ctx.configure(self._result.width, self._result.height, bounces, rr, self._flags)
+        if self._camera_dirty:
+            self._frame_count = 0
+            self._camera_dirty = False
+            self._ctx.set_camera(self._camera)
         if self._frame_count == 0:
             self._ctx.reset()
         if needs_rebuild:

@@ -99,6 +99,14 @@ namespace render
 		}
 	}
 
+	void HIPPathTracer::set_camera(const spt_camera *camera)
+	{
+		m_hasCamera = camera != nullptr;
+		if (camera)
+			m_camera = *camera;
+		m_cameraChanged = true;
+	}
+
 	const PathTracer::RenderResult &HIPPathTracer::get_render_result()
 	{
 		SPT_VERIFY(m_frameCount > 0, "No frames rendered yet");
@@ -174,6 +182,15 @@ namespace render
 			cfg.shard_count = 1;
 			cfg.frames_in_flight = 1;  // progressive: one frame per render() call
 			SPT_CALL(m_ctx, spt_configure(m_ctx, &cfg));
+		}
+		if (m_cameraChanged)
+		{
+			// another view: a fresh accumulation, and nothing resolved for it yet
+			SPT_CALL(m_ctx, spt_set_camera(m_ctx, m_hasCamera ? &m_camera : nullptr));
+			m_cameraChanged = false;
+			m_frameCount = 0;
+			m_resolvedAt = 0;
+			m_outputDirty = true;
 		}
 		if (m_frameCount == 0)
 		{

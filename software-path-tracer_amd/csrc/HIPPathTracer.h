@@ -49,6 +49,12 @@ namespace render
 		void set_settings_mode(bool enabled);
 		bool settings_mode() const { return m_settingsMode; }
 
+		// Not in the reference interface (its camera is hard-coded, CPUPathTracer.cpp:53-73): the camera
+		// of the next render() on (spt.h spt_camera, e.g. from spt_camera_look_at; copied), and back to
+		// the reference's. A change takes effect at the next render(), which restarts the accumulation.
+		void set_camera(const spt_camera *camera);
+		void clear_camera() { set_camera(nullptr); }
+
 	private:
 		void invalidate();
 		void rebuild_scene();
@@ -66,5 +72,8 @@ namespace render
 		bool m_outputRegistered = false;  // the result buffer is page-locked and GPU-mapped
 		uint32_t m_resolvedAt = 0;         // render() resolved the result for this frame count (0: none)
 		float m_resolvedExposure = 1.0f;   // ... with this exposure
+		spt_camera m_camera{};             // set_camera's, while m_hasCamera
+		bool m_hasCamera = false;
+		bool m_cameraChanged = false;
 	};
 } // namespace render

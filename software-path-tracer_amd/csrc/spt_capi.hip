@@ -18,6 +18,7 @@
 
 #include "scene.h"
 #include "spt.h"
+#include "spt_device.h"
 #include "spt_jit.h"
 #include "spt_kernels.h"
 #include "spt_launch_plan.h"
@@ -135,6 +136,11 @@ struct spt_ctx {
     bool fused = false;
 
     uint32_t frame_count = 0;
+
+    // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
+    bool has_camera = false;
+    spt_camera camera{};
+    float4* d_camera = nullptr;  // its device record (PassParams::cam_pose), allocated by the first spt_set_camera
 
     // stats
     uint64_t frames = 0, paths = 0, passes = 0;
@@ -434,7 +440,7 @@ static uint64_t flat_jit_key(const spt_ctx* c) {
     const uint64_t shape = flat_shape_key(c->flat_ends, c->n_prims, c->flat_rect);
     if (!c->configured) return shape;
     const uint32_t flags = (c->cfg.flags & ~spt::kFlagFastDiv) | (c->fast_div ? spt::kFlagFastDiv : 0u);
-    return jit_config_key(shape, c->cfg.max_bounces, c->cfg.rr_depth, c->env.sky_enabled ? 1u : 0u, flags);
+    return jit_config_key(shape, c->cfg.max_bounces, c->cfg.rr_depth, c->env.sky_enabled ? 1u : 0u, flags, c->has_camera);
 }
 
 // The NEE kernels run: the flag is set AND the scene has an emitter to sample (launch_paths / launch_frame
@@ -520,6 +526,10 @@ PassParams base_params(spt_ctx* c) {
     p.stack_tb = c->bvh_stack_tb;
     // NEE only with the flag and something to sample (otherwise the oracle's integrator is the plain one)
     p.nee = NeeParams{c->d_emit, nee_active(c) ? c->n_emit : 0u, c->n_emit_spheres};
+    if (c->has_camera) {
+        p.cam_mode = (c->camera.flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed;
+        p.cam_pose = c->d_camera;
+    }
     return p;
 }
 
@@ -584,6 +594,7 @@ void spt_destroy(spt_ctx* c) {
     free_dev(c->counts);
     free_dev(c->totals);
     free_dev(c->d_env);
+    free_dev(c->d_camera);
     free_dev(c->work);
     if (c->out_host) (void)hipHostUnregister(c->out_host);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -987,7 +998,9 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             p.live_rec = c->live_rec;
             p.sky_pix = c->sky_pix;
             p.list_counts = c->list_counts;
-            p.hit_mode = !c->hit_cache_valid ? 1u : (c->frame_lists ? 3u : 2u);
+            // (a jittered camera: hit_mode 0, the camera segment traced per frame; no cache, no lists, no wait)
+            const bool jitter = p.cam_mode == kCamJitter;
+            p.hit_mode = frame_hit_mode(p, c->hit_cache_valid, c->frame_lists);
             p.live_pixels = c->live_pixels;
             if (c->fuse_frames != 0.0f && done + 1u == n_frames) {  // the call's last frame resolves as it ends
                 p.rgba = (uint32_t*)c->out_dev;
@@ -999,7 +1012,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             if (end_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
             SPT_HIP(c, hipGetLastError());
             if (!c->hit_cache_valid) c->frame_lists = false;
-            if (!c->hit_cache_valid && frame_lists_scene(p, c->counters)) {  // compacted once (stream order)
+            if (!jitter && !c->hit_cache_valid && frame_lists_scene(p, c->counters)) {  // compacted once (stream order)
                 launch_hit_lists(p, c->list_counts + 2, c->stream);
                 SPT_HIP(c, hipGetLastError());
                 // the live count sizes the next launches' grids: read back once per scene / configuration
@@ -1009,7 +1022,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
                 SPT_HIP(c, hipStreamSynchronize(c->stream));
                 c->frame_lists = c->pixels - c->live_pixels >= c->pixels / kFrameListsMinSkyDiv;
             }
-            c->hit_cache_valid = true;  // (stream order: the next launch reads what this one stored)
+            if (!jitter) c->hit_cache_valid = true;  // (stream order: the next launch reads what this one stored)
             c->passes++;
         }
         c->frames += n_frames;
@@ -1208,6 +1221,95 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
         c->env_h = height;
     }
     if (c->configured) return spt_reset(c);  // a different sky: the accumulation restarts
+    return SPT_OK;
+}
+
+int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
+    if (!c) return SPT_ERR_INVALID;
+    if (cam) {
+        double w2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(cam->origin[a]) || !std::isfinite(cam->u[a]) || !std::isfinite(cam->v[a]) ||
+                !std::isfinite(cam->w[a]))
+                return fail(c, SPT_ERR_INVALID, "camera: non-finite value");
+            w2 += (double)cam->w[a] * cam->w[a];
+        }
+        if (!(w2 > 0.0)) return fail(c, SPT_ERR_INVALID, "camera: w (forward) is zero");
+        if (cam->flags & ~(uint32_t)SPT_CAMERA_JITTER) return fail(c, SPT_ERR_INVALID, "camera: unknown flags");
+        if (cam->reserved[0] | cam->reserved[1] | cam->reserved[2])
+            return fail(c, SPT_ERR_INVALID, "camera: reserved must be 0");
+        // the device record: (origin, mode), (u, 0), (v, 0), (w, 0); a launch in flight reads the old one
+        SPT_HIP(c, hipSetDevice(c->device));
+        SPT_HIP(c, hipStreamSynchronize(c->stream));
+        if (!c->d_camera) SPT_HIP(c, hipMalloc(&c->d_camera, 4 * sizeof(float4)));
+        const uint32_t mode = (cam->flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed;
+        float4 rec[4] = {make_float4(cam->origin[0], cam->origin[1], cam->origin[2], 0.0f),
+                         make_float4(cam->u[0], cam->u[1], cam->u[2], 0.0f), make_float4(cam->v[0], cam->v[1], cam->v[2], 0.0f),
+                         make_float4(cam->w[0], cam->w[1], cam->w[2], 0.0f)};
+        std::memcpy(&rec[0].w, &mode, sizeof(mode));
+        SPT_HIP(c, hipMemcpy(c->d_camera, rec, sizeof(rec), hipMemcpyHostToDevice));
+        c->camera = *cam;
+    }
+    c->has_camera = cam != nullptr;
+    // the camera hits k_frame cached and the chunk costs k_paths recorded were the previous camera's
+    c->hit_cache_valid = false;
+    c->frame_lists = false;
+    c->chunk_order_key = 0;
+    prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
+    if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
+    return SPT_OK;
+}
+
+int spt_camera_look_at(const float eye[3], const float target[3], const float up[3], float vfov_degrees,
+                       spt_camera* out) {
+    if (!eye || !target || !up || !out) return SPT_ERR_INVALID;
+    if (!(vfov_degrees > 0.0f && vfov_degrees < 180.0f)) return SPT_ERR_INVALID;
+    auto norm = [](double v[3]) {
+        const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        if (!(l > 0.0) || !std::isfinite(l)) return false;
+        for (int a = 0; a < 3; ++a) v[a] /= l;
+        return true;
+    };
+    double f[3], r[3], t[3];
+    for (int a = 0; a < 3; ++a) f[a] = (double)target[a] - (double)eye[a];
+    if (!norm(f)) return SPT_ERR_INVALID;  // eye == target
+    const double upd[3] = {up[0], up[1], up[2]};
+    r[0] = upd[1] * f[2] - upd[2] * f[1];  // cross(up, f)
+    r[1] = upd[2] * f[0] - upd[0] * f[2];
+    r[2] = upd[0] * f[1] - upd[1] * f[0];
+    // up parallel to the view direction: |cross| vanishes against |up| (|f| = 1)
+    const double ul = std::sqrt(upd[0] * upd[0] + upd[1] * upd[1] + upd[2] * upd[2]);
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (!(ul > 0.0) || !std::isfinite(ul) || !(rl > 1e-12 * ul)) return SPT_ERR_INVALID;
+    if (!norm(r)) return SPT_ERR_INVALID;
+    t[0] = f[1] * r[2] - f[2] * r[1];  // cross(f, r)
+    t[1] = f[2] * r[0] - f[0] * r[2];
+    t[2] = f[0] * r[1] - f[1] * r[0];
+    // tan(vfov / 2); 90 degrees is exactly 1 (tan(pi / 4) in double is 1 - 1 ulp)
+    const double h = vfov_degrees == 90.0f ? 1.0 : std::tan((double)vfov_degrees * (3.14159265358979323846 / 360.0));
+    spt_camera cam{};
+    for (int a = 0; a < 3; ++a) {
+        cam.origin[a] = eye[a];
+        cam.u[a] = (float)(r[a] * h);
+        cam.v[a] = (float)(t[a] * h);
+        cam.w[a] = (float)f[a];
+    }
+    *out = cam;
+    return SPT_OK;
+}
+
+int spt_camera_ray(const spt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float jx, float jy,
+                   float o[3], float d[3]) {
+    if (!cam || !o || !d || width == 0 || height == 0) return SPT_ERR_INVALID;
+    const CameraPose pose{F3{cam->origin[0], cam->origin[1], cam->origin[2]}, F3{cam->u[0], cam->u[1], cam->u[2]},
+                          F3{cam->v[0], cam->v[1], cam->v[2]}, F3{cam->w[0], cam->w[1], cam->w[2]}};
+    // the constants base_params computes (CPUPathTracer.cpp:53-54, 65)
+    const F3 dir = camera_ray_dir(pose, x, y, jx, jy, 1.0f / (float)width, 1.0f / (float)height,
+                                  (float)width / (float)height);
+    for (int a = 0; a < 3; ++a) o[a] = cam->origin[a];
+    d[0] = dir.x;
+    d[1] = dir.y;
+    d[2] = dir.z;
     return SPT_OK;
 }
 

@@ -148,6 +148,45 @@ __device__ __forceinline__ F3 primary_dir(uint32_t x, uint32_t y, float inv_w, f
     return F3{uv_x / len, uv_y / len, 1.0f / len};
 }
 
+// A posed camera (spt_set_camera, spt.h spt_camera): origin o, image-plane right u and up v (both
+// scaled by tan(vfov / 2)) and forward w. The superset of the pinhole above (the reference's Camera.h
+// is dead code): u = (1,0,0), v = (0,1,0), w = (0,0,1) at the origin gives primary_dir's bits wherever
+// no direction component is zero.
+struct CameraPose {
+    F3 o, u, v, w;
+};
+
+// The camera ray through the point (x + jx, y + jy) of the image plane, y the full-image row; the
+// pixel's footprint is [x, x + 1] x [y, y + 1] (jx = jy = 0: its corner, as primary_dir). fp32, no
+// contraction, correctly rounded sqrtf and '/': DESIGN.md "Camera" states the expressions, and the
+// host (spt_camera_ray) and every kernel compile this one function. On the device a lane whose
+// operands are inside sqrt_unit's and div_ref's ranges (q in [2^-80, 2^40), so len in [2^-40, 2^20);
+// every numerator in [2^-100, 2^50] in magnitude — a zero one takes the general division, which keeps
+// its sign) runs those forms: the same bits (tests/cpp/test_device_math.hip).
+__host__ __device__ inline F3 camera_ray_dir(const CameraPose& c, uint32_t x, uint32_t y, float jx, float jy,
+                                             float inv_w, float inv_h, float aspect) {
+    const float px = (float)x + jx;
+    const float py = (float)y + jy;
+    const float u = px * inv_w;
+    const float v = 1.0f - py * inv_h;
+    const float sx = (u * 2.0f - 1.0f) * aspect;
+    const float sy = v * 2.0f - 1.0f;
+    const F3 p{(sx * c.u.x + sy * c.v.x) + c.w.x, (sx * c.u.y + sy * c.v.y) + c.w.y, (sx * c.u.z + sy * c.v.z) + c.w.z};
+    const float q = (p.x * p.x + p.y * p.y) + p.z * p.z;
+#ifdef __HIP_DEVICE_COMPILE__
+    auto in_range = [](float a) {  // 2^-100 <= |a| <= 2^50 (on the magnitude's bits)
+        return (uint32_t)((__float_as_uint(a) & 0x7fffffffu) - 0x0d800000u <= 0x58800000u - 0x0d800000u);
+    };
+    // (combined without short-circuits: one branch)
+    if (((uint32_t)(q >= 0x1p-80f) & (uint32_t)(q < 0x1p40f) & in_range(p.x) & in_range(p.y) & in_range(p.z))) {
+        const RcpRef r = rcp_ref(sqrt_unit(q));
+        return F3{div_ref(p.x, r), div_ref(p.y, r), div_ref(p.z, r)};
+    }
+#endif
+    const float len = sqrtf(q);
+    return F3{p.x / len, p.y / len, p.z / len};
+}
+
 // sample_sky, CPUPathTracer.cpp:286-292: glm::mix(horizon, zenith, t).
 __device__ __forceinline__ F3 sample_sky(float dir_y, float4 horizon, float4 zenith) {
     const float t = 0.5f * (dir_y + 1.0f);

@@ -127,7 +127,20 @@ struct PassParams {
     uint16_t* chunk_cost;        // [shard pixels] step-loop iterations per first-tier chunk
     uint32_t* chunk_order;       // [shard pixels] first-tier chunk indices, costliest first
     uint64_t* chunk_order_key;   // (host) the plan the order was sorted for, 0 = none (launch_paths)
+    // the camera (spt_set_camera): kCamReference: the reference's pinhole at the origin (primary_dir);
+    // otherwise cam_pose (device memory) holds (origin, cam_mode bits), (u, 0), (v, 0), (w, 0) of the
+    // spt_camera (spt_device.h camera_ray_dir)
+    uint32_t cam_mode;
+    const float4* cam_pose;
 };
+
+// PassParams::cam_mode. kCamPosed: a camera ray per pixel, the same in every frame, so everything built
+// on that (k_paths' per-pixel bounce 0 and constant pixels, k_frame's hit cache and lists) stays.
+// kCamJitter: the ray goes through a point of the pixel drawn per path (the path's first two draws):
+// k_paths runs its kJitter form, k_frame and the wavefront kernels trace the camera segment as any other.
+constexpr uint32_t kCamReference = 0;
+constexpr uint32_t kCamPosed = 1;
+constexpr uint32_t kCamJitter = 2;
 
 // A flat scene's shape, the compile-time key of its specialized persistent kernels (spt_jit.hip):
 // its kind groups' ends (PassParams::flat_ends, 30 bits), the primitive count (6 bits), a valid bit.
@@ -144,12 +157,17 @@ __host__ __device__ constexpr uint64_t flat_shape_key(uint32_t flat_ends, uint32
 // without kConfigValid runs on the run-time values (the kernels' ShadeParams).
 constexpr uint64_t kConfigValid = 1ull << 37;
 constexpr uint32_t kFlagAbsFloatBit = 1u;  // SPT_FLAG_ABS_FLOAT (spt.h) == spt_device.h kFlagAbsFloat
+// ... and whether the launch has a camera (spt_set_camera; kConfigCamera): as a kernel argument the
+// camera's pointer stays in SGPRs across k_paths' step loop for the chunk set-up alone, which cost C2
+// 0.6 % without any camera; baked in, the kernel of a ctx without a camera has no camera code at all
+// (and a ctx with one no null test). The kernels that run on run-time values test the pointer.
+constexpr uint64_t kConfigCamera = 1ull << 56;
 __host__ __device__ constexpr uint64_t jit_config_key(uint64_t shape, uint32_t max_bounces, uint32_t rr_depth,
-                                                      uint32_t sky_enabled, uint32_t flags) {
+                                                      uint32_t sky_enabled, uint32_t flags, bool camera = false) {
     if (max_bounces > 63u || rr_depth > 63u) return shape;
     return shape | kConfigValid | (uint64_t)max_bounces << 38 | (uint64_t)rr_depth << 44 |
            (uint64_t)(sky_enabled != 0u) << 50 | (uint64_t)((flags & kFlagAbsFloatBit) != 0u) << 51 |
-           (uint64_t)((flags & kFlagFastDiv) != 0u) << 52;
+           (uint64_t)((flags & kFlagFastDiv) != 0u) << 52 | (camera ? kConfigCamera : 0ull);
 }
 
 // BVH traversal stack of the persistent kernels: a global buffer (PassParams::stack), the 64 lanes'

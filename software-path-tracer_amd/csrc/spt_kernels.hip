@@ -570,20 +570,62 @@ struct CameraParams {
     // k_frame: the fused resolve (PassParams::rgba)
     uint32_t* rgba = nullptr;
     float rgba_frames = 1.0f, rgba_exposure = 1.0f;
+    // the camera (PassParams::cam_pose): nullptr keeps the reference's, primary_dir from the origin. A
+    // pointer, not the 13 values: as kernel arguments they stayed in SGPRs across k_paths' step loop,
+    // which is at its SGPR limit (the flat kernel's spills 58 -> 71, C2 -0.8 %); read where a camera
+    // ray is made, they are scalar loads into registers that die there.
+    const float4* pose = nullptr;
 };
+
+// The posed camera of a launch: (origin, mode bits), (u, 0), (v, 0), (w, 0) at c.pose (not nullptr), read
+// by scalar loads the compiler cannot hoist (the records are constant for the launch).
+struct CameraRecord {
+    CameraPose pose;
+    uint32_t mode;  // kCamPosed or kCamJitter
+};
+__device__ __forceinline__ CameraRecord camera_record(const CameraParams& c) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const __attribute__((address_space(4))) float4* p = (const __attribute__((address_space(4))) float4*)c.pose;
+    asm volatile("" : "+s"(p));
+#else
+    const float4* p = c.pose;
+#endif
+    const float4 a = p[0], u = p[1], v = p[2], w = p[3];
+    return CameraRecord{CameraPose{F3{a.x, a.y, a.z}, F3{u.x, u.y, u.z}, F3{v.x, v.y, v.z}, F3{w.x, w.y, w.z}},
+                        __float_as_uint(a.w)};
+}
 
 struct CameraRay {
-    F3 d;
-    uint32_t seed;
+    F3 o, d;
+    uint32_t seed;  // the path's RNG state: the seed, advanced by the two jitter draws of kCamJitter
 };
 
+// The camera ray of pixel (x, y) (y: the full-image row) for a path whose RNG state is `rng`: the
+// reference's pinhole; a posed camera through the pixel's corner; or through the point (jx, jy) of the
+// pixel, the path's first two draws.
+// kShape: a kernel compiled with its launch configuration in the key (jit_config_key) knows whether the
+// launch has a camera; without one its code is the reference camera's alone, and the pointer is dead.
+template <uint64_t kShape = 0>
+__device__ __forceinline__ CameraRay camera_ray_xy(const CameraParams& c, uint32_t x, uint32_t y, uint32_t rng) {
+    const bool has_camera = (kShape & kConfigValid) != 0 ? (kShape & kConfigCamera) != 0 : c.pose != nullptr;
+    if (!has_camera) return CameraRay{F3{0.0f, 0.0f, 0.0f}, primary_dir(x, y, c.inv_w, c.inv_h, c.aspect), rng};
+    const CameraRecord r = camera_record(c);
+    float jx = 0.0f, jy = 0.0f;
+    if (r.mode == kCamJitter) {
+        jx = random_float(rng);
+        jy = random_float(rng);
+    }
+    return CameraRay{r.pose.o, camera_ray_dir(r.pose, x, y, jx, jy, c.inv_w, c.inv_h, c.aspect), rng};
+}
+
+template <uint64_t kShape = 0>
 __device__ __forceinline__ CameraRay camera_ray(const CameraParams& c, uint32_t pid) {
     const uint32_t f = pid / c.shard_pixels;
     const uint32_t pix = pid - f * c.shard_pixels;
     const uint32_t lrow = pix / c.width;
     const uint32_t x = pix - lrow * c.width;
     const uint32_t y = c.shard_rank + c.shard_count * lrow;
-    return CameraRay{primary_dir(x, y, c.inv_w, c.inv_h, c.aspect), rng_seed(x, y, c.width, c.first_frame + f + 1u)};
+    return camera_ray_xy<kShape>(c, x, y, rng_seed(x, y, c.width, c.first_frame + f + 1u));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -605,8 +647,9 @@ __global__ __launch_bounds__(kBlock) void k_extend(const float4* __restrict__ pr
     for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
         F3 o, d;
         if (kPrimary) {
-            o = F3{0.0f, 0.0f, 0.0f};
-            d = camera_ray(cam, dealt_path(s, i, cam.n_sub)).d;
+            const CameraRay cr = camera_ray(cam, dealt_path(s, i, cam.n_sub));
+            o = cr.o;
+            d = cr.d;
         } else {
             const float4 o4 = qo[base + i];
             const float4 d4 = qd[base + i];
@@ -989,6 +1032,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
             if (kPrimary) {
                 pid = dealt_path(s, i, n_sub);
                 const CameraRay cr = camera_ray(cam, pid);
+                o = cr.o;
                 d = cr.d;
                 rng = cr.seed;
             } else {
@@ -1154,7 +1198,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict_
 // launch). A slot is only handed out while its frame fits in the ring, so a long path holds back
 // at most kRing frames. HBM traffic per launch: 32 B per pixel (accum read + write).
 //
-// The camera ray of a pixel has no jitter (:63-69), so its first segment is the same in every
+// Unless the camera jitters (kCamJitter: the kJitter form below), the camera ray of a pixel has no
+// jitter (:63-69; a posed camera's neither), so its first segment is the same in every
 // frame: everything up to the random bounce direction (closest hit, Ng, n, emission, albedo, the
 // tangent frame of get_random_bounche, the offset origin) is computed once per pixel at the start
 // of the launch and kept in LDS. A frame's path starts from that state: only the RNG-dependent
@@ -1204,7 +1249,7 @@ template <bool kBvh, int kEnv, uint64_t kShape = 0, class Stk = StkP>
 __device__ __forceinline__ PrimaryState primary_state(const float4* __restrict__ prims,
                                                       const float4* __restrict__ nodes, uint32_t n_prims,
                                                       const float4* sh_prims, const float4* sh_mats,
-                                                      const ShadeParams& sp, F3 d, uint32_t seed,
+                                                      const ShadeParams& sp, F3 o, F3 d, uint32_t seed,
                                                       const Stk& stk) {
     PrimaryState ps;
     ps.r0 = make_float4(0.f, 0.f, 0.f, __uint_as_float(seed));
@@ -1212,7 +1257,6 @@ __device__ __forceinline__ PrimaryState primary_state(const float4* __restrict__
     ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
     ps.r3 = make_float4(0.f, 0.f, 0.f, 0.f);
     ps.r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    F3 o{0.f, 0.f, 0.f};
     float best_t = kInf;
     uint32_t best_k = kMiss;
     if (kBvh) closest_bvh4_on(nodes, prims, o, d, best_t, best_k, stk);
@@ -1378,7 +1422,14 @@ __device__ __forceinline__ void advance_rays(const float4* __restrict__ nodes, c
 // every emitter kind; kNeeNoSpheres (BVH scenes whose emitter table holds no sphere) leaves the sphere
 // sample out of the kernel: its fp64 registers cost the BVH step loop spills (C4 NEE -4.4 %, record
 // r05_x), the flat kernels nothing.
-template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, int kSimdWaves = 0, bool kChan = false, int kNee = 0>
+// kJitter: a jittered camera (kCamJitter). A path's camera ray depends on its own first two draws, so
+// there is no per-pixel bounce 0 and no constant pixel: every pixel of a chunk is live, and a slot
+// hand-out starts its path at bounce 0 — the seed, the two jitter draws, the camera ray, T = 1, L = 0 —
+// which the step then traces and shades like any other segment (with kNee its emission counts as the
+// camera segment's). The ring and the frame-ordered accumulation are unchanged. Generic kernels only,
+// run with kEnv = 2.
+template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, int kSimdWaves = 0, bool kChan = false, int kNee = 0,
+          bool kJitter = false>
 __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWavesBvh : (kNee ? kPathsWaves : kPathsWavesFlat))) void k_paths(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                                   const float4* __restrict__ nodes, uint32_t n_prims,
                                                   float4* __restrict__ accum,
@@ -1501,10 +1552,16 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             const uint32_t lrow = pix / cam.width;
             const uint32_t x = pix - lrow * cam.width;
             const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
-            const F3 d = primary_dir(x, y, cam.inv_w, cam.inv_h, cam.aspect);
-            // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
-            ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, d, x + y * cam.width, stk);
-            live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
+            if constexpr (kJitter) {  // the pixel's state is its coordinates and seed: r0 = (x, y, 0, seed)
+                ps.r0 = make_float4(__uint_as_float(x), __uint_as_float(y), 0.f, __uint_as_float(x + y * cam.width));
+                ps.r1 = ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
+                live_px = true;
+            } else {
+                const CameraRay cr = camera_ray_xy<kShape>(cam, x, y, x + y * cam.width);
+                // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
+                ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
+                live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
+            }
         }
         // constant pixel's Lc: the sky radiance of a miss (0 + 1 * sky, or 0 without a sky), or after a hit
         // with max_bounces <= 1 bounce 0's emission
@@ -1518,7 +1575,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                    : F3{0.f, 0.f, 0.f};
             }
         }
-        if (kStats && lane == 0u) atomicAdd(&s_seg[0], n_frames * npx);  // bounce 0: one segment per path
+        // bounce 0: one segment per path (kJitter: the step counts the camera segments it traces)
+        if (kStats && !kJitter && lane == 0u) atomicAdd(&s_seg[0], n_frames * npx);
         const uint32_t live_mask = (uint32_t)__ballot(live_px);  // bit j: pixel j is live (px <= 32)
         const uint32_t n_live = (uint32_t)__popc(live_mask);
 #ifdef SPT_TIMELINE
@@ -1886,6 +1944,23 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 const uint32_t r = q - f * n_live;
                 const uint32_t frame = cam.first_frame + f + 1u;
                 const float4 p0 = s_px[wave][0][r];
+                if constexpr (kJitter) {  // bounce 0 itself: the path's first two draws place its camera ray
+                    rng = rng_seed(__float_as_uint(p0.w), 0u, 0u, frame);
+                    const float jx = random_float(rng);
+                    const float jy = random_float(rng);
+                    const CameraPose pose = camera_record(cam).pose;
+                    o = pose.o;
+                    d = camera_ray_dir(pose, __float_as_uint(p0.x), __float_as_uint(p0.y), jx, jy, cam.inv_w, cam.inv_h,
+                                       cam.aspect);
+                    T = F3{1.f, 1.f, 1.f};
+                    L = F3{0.f, 0.f, 0.f};
+                    bc = 0u;
+                    have = true;
+                    if (kBvh) {
+                        trav_init(tv, d);
+                        tdone = false;
+                    }
+                } else {
                 const float4 p1 = s_px[wave][1][r];
                 bool alive = true;  // a live pixel: a hit, and bounce_count 1 < max_bounces
                 if (!kBvh) {  // ... from the hit primitive's LDS shading record (make_shade_recs)
@@ -1930,6 +2005,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     have = true;
                 }
                 if (!kNee) fin0 = !alive;
+                }
             }
             finish(fin0);
             next = min(limit, next + (uint32_t)__popcll(m));
@@ -2084,7 +2160,7 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
         const uint32_t n_sky = __builtin_amdgcn_readfirstlane(cam.list_counts[1]);
         for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_sky; i += sky_blocks * kBlock) {
             const uint32_t px = cam.sky_pix[i];
-            const CameraRay cr = camera_ray(cam, px);
+            const CameraRay cr = camera_ray<kShape>(cam, px);
             float4 a = accum[px];
             // shade_hit's miss with T = 1 on L = 0 (CPUPathTracer.cpp:231-235), then :77-80
             F3 lc{0.f, 0.f, 0.f};
@@ -2175,7 +2251,7 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
     bool have = false;
     F3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, 0.f}, T{1.f, 1.f, 1.f}, L{0.f, 0.f, 0.f};
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);  // the pixel's accumulator, loaded when the path starts
-    // The camera has no jitter (CPUPathTracer.cpp:63-69), so a pixel's camera segment has the same closest
+    // Without jitter (CPUPathTracer.cpp:63-69; a posed camera too) a pixel's camera segment has the same closest
     // hit in every frame: the first launch after a scene or configuration change stores it per pixel
     // (hit_mode 1), later launches take it instead of tracing the segment (hit_mode 2). Same (t, k), so
     // the same bits; the counters still count the segment.
@@ -2384,8 +2460,8 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
                     cached = true;
                 }
                 acc = accum[pix];  // in flight while the path is traced
-                const CameraRay cr = camera_ray(cam, pix);
-                o = F3{0.f, 0.f, 0.f};
+                const CameraRay cr = camera_ray<kShape>(cam, pix);
+                o = cr.o;
                 d = cr.d;
                 T = F3{1.f, 1.f, 1.f};
                 L = F3{0.f, 0.f, 0.f};
@@ -2558,7 +2634,8 @@ namespace {
 CameraParams camera_params(const PassParams& p) {
     return CameraParams{p.width,   p.shard_rank,  p.shard_count, p.shard_pixels, p.n_paths,
                         p.first_frame, p.n_sub, p.inv_w,       p.inv_h,        p.aspect, p.hit_cache, p.hit_mode,
-                        p.live_rec, p.sky_pix, p.list_counts, 0u, p.rgba, p.rgba_frames, p.rgba_exposure};
+                        p.live_rec, p.sky_pix, p.list_counts, 0u, p.rgba, p.rgba_frames, p.rgba_exposure,
+                        p.cam_mode == kCamReference ? nullptr : p.cam_pose};
 }
 // (the fields after env_h are read by k_paths and k_frame only)
 ShadeParams shade_params(const PassParams& p, uint32_t bounce) {
@@ -2687,6 +2764,16 @@ const void* kp(K* kernel) {
 // nullptr: no such kernel (paths_variant never asks for one).
 const void* paths_kernel(const PathsVariant& v) {
     const bool env = v.env == 1;
+    if (v.jitter) {  // the kJitter forms: the sky's kind at run time, no 8-wave and no channel-lane kernel
+        if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee == kNeeNoSpheres)) return nullptr;
+        if (!v.bvh) {
+            if (v.nee) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll, true>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll, true>);
+            return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, 0, true>) : kp(k_paths<false, false, 2, 0, 0, false, 0, true>);
+        }
+        if (v.nee == kNeeAll) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll, true>);
+        if (v.nee) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres, true>);
+        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, 0, true>) : kp(k_paths<false, true, 2, 0, 0, false, 0, true>);
+    }
     if (v.nee) {  // the sky's kind decided at run time (kEnv 2); BVH: the sphere sample compiled in only when needed
         if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee != kNeeAll)) return nullptr;
         if (!v.bvh) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll>);

@@ -12,13 +12,14 @@
 
 namespace spt {
 
-// k_paths<stats, bvh, env, shape, simd_waves, chan, nee> / k_frame<stats, bvh, env, shape, small, nee, rgba>
+// k_paths<stats, bvh, env, shape, simd_waves, chan, nee, jitter> / k_frame<stats, bvh, env, shape, small, nee, rgba>
 struct PathsVariant {
     bool stats, bvh;
     int env;         // 0 gradient sky, 1 environment map, 2 decided at run time (the NEE kernels)
     int simd_waves;  // 0, or kBvhSmallWaves: the 8-wave kernel of small BVH scenes
     bool chan;       // the channel-lane kernel of flat scenes whose chunks are all <= 16 pixels (a small row shard)
     int nee;         // 0, kNeeAll, or kNeeNoSpheres (a BVH scene without sphere lights)
+    bool jitter = false;  // the kJitter form (a jittered camera): every path traces its camera segment; env 2 only
 };
 struct FrameVariant {
     bool stats, bvh;
@@ -26,6 +27,7 @@ struct FrameVariant {
     bool small;  // a BVH scene held whole in LDS (frame_small_scene)
     int nee;
     bool rgba;   // the resolve fused into the frame; it has no stats form
+    bool jitter = false;  // a jittered camera: the same kernels on hit_mode 0 (no camera-hit cache, no lists)
 };
 
 inline int nee_variant(const PassParams& p) {
@@ -37,6 +39,11 @@ inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t firs
     const bool bvh = p.nodes != nullptr;
     const int nee = nee_variant(p);
     PathsVariant v{stats, bvh, nee ? 2 : (p.env ? 1 : 0), 0, false, nee};
+    if (p.cam_mode == kCamJitter) {  // one generic form per (stats, bvh, nee): no 8-wave, no channel-lane kernel
+        v.env = 2;
+        v.jitter = true;
+        return v;
+    }
     if (bvh && !stats && !nee && p.n_prims <= kBvhSmall) v.simd_waves = kBvhSmallWaves;
     v.chan = !bvh && !stats && !nee && first_shift < kMaxChunkShift;
     return v;
@@ -45,7 +52,14 @@ inline FrameVariant frame_variant(const PassParams& p, bool stats) {
     const bool rgba = p.rgba != nullptr;
     stats = stats && !rgba;
     const int nee = nee_variant(p);
-    return FrameVariant{stats, p.nodes != nullptr, nee ? 2 : (p.env ? 1 : 0), frame_small_scene(p, stats), nee, rgba};
+    return FrameVariant{stats, p.nodes != nullptr, nee ? 2 : (p.env ? 1 : 0), frame_small_scene(p, stats), nee, rgba,
+                        p.cam_mode == kCamJitter};
+}
+// k_frame's hit_mode for a launch: a jittered camera's segment differs per frame, so its launches neither
+// store nor read the camera-hit cache and take no lists, whatever the ctx holds
+inline uint32_t frame_hit_mode(const PassParams& p, bool cache_valid, bool lists) {
+    if (p.cam_mode == kCamJitter) return 0u;
+    return !cache_valid ? 1u : (lists ? 3u : 2u);
 }
 
 // The variant's kernel compiled for a flat scene's shape (spt_jit.h), and the env to ask for it with;
@@ -55,7 +69,7 @@ struct JitKind {
 };
 constexpr JitKind kJitNone{-1, 0};
 inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.stats) return kJitNone;
+    if (!shape || v.bvh || v.stats || v.jitter) return kJitNone;
     return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
 }
 inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
