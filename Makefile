@@ -1,7 +1,8 @@
 # Build of the MI355X path-tracing integrator (no cmake needed: hipcc + g++ only).
 #
 #   make            libspt_hip.so (C-ABI + gfx950 kernels) and libspt_render.so (C++ render::PathTracer backend)
-#   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so)
+#   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so) and its restatement with
+#                   material models (tests/cpp/libref_materials.so)
 #   make cpp-tests  the C++ interface test driver (tests/cpp)
 #
 # Every float operation on the hot path is compiled with -ffp-contract=off, on the device and on the
@@ -56,8 +57,18 @@ RENDER_SRCS := $(CSRC)/HIPPathTracer.cpp $(CSRC)/RenderSettings.cpp $(CSRC)/Path
 $(RLIB): $(RENDER_SRCS) $(LIB) $(wildcard include/render/*.h) $(CSRC)/HIPPathTracer.h
 	$(CXX) $(CXXFLAGS) -std=c++20 -shared -o $@ $(RENDER_SRCS) -L$(PKG) -lspt_hip -Wl,-rpath,'$$ORIGIN'
 
-oracle:
+REFMAT := tests/cpp/libref_materials.so
+oracle: $(REFMAT)
+
+oracle/build/libcpu_ref.so: oracle/cpu_ref.c oracle/cpu_ref.h include/spt.h oracle/Makefile
 	$(MAKE) -C oracle
+
+# the integrator restated with material models (tests/test_materials_host.py, tests/test_gpu_materials.py):
+# the oracle's pieces plus its own METAL / DIELECTRIC step, no product code; test infrastructure, built
+# beside the C++ test drivers
+$(REFMAT): tests/cpp/ref_materials.c oracle/cpu_ref.h include/spt.h oracle/build/libcpu_ref.so
+	$(CC) -O2 $(FPFLAGS) -fPIC -std=c11 -Wall -Wextra -Iinclude -shared -o $@ tests/cpp/ref_materials.c \
+	  -Loracle/build -lcpu_ref -lm -Wl,-rpath,'$$ORIGIN/../../oracle/build'
 
 cpp-tests: $(RLIB) oracle
 	$(MAKE) -C tests/cpp
@@ -65,4 +76,5 @@ cpp-tests: $(RLIB) oracle
 clean:
 	rm -rf $(OBJ) $(LIB) $(RLIB)
 	$(MAKE) -C oracle clean
+	rm -f $(REFMAT)
 	-$(MAKE) -C tests/cpp clean

@@ -101,7 +101,8 @@ enum spt_flags {
      * nothing lies in [0.001, 0.999 * distance) the Lambertian estimate T * Le * cos_s * cos_l * area *
      * n_emitters / (pi * distance^2) is added (a sphere's cos_l counts its side facing the hit point
      * only; quads and triangles emit from both sides). Emission reached by a BSDF ray then counts on
-     * the camera segment only.
+     * the camera segment only (with material models: also after a METAL or DIELECTRIC vertex, which takes
+     * no light sample; see "materials" below).
      * RNG draw order per hit: emitter, u, v (NEE), then Russian roulette, then the direction.
      * oracle/cpu_ref.c restates it (ref_light_sample); every schedule gives identical results. */
     SPT_FLAG_NEE = 1u << 4
@@ -221,10 +222,11 @@ int spt_get_frame_count(const spt_ctx* ctx, uint32_t* frame_count);
 /* Traces frames [first_frame, first_frame + n_frames): frame k is seeded with k + 1 exactly as
  * get_rng_state(.., m_frameCount + 1) (:61, :192-195), and adds each frame's radiance to the
  * accumulation buffer in frame order (:77-80). Asynchronous on the ctx stream, with one exception:
- * the first one-frame call after spt_set_scene / spt_update_prims / spt_configure / spt_set_camera
- * stores the pixels' camera hits and, for scenes that use the compacted live-pixel lists, waits for that
- * frame to read the live-pixel count back (once per change). A camera with SPT_CAMERA_JITTER has no
- * such cache (its camera segments differ from frame to frame) and never waits. The progressive renderer calls
+ * the first one-frame call after spt_set_scene / spt_update_prims / spt_configure / spt_set_camera /
+ * spt_set_material_models stores the pixels' camera hits and, for scenes that use the compacted
+ * live-pixel lists, waits for that frame to read the live-pixel count back (once per change). A camera
+ * with SPT_CAMERA_JITTER has no such cache (its camera segments differ from frame to frame) and never
+ * waits; nor has a scene with a METAL or DIELECTRIC material. The progressive renderer calls
  * spt_render(ctx, frame_count, 1) once per App frame. */
 int spt_render(spt_ctx* ctx, uint32_t first_frame, uint32_t n_frames);
 int spt_synchronize(spt_ctx* ctx);
@@ -302,6 +304,60 @@ int spt_camera_look_at(const float eye[3], const float target[3], const float up
  * function the kernels compile (csrc/spt_device.h camera_ray_dir): the same bits. */
 int spt_camera_ray(const spt_camera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
                    float jx, float jy, float o[3], float d[3]);
+
+/* ---- materials (superset, north_star "BRDF + light sampling": the reference shades one Lambertian
+ * surface of albedo 0.7, CPUPathTracer.cpp:260-274) -----------------------------------------------
+ * Each material of the scene has a model beside its albedo and emission: DIFFUSE (the reference's
+ * cosine-weighted bounce, the default), METAL (a mirror, roughened by `fuzz`) or DIELECTRIC (glass of
+ * index of refraction `ior`). At a hit everything up to and including T *= albedo (the albedo tints
+ * metal and glass) and Russian roulette is as before. Then, all in fp32 without contraction, with
+ * correctly rounded sqrtf and '/', dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z and normalize(v) =
+ * v * (1.0f / sqrtf(dot(v,v))):
+ *   d: the incoming direction;  n: the shading normal (a sphere's points outward, a quad's or
+ *   triangle's faces the ray);  entering: a sphere: not (dot(d,n) > 0); a quad or triangle: hit on the
+ *   side of its stored normal cross(u,v) / cross(v1-v0, v2-v0) (a closed mesh wound outward is a
+ *   solid);  nf = -n for a sphere that is not entering, n otherwise.
+ *   DIFFUSE: as the reference: direction get_random_bounche(n), origin hit + n*1e-4 (inside a sphere
+ *     too: n stays the outward normal there).
+ *   METAL(f): c = dot(d,nf);  r.k = d.k - (2.0f*c)*nf.k;  if f > 0: b = get_random_bounche(nf) (two
+ *     draws), r.k = r.k + f*b.k;  r = normalize(r);  if not dot(r,nf) > 0 the path ends (absorbed, it
+ *     adds nothing more);  otherwise origin hit + nf*1e-4. f == 0 draws nothing.
+ *   DIELECTRIC(ior): always one draw u = random_float();  eta = entering ? 1.0f/ior : ior;
+ *     ci = fminf(-dot(d,nf), 1.0f);  s2 = fmaxf(1.0f - ci*ci, 0.0f);  k = (eta*eta)*s2;
+ *     ct = sqrtf(fmaxf(1.0f - k, 0.0f));  q = (1.0f - ior)/(1.0f + ior);  r0 = q*q;
+ *     x = 1.0f - (entering ? ci : ct);  x2 = x*x;  R = r0 + (1.0f - r0)*((x2*x2)*x);
+ *     if k > 1.0f || R > u: reflect exactly as METAL(0) around nf (normalized, absorbed unless
+ *     dot(r,nf) > 0);  otherwise t.k = eta*(d.k + ci*nf.k) - ct*nf.k, normalized, origin
+ *     hit - nf*1e-4 (transmitted). The throughput is not rescaled.
+ * RNG draw order per hit: the NEE light sample (3 draws) only at a DIFFUSE hit, then Russian roulette,
+ * then the model's draws. With SPT_FLAG_NEE a METAL or DIELECTRIC hit draws no light sample and traces
+ * no shadow ray, and a hit's emission counts iff it is on the camera segment or the previous vertex was
+ * METAL or DIELECTRIC (so an emitter seen in a mirror counts exactly once). Every schedule gives the
+ * same bits. */
+typedef enum spt_material_kind { SPT_MAT_DIFFUSE = 0, SPT_MAT_METAL = 1, SPT_MAT_DIELECTRIC = 2 } spt_material_kind;
+typedef struct spt_material_model {   /* 16 bytes */
+    uint32_t kind;        /* spt_material_kind */
+    float    param;       /* METAL: fuzz in [0,1]; DIELECTRIC: index of refraction, finite, > 0 (1 is allowed);
+                             DIFFUSE: must be 0 */
+    uint32_t reserved[2]; /* must be 0 */
+} spt_material_model;
+/* One model per material of the current scene, in the order of spt_set_scene's material array; n must
+ * equal that array's length. NULL (n ignored) restores all-diffuse, bit for bit what a ctx that never
+ * called this renders (an array of DIFFUSE models too: both run the kernels without any material code).
+ * spt_set_scene resets to all-diffuse; spt_update_prims keeps the models (they belong to materials, not
+ * to primitives). Resets the progressive accumulation and the one-frame kernel's camera-hit cache, like
+ * spt_set_camera. SPT_ERR_NO_SCENE before a scene; SPT_ERR_INVALID for an unknown kind, a parameter out
+ * of range or non-finite, a non-zero reserved word, or a wrong n. */
+int spt_set_material_models(spt_ctx* ctx, const spt_material_model* models, uint32_t n);
+/* Host only: the scattering step the kernels compile (csrc/spt_device.h bsdf_scatter), the same bits.
+ * d: the incoming direction; n: the surface's unit normal on its outside, so nf = entering ? n : -n (a
+ * sphere's shading normal; for a quad or triangle hit from behind, the negated shading normal); *rng:
+ * the path's RNG state, advanced by the model's draws. DIFFUSE returns get_random_bounche(n) around n as
+ * given. dir_out: the new direction; *transmitted: it leaves on the far side (origin hit - nf*1e-4);
+ * *absorbed: the path ends (dir_out is then the rejected direction). SPT_ERR_INVALID for a null pointer
+ * or an invalid model. */
+int spt_bsdf_sample(const spt_material_model* model, const float d[3], const float n[3], int entering,
+                    uint32_t flags, uint32_t* rng, float dir_out[3], int* transmitted, int* absorbed);
 
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */

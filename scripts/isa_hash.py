@@ -7,6 +7,8 @@ added), comments and directives dropped.
     python3 scripts/isa_hash.py a.s b.s            -> kernels present in both whose code differs
     python3 scripts/isa_hash.py a.s b.s --defaulted-last   (b's kernels have one more defaulted template
                                                             argument and a trailing NeeParams argument)
+    python3 scripts/isa_hash.py a.s b.s --defaulted-template   (b's kernels have one more defaulted template
+                                                                argument, false, and the same arguments)
 """
 import hashlib
 import re
@@ -57,6 +59,12 @@ def main():
             i = k.rfind("Lb0EEEv")
             return k[:i] + k[i + 4:] if i >= 0 else k
         b = {back(k): v for k, v in b.items()}
+    if len(sys.argv) > 3 and sys.argv[3] == "--defaulted-template":
+        def back_t(k):  # ...Lb0EEEv<arguments> -> ...EEv<arguments>; a kernel whose last argument is set has no match in a
+            i = k.find("Lb0EEEv")
+            return k[:i] + k[i + 4:] if i >= 0 else k
+        names = set(a)
+        b = {(back_t(k) if back_t(k) in names else k): v for k, v in b.items()}
     same = diff = 0
     for k in sorted(set(a) & set(b)):
         if a[k] == b[k]:

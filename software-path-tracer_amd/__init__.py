@@ -68,6 +68,10 @@ PRIM_DTYPE = np.dtype(
 )
 MATERIAL_DTYPE = np.dtype([("albedo", "<f4", (3,)), ("emission", "<f4", (3,))])
 assert PRIM_DTYPE.itemsize == 64 and MATERIAL_DTYPE.itemsize == 24
+# spt_material_model: one per material (Context.set_material_models)
+MATERIAL_MODEL_DTYPE = np.dtype([("kind", "<u4"), ("param", "<f4"), ("reserved", "<u4", (2,))])
+assert MATERIAL_MODEL_DTYPE.itemsize == 16
+MAT_DIFFUSE, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2  # spt_material_kind
 
 
 class SptEnv(ctypes.Structure):
@@ -161,6 +165,7 @@ EXPORTED_SYMBOLS = (
     "spt_comm_destroy", "spt_set_tuning",
     "spt_specialize_scene", "spt_compile_flat_kernels", "spt_update_prims",
     "spt_set_camera", "spt_camera_look_at", "spt_camera_ray",
+    "spt_set_material_models", "spt_bsdf_sample",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -247,6 +252,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                 ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(SptCamera)], I),
         "spt_camera_ray": ([ctypes.POINTER(SptCamera), U32, U32, U32, U32, ctypes.c_float, ctypes.c_float,
                             ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], I),
+        "spt_set_material_models": ([P, P, U32], I),
+        "spt_bsdf_sample": ([P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), I, U32,
+                             ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(I),
+                             ctypes.POINTER(I)], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -323,6 +332,32 @@ def camera_ray(cam: SptCamera, width: int, height: int, x: int, y: int, jx: floa
     if rc != SPT_OK:
         raise SptError(f"spt_camera_ray -> {SPT_ERR.get(rc, rc)}")
     return o, d
+
+
+def material_models(models) -> np.ndarray:
+    """A MATERIAL_MODEL_DTYPE array from (kind, param) pairs (or such an array itself)."""
+    if isinstance(models, np.ndarray) and models.dtype == MATERIAL_MODEL_DTYPE:
+        return np.ascontiguousarray(models)
+    out = np.zeros(len(models), dtype=MATERIAL_MODEL_DTYPE)
+    for i, (kind, param) in enumerate(models):
+        out[i]["kind"], out[i]["param"] = kind, param
+    return out
+
+
+def bsdf_sample(kind: int, param: float, d, n, entering: bool, state: int, flags: int = 0):
+    """spt_bsdf_sample (host only): the scattering step the kernels compile, the same bits. d: the incoming
+    direction, n: the surface's outward unit normal (nf = n if entering else -n), state: the RNG state.
+    Returns (direction float32[3], transmitted, absorbed, state after the model's draws)."""
+    m = material_models([(kind, param)])
+    f3 = ctypes.c_float * 3
+    out = np.zeros(3, dtype=np.float32)
+    st, tr, ab = ctypes.c_uint32(state), ctypes.c_int(0), ctypes.c_int(0)
+    rc = load_library().spt_bsdf_sample(m.ctypes.data, f3(*d), f3(*n), int(bool(entering)), flags, ctypes.byref(st),
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(tr),
+                                        ctypes.byref(ab))
+    if rc != SPT_OK:
+        raise SptError(f"spt_bsdf_sample -> {SPT_ERR.get(rc, rc)}")
+    return out, bool(tr.value), bool(ab.value), st.value
 
 
 def build_scene(scene: "int | str") -> Tuple[np.ndarray, np.ndarray, SptEnv]:
@@ -555,6 +590,16 @@ class Context:
         the origin; resets the accumulation."""
         self._check(self.lib.spt_set_camera(self.h, ctypes.byref(cam) if cam is not None else None), "spt_set_camera")
 
+    def set_material_models(self, models) -> None:
+        """spt_set_material_models: one model per material of the current scene — a MATERIAL_MODEL_DTYPE array
+        or (kind, param) pairs with kind MAT_DIFFUSE / MAT_METAL (param: fuzz) / MAT_DIELECTRIC (param: index of
+        refraction) — or None for all-diffuse; resets the accumulation."""
+        if models is None:
+            self._check(self.lib.spt_set_material_models(self.h, None, 0), "spt_set_material_models")
+            return
+        m = material_models(models)
+        self._check(self.lib.spt_set_material_models(self.h, m.ctypes.data, len(m)), "spt_set_material_models")
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -758,6 +803,8 @@ class HIPPathTracer(PathTracer):
         self._settings_mode = settings_mode
         self._camera: Optional[SptCamera] = None
         self._camera_dirty = False
+        self._models = None
+        self._models_dirty = False
 
     def set_scene(self, scene: Scene) -> None:
         self._scene = scene
@@ -767,6 +814,13 @@ class HIPPathTracer(PathTracer):
         reference's; the accumulation restarts there."""
         self._camera = cam
         self._camera_dirty = True
+
+    def set_material_models(self, models) -> None:
+        """Not in the reference interface: one model per material of the scene (Context.set_material_models; the
+        backend's scenes have the one reference material) from the next render() on, or None for all-diffuse;
+        the accumulation restarts there. A scene rebuild keeps them."""
+        self._models = None if models is None else material_models(models)
+        self._models_dirty = True
 
     def set_settings(self, settings: RenderSettings) -> None:
         self._settings = settings
@@ -810,6 +864,11 @@ class HIPPathTracer(PathTracer):
                        if isinstance(n, SphereObject)]
             self._ctx.set_scene(sphere_prims(spheres), reference_materials(), reference_env(True))
             self._scene.markChangesProcessed()
+        # (after the rebuild: spt_set_scene resets the models, and they need a scene)
+        if self._models_dirty or (needs_rebuild and self._models is not None):
+            self._frame_count = 0
+            self._models_dirty = False
+            self._ctx.set_material_models(self._models)
 
     def render(self) -> None:
         if self._scene is None:

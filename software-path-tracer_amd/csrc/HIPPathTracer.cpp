@@ -107,6 +107,12 @@ namespace render
 		m_cameraChanged = true;
 	}
 
+	void HIPPathTracer::set_material_models(const spt_material_model *models, uint32_t n)
+	{
+		m_models.assign(models ? models : nullptr, models ? models + n : nullptr);
+		m_modelsChanged = true;
+	}
+
 	const PathTracer::RenderResult &HIPPathTracer::get_render_result()
 	{
 		SPT_VERIFY(m_frameCount > 0, "No frames rendered yet");
@@ -200,6 +206,16 @@ namespace render
 		{
 			rebuild_scene();
 			m_scene->markChangesProcessed();
+		}
+		// after the rebuild: the models need a scene, and spt_set_scene resets them (spt_update_prims keeps them)
+		if (m_modelsChanged || (needs_rebuild && !m_models.empty()))
+		{
+			SPT_CALL(m_ctx, spt_set_material_models(m_ctx, m_models.empty() ? nullptr : m_models.data(),
+													(uint32_t)m_models.size()));
+			m_modelsChanged = false;
+			m_frameCount = 0;
+			m_resolvedAt = 0;
+			m_outputDirty = true;
 		}
 	}
 

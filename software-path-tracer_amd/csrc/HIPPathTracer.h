@@ -55,6 +55,12 @@ namespace render
 		void set_camera(const spt_camera *camera);
 		void clear_camera() { set_camera(nullptr); }
 
+		// Not in the reference interface (it shades one Lambertian 0.7, CPUPathTracer.cpp:260-274): the
+		// material models of the next render() on (spt.h spt_material_model; copied), one per material of
+		// the uploaded scene — this backend's scenes have the single reference material, so n is 1 — or
+		// (nullptr, 0) for all-diffuse. Kept across scene rebuilds; a change restarts the accumulation.
+		void set_material_models(const spt_material_model *models, uint32_t n);
+
 	private:
 		void invalidate();
 		void rebuild_scene();
@@ -75,5 +81,7 @@ namespace render
 		spt_camera m_camera{};             // set_camera's, while m_hasCamera
 		bool m_hasCamera = false;
 		bool m_cameraChanged = false;
+		std::vector<spt_material_model> m_models;  // set_material_models's (empty: all diffuse)
+		bool m_modelsChanged = false;
 	};
 } // namespace render

@@ -28,7 +28,7 @@ struct DevPrim {
 static_assert(sizeof(DevPrim) == 64, "DevPrim must be 64 bytes");
 
 struct DevMaterial {
-    float albedo[4];    // rgb, 0
+    float albedo[4];    // rgb, the material model as one word (spt_device.h model_kind; 0: DIFFUSE)
     float emission[4];  // rgb, flag(1 if any emission component != 0)
 };
 static_assert(sizeof(DevMaterial) == 32, "DevMaterial must be 32 bytes");

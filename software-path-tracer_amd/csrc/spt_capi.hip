@@ -26,6 +26,9 @@
 using namespace spt;
 
 static_assert(kBvhStackMax == kBvhStackEntries, "scene.h and spt_kernels.h stack bounds");
+static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kMatDielectric == SPT_MAT_DIELECTRIC,
+              "spt.h spt_material_kind and spt_device.h model_kind");
+static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
 
 namespace {
 
@@ -141,6 +144,15 @@ struct spt_ctx {
     bool has_camera = false;
     spt_camera camera{};
     float4* d_camera = nullptr;  // its device record (PassParams::cam_pose), allocated by the first spt_set_camera
+
+    // spt_set_material_models: one model per material of h_mats, or empty (all DIFFUSE). The device
+    // materials carry each model as one word (DevMaterial::albedo[3], spt_device.h model_kind); h_dm is
+    // the uploaded array without them and h_dev_mat[i] the caller's material behind device material i
+    // (a flat scene's materials are compacted). bsdf: some model is not DIFFUSE (PassParams::bsdf).
+    std::vector<spt_material_model> h_models;
+    std::vector<DevMaterial> h_dm;
+    std::vector<uint32_t> h_dev_mat;
+    bool bsdf = false;
 
     // stats
     uint64_t frames = 0, paths = 0, passes = 0;
@@ -530,7 +542,38 @@ PassParams base_params(spt_ctx* c) {
         p.cam_mode = (c->camera.flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed;
         p.cam_pose = c->d_camera;
     }
+    p.bsdf = c->bsdf ? 1u : 0u;
     return p;
+}
+
+// The model word of a material (spt_device.h model_kind): +0.0f DIFFUSE, -fuzz METAL, ior DIELECTRIC.
+float model_word(const spt_material_model& m) {
+    if (m.kind == SPT_MAT_METAL) return -std::fabs(m.param);  // (a fuzz of -0.0f is a mirror too, not word 0)
+    return m.kind == SPT_MAT_DIELECTRIC ? m.param : 0.0f;
+}
+// nullptr: valid
+const char* model_error(const spt_material_model& m) {
+    if (m.reserved[0] | m.reserved[1]) return "material model: reserved must be 0";
+    if (!std::isfinite(m.param)) return "material model: non-finite parameter";
+    if (m.kind == SPT_MAT_DIFFUSE) return m.param == 0.0f ? nullptr : "material model: a DIFFUSE parameter must be 0";
+    if (m.kind == SPT_MAT_METAL) return m.param >= 0.0f && m.param <= 1.0f ? nullptr : "material model: fuzz outside [0, 1]";
+    if (m.kind == SPT_MAT_DIELECTRIC) return m.param > 0.0f ? nullptr : "material model: index of refraction not > 0";
+    return "material model: unknown kind";
+}
+// Upload the scene's device materials with the models' words (c->h_models; empty: none) and set c->bsdf.
+// The caller has synchronized the stream.
+int upload_materials(spt_ctx* c) {
+    std::vector<DevMaterial> dm = c->h_dm;
+    bool bsdf = false;
+    if (!c->h_models.empty())
+        for (size_t i = 0; i < dm.size(); ++i) {
+            const spt_material_model& m = c->h_models[c->h_dev_mat[i]];
+            dm[i].albedo[3] = model_word(m);
+            bsdf = bsdf || m.kind != SPT_MAT_DIFFUSE;
+        }
+    SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * dm.size(), hipMemcpyHostToDevice));
+    c->bsdf = bsdf;
+    return SPT_OK;
 }
 
 
@@ -622,6 +665,7 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     // to the <= kFlatSceneMax ones the primitives use, in order of first use.
     std::vector<spt_prim> remapped;
     std::vector<spt_material> used_mats;
+    std::vector<uint32_t> dev_mat;  // the caller's material behind each device material (spt_set_material_models)
     if (n_prims <= kFlatSceneMax) {
         std::vector<uint32_t> map(n_mats, 0xffffffffu);
         remapped.assign(prims, prims + n_prims);
@@ -630,10 +674,14 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
             if (map[p.material] == 0xffffffffu) {
                 map[p.material] = (uint32_t)used_mats.size();
                 used_mats.push_back(mats[p.material]);
+                dev_mat.push_back(p.material);
             }
             p.material = map[p.material];
         }
-        if (used_mats.empty()) used_mats.push_back(mats[0]);
+        if (used_mats.empty()) {
+            used_mats.push_back(mats[0]);
+            dev_mat.push_back(0u);
+        }
         prims = remapped.data();
         mats = used_mats.data();
         n_mats = (uint32_t)used_mats.size();
@@ -710,6 +758,12 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     c->flat_rect = flat_rect;
     c->h_prims.swap(keep_prims);
     c->h_mats.swap(keep_mats);
+    if (dev_mat.empty())
+        for (uint32_t i = 0; i < n_mats; ++i) dev_mat.push_back(i);
+    c->h_dev_mat.swap(dev_mat);
+    c->h_dm.swap(dm);
+    c->h_models.clear();  // a new scene's materials are all DIFFUSE
+    c->bsdf = false;
     if (n_prims > kFlatSceneMax) {  // what spt_update_prims refits
         c->h_dp = dp;
         c->h_nodes = nodes;
@@ -759,8 +813,11 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     for (uint32_t j = 0; j < n; ++j) all[indices[j]] = prims[j];
     if (c->h_nodes.empty()) {  // flat scene: its records are a few hundred bytes, re-prepare them all
         const std::vector<spt_material> mats = c->h_mats;
+        const std::vector<spt_material_model> models = c->h_models;  // (they belong to the materials: kept)
         const spt_env env = c->env;
-        return spt_set_scene(c, all.data(), total, mats.data(), (uint32_t)mats.size(), &env);
+        const int rc = spt_set_scene(c, all.data(), total, mats.data(), (uint32_t)mats.size(), &env);
+        if (rc != SPT_OK || models.empty()) return rc;
+        return spt_set_material_models(c, models.data(), (uint32_t)models.size());
     }
     // BVH scene: the changed records at their device positions, the tree refitted (same topology:
     // no rebuild), the 4-wide collapse and its quantization redone, the node array re-uploaded
@@ -999,7 +1056,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             p.sky_pix = c->sky_pix;
             p.list_counts = c->list_counts;
             // (a jittered camera: hit_mode 0, the camera segment traced per frame; no cache, no lists, no wait)
-            const bool jitter = p.cam_mode == kCamJitter;
+            const bool jitter = p.cam_mode == kCamJitter || p.bsdf != 0u;  // (and so do material models)
             p.hit_mode = frame_hit_mode(p, c->hit_cache_valid, c->frame_lists);
             p.live_pixels = c->live_pixels;
             if (c->fuse_frames != 0.0f && done + 1u == n_frames) {  // the call's last frame resolves as it ends
@@ -1257,6 +1314,54 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     c->chunk_order_key = 0;
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
+    return SPT_OK;
+}
+
+int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32_t n) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "spt_set_material_models before spt_set_scene");
+    if (models) {
+        if (n != (uint32_t)c->h_mats.size())
+            return fail(c, SPT_ERR_INVALID, "spt_set_material_models: n is not the scene's material count");
+        for (uint32_t i = 0; i < n; ++i)
+            if (const char* msg = model_error(models[i])) return fail(c, SPT_ERR_INVALID, msg);
+    }
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));  // (a launch in flight reads the old words)
+    const std::vector<spt_material_model> old = c->h_models;
+    if (models) c->h_models.assign(models, models + n);
+    else c->h_models.clear();
+    if (upload_materials(c) != SPT_OK) {
+        c->h_models = old;
+        return SPT_ERR_HIP;
+    }
+    // what was cached for the old materials' kernels: k_frame's camera hits and lists, k_paths' chunk costs
+    c->hit_cache_valid = false;
+    c->frame_lists = false;
+    c->chunk_order_key = 0;
+    if (c->configured) return spt_reset(c);  // other materials: the accumulation restarts
+    return SPT_OK;
+}
+
+int spt_bsdf_sample(const spt_material_model* model, const float d[3], const float n[3], int entering, uint32_t flags,
+                    uint32_t* rng, float dir_out[3], int* transmitted, int* absorbed) {
+    if (!model || !d || !n || !rng || !dir_out || !transmitted || !absorbed) return SPT_ERR_INVALID;
+    if (model_error(*model)) return SPT_ERR_INVALID;
+    const F3 dv{d[0], d[1], d[2]}, nv{n[0], n[1], n[2]};
+    uint32_t state = *rng;
+    Scatter s{F3{0.f, 0.f, 0.f}, false, false};
+    if (model->kind == SPT_MAT_DIFFUSE) {
+        s.dir = bounce_dir(nv, state, flags);
+    } else {
+        const F3 nf = entering ? nv : F3{-nv.x, -nv.y, -nv.z};
+        s = bsdf_scatter(model->kind, model->param, dv, nf, entering != 0, flags, state);
+    }
+    *rng = state;
+    dir_out[0] = s.dir.x;
+    dir_out[1] = s.dir.y;
+    dir_out[2] = s.dir.z;
+    *transmitted = s.transmitted ? 1 : 0;
+    *absorbed = s.absorbed ? 1 : 0;
     return SPT_OK;
 }
 

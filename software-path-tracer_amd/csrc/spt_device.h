@@ -37,11 +37,11 @@ struct F3 {
     float x, y, z;
 };
 
-__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ F3 cross3(F3 a, F3 b) {
+__host__ __device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__host__ __device__ __forceinline__ F3 cross3(F3 a, F3 b) {
     return F3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y};
 }
-__device__ __forceinline__ float sqrt_unit(float x);
+__host__ __device__ __forceinline__ float sqrt_unit(float x);
 
 // 1.0f / sqrtf(x) as glm::normalize computes it (two correctly rounded operations), bit for bit.
 // For x in [2^-96, 2^96) it runs hipcc's own instruction sequences minus the steps that are the
@@ -54,8 +54,11 @@ __device__ __forceinline__ float sqrt_unit(float x);
 #if (defined(SPT_EXPERIMENT_FAST_NORM) || defined(SPT_EXPERIMENT_FP32_TRIG)) && !defined(SPT_EXPERIMENT_BUILD)
 #error "SPT_EXPERIMENT_* flags break parity with the reference: measurement builds only (scripts/build_variant.sh sets SPT_EXPERIMENT_BUILD)"
 #endif
-__device__ __forceinline__ float inv_sqrt_ref(float x) {
-#ifdef SPT_EXPERIMENT_FAST_NORM
+// (the host build — spt_bsdf_sample — is the definition itself: 1.0f / sqrtf(x))
+__host__ __device__ __forceinline__ float inv_sqrt_ref(float x) {
+#ifndef __HIP_DEVICE_COMPILE__
+    return 1.0f / sqrtf(x);
+#elif defined(SPT_EXPERIMENT_FAST_NORM)
     return __builtin_amdgcn_rsqf(x);
 #else
     if (__float_as_uint(x) - 0x0f800000u < 0x60000000u - 0x0f800000u) {  // 2^-96 <= x < 2^96
@@ -71,7 +74,7 @@ __device__ __forceinline__ float inv_sqrt_ref(float x) {
     return 1.0f / sqrtf(x);
 #endif
 }
-__device__ __forceinline__ F3 normalize3(F3 v) {
+__host__ __device__ __forceinline__ F3 normalize3(F3 v) {
     const float inv = inv_sqrt_ref(dot3(v, v));
     return F3{v.x * inv, v.y * inv, v.z * inv};
 }
@@ -82,7 +85,7 @@ __device__ __forceinline__ uint32_t rng_seed(uint32_t x, uint32_t y, uint32_t wi
 }
 
 // random_float, CPUPathTracer.cpp:294-301. 4294967295.0f rounds to 2^32, so this is exact.
-__device__ __forceinline__ float random_float(uint32_t& state) {
+__host__ __device__ __forceinline__ float random_float(uint32_t& state) {
     state = state * 747796405u + 2891336453u;
     uint32_t r = ((state >> ((state >> 28) + 4u)) ^ state) * 277803737u;
     r = (r >> 22) ^ r;
@@ -221,7 +224,7 @@ __host__ __device__ inline uint32_t octa_texel(float dx, float dy, float dz, uin
 // hit and reused for every frame of a pixel) and the random direction around (n, t, n x t).
 // (float)sqrt((double)u) == sqrtf(u) exactly for float u (double has > 2*24+2 bits), so the two
 // square roots stay fp32; cos/sin and the products with sinTheta are fp64 as in the reference.
-__device__ __forceinline__ F3 bounce_tangent(F3 n, uint32_t flags) {
+__host__ __device__ __forceinline__ F3 bounce_tangent(F3 n, uint32_t flags) {
     // `abs(normal.z) < 0.999f`: ::abs(int) under libstdc++ (truncate, then |i| < 0.999 <=> i == 0)
     const bool not_pole = (flags & kFlagAbsFloat) ? (fabsf(n.z) < 0.999f) : ((int)n.z == 0);
     const F3 up = not_pole ? F3{0.0f, 0.0f, 1.0f} : F3{1.0f, 0.0f, 0.0f};
@@ -319,7 +322,10 @@ __host__ __device__ inline void sincos_2pi(double phi, double& s, double& c) {
 // estimate, then the +-1 ulp residual corrections) without its rescaling of inputs below 2^-96 and
 // its 0/inf pass-through, neither of which these inputs reach (sqrt(0): the estimate is 0 and both
 // corrections keep it). Used for the random_float range [2^-32, 1] and by inv_sqrt_ref.
-__device__ __forceinline__ float sqrt_unit(float x) {
+__host__ __device__ __forceinline__ float sqrt_unit(float x) {
+#ifndef __HIP_DEVICE_COMPILE__
+    return sqrtf(x);  // (the host build: the correctly rounded root itself)
+#else
     const float s = __builtin_amdgcn_sqrtf(x);
     const float sm = __uint_as_float(__float_as_uint(s) - 1u);
     const float sp = __uint_as_float(__float_as_uint(s) + 1u);
@@ -327,10 +333,11 @@ __device__ __forceinline__ float sqrt_unit(float x) {
     const float rp = __builtin_fmaf(-sp, s, x);
     const float r = rm <= 0.0f ? sm : s;
     return rp > 0.0f ? sp : r;
+#endif
 }
 
 template <bool kSmemCoef = false>
-__device__ __forceinline__ F3 bounce_dir_frame(F3 n, F3 t, uint32_t& state) {
+__host__ __device__ __forceinline__ F3 bounce_dir_frame(F3 n, F3 t, uint32_t& state) {
     const float u1 = random_float(state);
     const float u2 = random_float(state);
     const float cos_t = sqrt_unit(u1);
@@ -353,7 +360,7 @@ __device__ __forceinline__ F3 bounce_dir_frame(F3 n, F3 t, uint32_t& state) {
 }
 
 template <bool kSmemCoef = false>
-__device__ __forceinline__ F3 bounce_dir(F3 n, uint32_t& state, uint32_t flags) {
+__host__ __device__ __forceinline__ F3 bounce_dir(F3 n, uint32_t& state, uint32_t flags) {
     return bounce_dir_frame<kSmemCoef>(n, bounce_tangent(n, flags), state);
 }
 
@@ -580,6 +587,63 @@ __device__ __forceinline__ bool light_sample(const float4* __restrict__ emit, ui
     tmax = dist * kShadowFar;
     add = F3{T.x * (e4.x * g), T.y * (e4.y * g), T.z * (e4.z * g)};
     return true;
+}
+
+// ---- materials (spt_set_material_models; superset: the reference shades one Lambertian 0.7) ----------
+// A material's model travels in one word that was zero before, DevMaterial::albedo[3] (scene.h; the flat
+// scenes' LDS shading record carries it as alb.w): +0.0f is DIFFUSE, a float with the sign bit set is
+// METAL with fuzz = |word| (-0.0f: a mirror), any other value is DIELECTRIC with that index of refraction
+// (finite and > 0). Lossless: the kernels compute with the caller's parameter bits.
+constexpr uint32_t kMatDiffuse = 0u, kMatMetal = 1u, kMatDielectric = 2u;  // spt_material_kind
+__host__ __device__ __forceinline__ uint32_t model_kind(uint32_t word) {
+    return word == 0u ? kMatDiffuse : ((word >> 31) ? kMatMetal : kMatDielectric);
+}
+
+// The scattering step of a METAL or DIELECTRIC hit (spt.h "materials" states the expressions): d the
+// incoming direction, nf the unit normal on the side the ray arrives from, `entering` whether the ray
+// goes from outside in. fp32, no contraction, correctly rounded sqrtf and '/', normalize3's 1 / sqrt.
+// METAL(f): r = d - (2 (d . nf)) nf, plus f times a cosine-weighted direction around nf when f > 0 (two
+// draws), normalized; absorbed unless r . nf > 0. DIELECTRIC(ior): one draw u; Snell with Schlick's
+// reflectance; total internal reflection or R > u reflects as METAL(0), else the refracted direction,
+// normalized (`transmitted`: the next origin lies on the far side). The host (spt_bsdf_sample) and every
+// kernel compile this one function.
+struct Scatter {
+    F3 dir;
+    bool transmitted, absorbed;
+};
+template <bool kSmemCoef = false>
+__host__ __device__ inline Scatter bsdf_scatter(uint32_t kind, float param, F3 d, F3 nf, bool entering, uint32_t flags,
+                                                uint32_t& rng) {
+    float fuzz = 0.0f;
+    if (kind == kMatDielectric) {
+        const float ior = param;
+        const float u = random_float(rng);
+        const float eta = entering ? 1.0f / ior : ior;
+        const float ci = fminf(-dot3(d, nf), 1.0f);
+        const float s2 = fmaxf(1.0f - ci * ci, 0.0f);
+        const float k = (eta * eta) * s2;
+        const float ct = sqrtf(fmaxf(1.0f - k, 0.0f));
+        const float q = (1.0f - ior) / (1.0f + ior);
+        const float r0 = q * q;
+        const float x = 1.0f - (entering ? ci : ct);
+        const float x2 = x * x;
+        const float R = r0 + (1.0f - r0) * ((x2 * x2) * x);
+        if (!(k > 1.0f || R > u)) {
+            const F3 t{eta * (d.x + ci * nf.x) - ct * nf.x, eta * (d.y + ci * nf.y) - ct * nf.y,
+                       eta * (d.z + ci * nf.z) - ct * nf.z};
+            return Scatter{normalize3(t), true, false};
+        }
+    } else {
+        fuzz = param;
+    }
+    const float c2 = 2.0f * dot3(d, nf);
+    F3 r{d.x - c2 * nf.x, d.y - c2 * nf.y, d.z - c2 * nf.z};
+    if (fuzz > 0.0f) {
+        const F3 b = bounce_dir<kSmemCoef>(nf, rng, flags);
+        r = F3{r.x + fuzz * b.x, r.y + fuzz * b.y, r.z + fuzz * b.z};
+    }
+    r = normalize3(r);
+    return Scatter{r, false, !(dot3(r, nf) > 0.0f)};
 }
 
 __device__ __forceinline__ uint32_t meta_type(float4 pd) { return __float_as_uint(pd.w) & 3u; }

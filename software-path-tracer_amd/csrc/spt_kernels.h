@@ -131,7 +131,11 @@ struct PassParams {
     // otherwise cam_pose (device memory) holds (origin, cam_mode bits), (u, 0), (v, 0), (w, 0) of the
     // spt_camera (spt_device.h camera_ray_dir)
     uint32_t cam_mode;
+    uint32_t bsdf;  // (below; here it fills the padding before the pointer: PassParams keeps its size)
     const float4* cam_pose;
+    // bsdf = 1: some material of the scene has a METAL or DIELECTRIC model (spt_set_material_models; the model
+    // words are in DevMaterial::albedo[3]): every schedule runs its kBsdf kernels. 0: the kernels without
+    // any material code, the same launches as before the models existed
 };
 
 // PassParams::cam_mode. kCamPosed: a camera ray per pixel, the same in every frame, so everything built

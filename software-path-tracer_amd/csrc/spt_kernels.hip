@@ -847,10 +847,21 @@ constexpr uint32_t kLdsScene = 4 * kFlatPrims + 2 * 32;  // float4s: 32 DevPrims
 // sampled: parallelograms, triangles, spheres), and the hit stops before Russian roulette: `alive`
 // says the path continues past this hit (bounce_count < max_bounces), o is the hit point without the
 // offset — the caller draws the light sample, then runs rr_continue.
-template <int kEnv = 2, bool kRec = false, bool kNee = false>
+//
+// kBsdf (a scene with material models, spt_set_material_models): `mh` reports the hit material's model
+// and the side the ray arrives from; the hit point keeps no offset (the caller offsets it along the
+// normal the model scatters around: offset_origin for DIFFUSE, scatter_specular otherwise); with kNee the
+// emission also counts when the previous vertex was METAL or DIELECTRIC (`spec_prev`).
+struct ModelHit {
+    uint32_t word;  // DevMaterial::albedo[3] (spt_device.h model_kind); 0: DIFFUSE
+    bool entering;  // a sphere: not (d . n > 0); a quad or triangle: hit on its stored normal's side
+    bool flip;      // nf = -n: a sphere hit from inside (n stays the outward normal)
+};
+template <int kEnv = 2, bool kRec = false, bool kNee = false, bool kBsdf = false>
 __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                           const ShadeParams& sp, uint32_t bounce_count, float t, uint32_t k, F3& o,
-                                          F3 d, F3& T, uint32_t& rng, bool& alive, F3& add, F3& n) {
+                                          F3 d, F3& T, uint32_t& rng, bool& alive, F3& add, F3& n,
+                                          ModelHit* mh = nullptr, bool spec_prev = false) {
     alive = false;
     add = F3{0.f, 0.f, 0.f};
     if (k == kMiss) {
@@ -865,15 +876,20 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
     o = F3{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
     F3 ng;
     float4 alb, emi;
+    bool sphere = false, back = false;  // kBsdf: the primitive's kind, and whether the two-sided flip was taken
     if (kRec) {  // flat scenes: the LDS shading record (make_shade_recs), one round trip
         const float4 g = prims[3 * k + 0];
         alb = prims[3 * k + 1];
         emi = prims[3 * k + 2];
         if (__float_as_uint(g.w) == 0u) {
             ng = F3{o.x - g.x, o.y - g.y, o.z - g.z};  // sphere Ng = hit - center
+            sphere = true;
         } else {
             ng = F3{g.x, g.y, g.z};
-            if (dot3(ng, d) > 0.0f) ng = F3{-ng.x, -ng.y, -ng.z};  // two-sided
+            if (dot3(ng, d) > 0.0f) {  // two-sided
+                ng = F3{-ng.x, -ng.y, -ng.z};
+                back = true;
+            }
         }
     } else {
         const float4 pa = prims[4 * k + 0];
@@ -881,11 +897,15 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
         const uint32_t type = meta_type(pd);
         if (type == 0u) {
             ng = F3{o.x - pa.x, o.y - pa.y, o.z - pa.z};  // sphere Ng = hit - center
+            sphere = true;
         } else {
             const float4 pb = prims[4 * k + 1];  // loaded unconditionally: a pointer select here spilled pd to scratch
             const float4 nv = type == 1u ? pb : pd;
             ng = F3{nv.x, nv.y, nv.z};
-            if (dot3(ng, d) > 0.0f) ng = F3{-ng.x, -ng.y, -ng.z};  // two-sided
+            if (dot3(ng, d) > 0.0f) {  // two-sided
+                ng = F3{-ng.x, -ng.y, -ng.z};
+                back = true;
+            }
         }
         const uint32_t m = meta_material(pd);
         alb = mats[2 * m + 0];
@@ -894,7 +914,11 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
     // n = Ng / |Ng| (:244-250)
     const float inv_len = inv_sqrt_ref(ng.x * ng.x + ng.y * ng.y + ng.z * ng.z);
     n = F3{ng.x * inv_len, ng.y * inv_len, ng.z * inv_len};
-    if (emi.w != 0.0f && (!kNee || bounce_count == 1u)) {  // superset: emission
+    if constexpr (kBsdf) {
+        const bool inside = sphere && dot3(d, n) > 0.0f;
+        *mh = ModelHit{__float_as_uint(alb.w), sphere ? !inside : !back, inside};
+    }
+    if (emi.w != 0.0f && (!kNee || bounce_count == 1u || (kBsdf && spec_prev))) {  // superset: emission
         add = F3{T.x * emi.x, T.y * emi.y, T.z * emi.z};
         contributes = true;
     }
@@ -914,18 +938,48 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
                 T = rr_divide(T, cp);
             }
         }
-        if (alive) o = F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};  // :277-280
+        if (alive && !kBsdf) o = F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};  // :277-280
     }
     return contributes;
 }
 
+// current_origin += normal * EPSILON (:277-280): the next ray's origin, and the shadow ray's
+__device__ __forceinline__ F3 offset_origin(F3 o, F3 n) {
+    return F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};
+}
+
+// A METAL or DIELECTRIC hit that continues (after Russian roulette): the model's draws and the new
+// direction (spt_device.h bsdf_scatter) around nf, and the next origin, hit + nf * EPSILON or, for a
+// transmitted ray, hit - nf * EPSILON. False: absorbed, the path ends and adds nothing more.
+template <bool kSmemCoef = false>
+__device__ __forceinline__ bool scatter_specular(ModelHit mh, F3 n, uint32_t flags, F3& o, F3& d, uint32_t& rng) {
+    const uint32_t kind = model_kind(mh.word);
+    const float param = __uint_as_float(kind == kMatMetal ? (mh.word & 0x7fffffffu) : mh.word);
+    const F3 nf = mh.flip ? F3{-n.x, -n.y, -n.z} : n;
+    const Scatter s = bsdf_scatter<kSmemCoef>(kind, param, d, nf, mh.entering, flags, rng);
+    if (s.absorbed) return false;
+    o = s.transmitted ? F3{o.x - nf.x * kOriginEps, o.y - nf.y * kOriginEps, o.z - nf.z * kOriginEps}
+                      : offset_origin(o, nf);
+    d = s.dir;
+    return true;
+}
+
 // shade_hit plus the new direction (get_random_bounche, :273-274): the whole loop body.
+template <bool kBsdf = false>
 __device__ __forceinline__ bool shade_segment(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                               const ShadeParams& sp, uint32_t bounce_count, float t, uint32_t k,
                                               F3& o, F3& d, F3& T, uint32_t& rng, bool& alive, F3& add) {
     F3 n;
-    const bool contributes = shade_hit(prims, mats, sp, bounce_count, t, k, o, d, T, rng, alive, add, n);
-    if (alive) d = bounce_dir(n, rng, sp.flags);
+    ModelHit mh{0u, true, false};
+    const bool contributes = shade_hit<2, false, false, kBsdf>(prims, mats, sp, bounce_count, t, k, o, d, T, rng, alive, add, n, &mh);
+    if (alive) {
+        if (kBsdf && mh.word != 0u) {
+            alive = scatter_specular(mh, n, sp.flags, o, d, rng);
+        } else {
+            if (kBsdf) o = offset_origin(o, n);
+            d = bounce_dir(n, rng, sp.flags);
+        }
+    }
     return contributes;
 }
 
@@ -939,11 +993,6 @@ __device__ __forceinline__ bool rr_continue(const ShadeParams& sp, uint32_t boun
         T = rr_divide(T, cp);
     }
     return true;
-}
-
-// current_origin += normal * EPSILON (:277-280): the next ray's origin, and the shadow ray's
-__device__ __forceinline__ F3 offset_origin(F3 o, F3 n) {
-    return F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};
 }
 
 // The shadow ray (o, w): true when nothing lies at 0.001 <= t < tmax (oracle ref_visible). The search
@@ -962,15 +1011,30 @@ __device__ __forceinline__ bool shadow_visible(const float4* __restrict__ prims,
 // shade_segment with NEE, for the wavefront kernels: the hit, the light sample and its shadow ray
 // (traced here, inline), Russian roulette and the new direction. Bit 0: `add` (emission or sky) is
 // added to the path's radiance, bit 1: then `add2` (the light sample), in that order.
-template <bool kBvh>
+// kBsdf: `spec` is the path's one bit of material state, "the previous vertex was METAL or DIELECTRIC"
+// (emission counts there), read and updated; such a hit draws no light sample and traces no shadow ray.
+template <bool kBvh, bool kBsdf = false>
 __device__ __forceinline__ uint32_t shade_segment_nee(const float4* sh_prims, const float4* sh_mats,
                                                       const float4* __restrict__ prims,
                                                       const float4* __restrict__ nodes, uint32_t n_prims,
                                                       const ShadeParams& sp, const NeeParams& nee,
                                                       uint32_t bounce_count, float t, uint32_t k, F3& o, F3& d,
-                                                      F3& T, uint32_t& rng, bool& alive, F3& add, F3& add2) {
+                                                      F3& T, uint32_t& rng, bool& alive, F3& add, F3& add2,
+                                                      bool& spec) {
     F3 n;
-    const bool c1 = shade_hit<2, false, true>(sh_prims, sh_mats, sp, bounce_count, t, k, o, d, T, rng, alive, add, n);
+    ModelHit mh{0u, true, false};
+    bool c1;
+    if constexpr (kBsdf) {
+        c1 = shade_hit<2, false, true, true>(sh_prims, sh_mats, sp, bounce_count, t, k, o, d, T, rng, alive, add, n, &mh, spec);
+        if (alive && mh.word != 0u) {  // METAL / DIELECTRIC: no light sample; roulette, then the model
+            spec = true;
+            alive = rr_continue(sp, bounce_count, T, rng) && scatter_specular(mh, n, sp.flags, o, d, rng);
+            return c1 ? 1u : 0u;
+        }
+        if (alive) spec = false;
+    } else {
+        c1 = shade_hit<2, false, true>(sh_prims, sh_mats, sp, bounce_count, t, k, o, d, T, rng, alive, add, n);
+    }
     bool c2 = false;
     if (alive) {
         o = offset_origin(o, n);
@@ -987,7 +1051,8 @@ __device__ __forceinline__ uint32_t shade_segment_nee(const float4* sh_prims, co
 // kFused: the "bounce" kernel — the closest hit is computed here (extend + shade in one launch), so
 // the 8 B hit record and the 32 B ray re-read of a separate extend launch disappear.
 // kNee (SPT_FLAG_NEE): each hit's light sample and its shadow ray are traced here too (shade_segment_nee).
-template <bool kPrimary, bool kFused, bool kBvh, bool kNee = false>
+// kBsdf: a scene with material models; the path's `spec` bit travels in the queue's t.w (free otherwise).
+template <bool kPrimary, bool kFused, bool kBvh, bool kNee = false, bool kBsdf = false>
 __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                                   const float4* __restrict__ nodes, uint32_t n_prims,
                                                   const float2* __restrict__ hit, QueueBufs cur, QueueBufs nxt,
@@ -1026,6 +1091,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
         bool did_rmw = false;
         F3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, 0.f}, T{1.f, 1.f, 1.f};
         uint32_t pid = 0, rng = 0;
+        bool spec = false;  // kBsdf: the previous vertex was METAL or DIELECTRIC
         if (i < n) {
             float2 h;
             if (!kFused) h = hit[base + i];
@@ -1045,6 +1111,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
                 T = F3{t4.x, t4.y, t4.z};
                 pid = __float_as_uint(o4.w);
                 rng = __float_as_uint(d4.w);
+                if (kBsdf) spec = __float_as_uint(t4.w) != 0u;
             }
             if (kFused) {
                 float best_t = kInf;
@@ -1056,8 +1123,8 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
             F3 add;
             if constexpr (kNee) {
                 F3 add2;
-                const uint32_t c = shade_segment_nee<kBvh>(sh_prims, sh_mats, prims, nodes, n_prims, sp, nee, bounce_count,
-                                                           h.x, __float_as_uint(h.y), o, d, T, rng, alive, add, add2);
+                const uint32_t c = shade_segment_nee<kBvh, kBsdf>(sh_prims, sh_mats, prims, nodes, n_prims, sp, nee, bounce_count,
+                                                                  h.x, __float_as_uint(h.y), o, d, T, rng, alive, add, add2, spec);
                 // accumulated_color += emission (or sky), then += the light sample, in bounce order
                 if (kPrimary || c) {
                     float4 L = kPrimary ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : radiance[pid];
@@ -1068,7 +1135,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
                 }
             } else {
             const bool contributes =
-                shade_segment(sh_prims, sh_mats, sp, bounce_count, h.x, __float_as_uint(h.y), o, d, T, rng, alive, add);
+                shade_segment<kBsdf>(sh_prims, sh_mats, sp, bounce_count, h.x, __float_as_uint(h.y), o, d, T, rng, alive, add);
             // accumulated_color += contribution, in bounce order (L starts at 0 in bounce 0)
             if (kPrimary) {
                 radiance[pid] = contributes ? make_float4(0.0f + add.x, 0.0f + add.y, 0.0f + add.z, 0.0f)
@@ -1101,7 +1168,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
             const uint32_t slot = base + out_n + before + lane_off;
             nxt.o[slot] = make_float4(o.x, o.y, o.z, __uint_as_float(pid));
             nxt.d[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(rng));
-            nxt.t[slot] = make_float4(T.x, T.y, T.z, 0.0f);
+            nxt.t[slot] = make_float4(T.x, T.y, T.z, __uint_as_float(kBsdf && spec ? 1u : 0u));
         }
         out_n += total;
         parity ^= 1u;
@@ -1123,7 +1190,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(const float4* __restrict__ pri
 // (bounce >= 3 holds ~5 % of C2's rays) a launch pair per bounce costs more than its work.
 // Per-bounce segment and radiance-update counts are tallied in LDS for the statistics.
 // ---------------------------------------------------------------------------------------------
-template <bool kBvh, bool kNee = false>
+template <bool kBvh, bool kNee = false, bool kBsdf = false>
 __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict__ prims,
                                                        const float4* __restrict__ nodes, uint32_t n_prims,
                                                        const float4* __restrict__ mats, QueueBufs cur,
@@ -1147,6 +1214,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict_
         F3 o{o4.x, o4.y, o4.z}, d{d4.x, d4.y, d4.z}, T{t4.x, t4.y, t4.z};
         const uint32_t pid = __float_as_uint(o4.w);
         uint32_t rng = __float_as_uint(d4.w);
+        bool spec = kBsdf && __float_as_uint(t4.w) != 0u;  // (k_shade's)
         for (uint32_t b = sp.bounce; b < sp.max_bounces; ++b) {
             atomicAdd(&s_seg[b], 1u);
             float best_t = kInf;
@@ -1157,8 +1225,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict_
             F3 add;
             if constexpr (kNee) {
                 F3 add2;
-                const uint32_t c = shade_segment_nee<kBvh>(prims, mats, prims, nodes, n_prims, sp, nee, b + 1u, best_t,
-                                                           best_k, o, d, T, rng, alive, add, add2);
+                const uint32_t c = shade_segment_nee<kBvh, kBsdf>(prims, mats, prims, nodes, n_prims, sp, nee, b + 1u, best_t,
+                                                                  best_k, o, d, T, rng, alive, add, add2, spec);
                 if (c) {
                     atomicAdd(&s_rmw[b], 1u);
                     float4 L = radiance[pid];
@@ -1166,7 +1234,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict_
                     if (c & 2u) L = make_float4(L.x + add2.x, L.y + add2.y, L.z + add2.z, L.w);
                     radiance[pid] = L;
                 }
-            } else if (shade_segment(prims, mats, sp, b + 1u, best_t, best_k, o, d, T, rng, alive, add)) {
+            } else if (shade_segment<kBsdf>(prims, mats, sp, b + 1u, best_t, best_k, o, d, T, rng, alive, add)) {
                 atomicAdd(&s_rmw[b], 1u);
                 float4 L = radiance[pid];
                 L.x = L.x + add.x;
@@ -1428,9 +1496,14 @@ __device__ __forceinline__ void advance_rays(const float4* __restrict__ nodes, c
 // which the step then traces and shades like any other segment (with kNee its emission counts as the
 // camera segment's). The ring and the frame-ordered accumulation are unchanged. Generic kernels only,
 // run with kEnv = 2.
+// kBsdf: a scene with material models (spt_set_material_models). The per-pixel bounce 0 assumes a hit's
+// state is the same in every frame up to the random direction, which a METAL or DIELECTRIC camera hit is
+// not, so this form starts every path at bounce 0 as kJitter does (the camera — the reference's, posed or
+// jittered — is read at run time: camera_ray_xy) and shades with shade_hit's kBsdf and scatter_specular;
+// `spec`, the path's one bit of material state, is a lane register. Generic kernels only, kEnv = 2.
 template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, int kSimdWaves = 0, bool kChan = false, int kNee = 0,
-          bool kJitter = false>
-__global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWavesBvh : (kNee ? kPathsWaves : kPathsWavesFlat))) void k_paths(const float4* __restrict__ prims, const float4* __restrict__ mats,
+          bool kJitter = false, bool kBsdf = false>
+__global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWavesBvh : ((kNee || kBsdf) ? kPathsWaves : kPathsWavesFlat))) void k_paths(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                                   const float4* __restrict__ nodes, uint32_t n_prims,
                                                   float4* __restrict__ accum,
                                                   unsigned long long* __restrict__ totals,
@@ -1438,6 +1511,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                                   ShadeParams sp, CameraParams cam, uint32_t n_frames, ChunkPlan plan,
                                                   NeeParams nee) {
     constexpr uint32_t kWaves = kBlock / 64u;
+    constexpr bool kStart0 = kJitter || kBsdf;  // every path starts at bounce 0: no per-pixel primary state
     bake_config<kShape>(sp);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
@@ -1552,7 +1626,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             const uint32_t lrow = pix / cam.width;
             const uint32_t x = pix - lrow * cam.width;
             const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
-            if constexpr (kJitter) {  // the pixel's state is its coordinates and seed: r0 = (x, y, 0, seed)
+            if constexpr (kStart0) {  // the pixel's state is its coordinates and seed: r0 = (x, y, 0, seed)
                 ps.r0 = make_float4(__uint_as_float(x), __uint_as_float(y), 0.f, __uint_as_float(x + y * cam.width));
                 ps.r1 = ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
                 live_px = true;
@@ -1576,7 +1650,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             }
         }
         // bounce 0: one segment per path (kJitter: the step counts the camera segments it traces)
-        if (kStats && !kJitter && lane == 0u) atomicAdd(&s_seg[0], n_frames * npx);
+        if (kStats && !kStart0 && lane == 0u) atomicAdd(&s_seg[0], n_frames * npx);
         const uint32_t live_mask = (uint32_t)__ballot(live_px);  // bit j: pixel j is live (px <= 32)
         const uint32_t n_live = (uint32_t)__popc(live_mask);
 #ifdef SPT_TIMELINE
@@ -1662,6 +1736,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         // the others shade); nd then holds the shadow ray's direction.
         constexpr bool kInline = kNee && !kBvh;
         bool shadow = false, after = false;
+        bool spec = false;  // kBsdf: the path's previous vertex was METAL or DIELECTRIC
         float smax = 0.f;
         F3 nd{0.f, 0.f, 0.f};
 
@@ -1887,8 +1962,14 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         } else {
                             bool alive;
                             F3 add, n;
-                            const bool contributes = shade_hit<kEnv, !kBvh, true>(sh_prims, sh_mats, sp, bc + 1u, best_t,
-                                                                                  best_k, o, d, T, rng, alive, add, n);
+                            ModelHit mh{0u, true, false};
+                            bool contributes;
+                            if constexpr (kBsdf)
+                                contributes = shade_hit<kEnv, !kBvh, true, true>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o,
+                                                                                 d, T, rng, alive, add, n, &mh, spec);
+                            else
+                                contributes = shade_hit<kEnv, !kBvh, true>(sh_prims, sh_mats, sp, bc + 1u, best_t,
+                                                                           best_k, o, d, T, rng, alive, add, n);
                             if (contributes) L = F3{L.x + add.x, L.y + add.y, L.z + add.z};
                             if (kStats) {
                                 atomicAdd(&s_seg[bc], 1u);
@@ -1897,7 +1978,19 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                             ++bc;
                             fin = !alive;
                             have = alive;
-                            if (alive) {
+                            if (kBsdf && alive && mh.word != 0u) {  // METAL / DIELECTRIC: no light sample; roulette, the model
+                                spec = true;
+                                if (rr_continue(sp, bc, T, rng) && scatter_specular<true>(mh, n, sp.flags, o, d, rng)) {
+                                    if (kBvh) {
+                                        trav_init(tv, d);
+                                        tdone = false;
+                                    }
+                                } else {
+                                    have = false;
+                                    fin = true;
+                                }
+                            } else if (alive) {
+                                if (kBsdf) spec = false;
                                 o = offset_origin(o, n);
                                 nee_hit(n, fin);
                                 if (pend) dt = bounce_tangent(n, sp.flags);
@@ -1906,10 +1999,23 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     } else {
                     bool alive;
                     F3 add;
+                    ModelHit mh{0u, true, false};
                     SPT_MARK(shade);
                     const bool contributes =
-                        shade_hit<kEnv, !kBvh>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, dn);
-                    if (alive) {
+                        shade_hit<kEnv, !kBvh, false, kBsdf>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, dn, &mh);
+                    bool scattered = false;  // kBsdf: a METAL / DIELECTRIC hit has set o and d
+                    if constexpr (kBsdf) {
+                        if (alive && mh.word != 0u) {
+                            scattered = alive = scatter_specular<true>(mh, dn, sp.flags, o, d, rng);
+                            if (kBvh && alive) {
+                                trav_init(tv, d);
+                                tdone = false;
+                            }
+                        } else if (alive) {
+                            o = offset_origin(o, dn);
+                        }
+                    }
+                    if (alive && !scattered) {
                         dt = bounce_tangent(dn, sp.flags);
                         pend = true;
                     }
@@ -1944,14 +2050,22 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 const uint32_t r = q - f * n_live;
                 const uint32_t frame = cam.first_frame + f + 1u;
                 const float4 p0 = s_px[wave][0][r];
-                if constexpr (kJitter) {  // bounce 0 itself: the path's first two draws place its camera ray
+                if constexpr (kStart0) {  // bounce 0 itself: the path's first two draws place its camera ray
                     rng = rng_seed(__float_as_uint(p0.w), 0u, 0u, frame);
+                    if constexpr (kBsdf) {  // whichever camera the launch has (a jittered one draws here)
+                        const CameraRay cr = camera_ray_xy<0>(cam, __float_as_uint(p0.x), __float_as_uint(p0.y), rng);
+                        o = cr.o;
+                        d = cr.d;
+                        rng = cr.seed;
+                        spec = false;
+                    } else {
                     const float jx = random_float(rng);
                     const float jy = random_float(rng);
                     const CameraPose pose = camera_record(cam).pose;
                     o = pose.o;
                     d = camera_ray_dir(pose, __float_as_uint(p0.x), __float_as_uint(p0.y), jx, jy, cam.inv_w, cam.inv_h,
                                        cam.aspect);
+                    }
                     T = F3{1.f, 1.f, 1.f};
                     L = F3{0.f, 0.f, 0.f};
                     bc = 0u;
@@ -2141,7 +2255,10 @@ constexpr uint32_t kFrameBvhBatchLds = 64;   // ... for a scene held whole in LD
 // run with kEnv = 2.
 // kRgba: the resolve fused into the launch (cam.rgba, spt_render_resolve_rgba8); a separate
 // instantiation, so the frames that are not resolved keep their code
-template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, bool kSmall = false, int kNee = 0, bool kRgba = false>
+// kBsdf: a scene with material models (shade_hit's kBsdf, scatter_specular); `spec`, the path's one bit of
+// material state, is a lane register. Generic kernels only, run with kEnv = 2 on hit_mode 0.
+template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, bool kSmall = false, int kNee = 0, bool kRgba = false,
+          bool kBsdf = false>
 __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsWavesBvh : kPathsWaves)) void k_frame(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                                   const float4* __restrict__ nodes, uint32_t n_prims,
                                                   float4* __restrict__ accum,
@@ -2269,6 +2386,7 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
     // any-hit), its estimate sadd, and — every draw of the hit made at the hit, in the oracle's order:
     // light sample, roulette, direction — whether the path goes on after it (`after`) along nd
     bool shadow = false, after = false;
+    bool spec = false;  // kBsdf: the path's previous vertex was METAL or DIELECTRIC
     float smax = 0.f;
     F3 nd{0.f, 0.f, 0.f}, sadd{0.f, 0.f, 0.f};
     // A scene held whole in LDS (its primitive records copied above) traverses in a few LDS round
@@ -2328,15 +2446,26 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
                     } else {
                         bool alive;
                         F3 add, n;
-                        const bool contributes = shade_hit<kEnv, !kBvh, true>(sh_prims, sh_mats, sp, bc + 1u, best_t,
-                                                                              best_k, o, d, T, rng, alive, add, n);
+                        ModelHit mh{0u, true, false};
+                        bool contributes;
+                        if constexpr (kBsdf)
+                            contributes = shade_hit<kEnv, !kBvh, true, true>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d,
+                                                                             T, rng, alive, add, n, &mh, spec);
+                        else
+                            contributes = shade_hit<kEnv, !kBvh, true>(sh_prims, sh_mats, sp, bc + 1u, best_t,
+                                                                       best_k, o, d, T, rng, alive, add, n);
                         if (contributes) L = F3{L.x + add.x, L.y + add.y, L.z + add.z};
                         if (kStats) {
                             atomicAdd(&s_seg[bc], 1u);
                             if (contributes) atomicAdd(&s_rmw[bc], 1u);
                         }
                         ++bc;
-                        if (alive) {  // light sample, Russian roulette, then get_random_bounche (:264-274)
+                        if (kBsdf && alive && mh.word != 0u) {  // METAL / DIELECTRIC: no light sample; roulette, the model
+                            spec = true;
+                            if (rr_continue(sp, bc, T, rng) && scatter_specular<true>(mh, n, sp.flags, o, d, rng)) trace = true;
+                            else done = true;
+                        } else if (alive) {  // light sample, Russian roulette, then get_random_bounche (:264-274)
+                            if (kBsdf) spec = false;
                             o = offset_origin(o, n);
                             F3 w;
                             float tm;
@@ -2389,16 +2518,29 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
                 } else {
                 bool alive;
                 F3 add, n;
-                const bool contributes =
-                    shade_hit<kEnv, !kBvh>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, n);
+                ModelHit mh{0u, true, false};
+                bool contributes;
+                if constexpr (kBsdf)
+                    contributes = shade_hit<kEnv, !kBvh, false, true>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng,
+                                                                      alive, add, n, &mh);
+                else
+                    contributes = shade_hit<kEnv, !kBvh>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, n);
                 if (contributes) L = F3{L.x + add.x, L.y + add.y, L.z + add.z};
                 if (kStats) {
                     atomicAdd(&s_seg[bc], 1u);
                     if (contributes) atomicAdd(&s_rmw[bc], 1u);
                 }
                 ++bc;
+                if constexpr (kBsdf) {  // a METAL / DIELECTRIC hit sets o and d itself, and may absorb the path
+                    if (alive && mh.word != 0u) {
+                        alive = scatter_specular<true>(mh, n, sp.flags, o, d, rng);
+                    } else if (alive) {
+                        o = offset_origin(o, n);
+                        d = bounce_dir<true>(n, rng, sp.flags);
+                    }
+                }
                 if (alive) {
-                    d = bounce_dir<true>(n, rng, sp.flags);  // get_random_bounche (:273-274)
+                    if (!kBsdf) d = bounce_dir<true>(n, rng, sp.flags);  // get_random_bounche (:273-274)
                     if (kBvh) {
                         trav_init(tv, d);
                         tdone = false;
@@ -2467,6 +2609,7 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
                 L = F3{0.f, 0.f, 0.f};
                 rng = cr.seed;
                 bc = 0;
+                if (kBsdf) spec = false;
                 have = true;
                 if (kBvh) {
                     trav_init(tv, d);
@@ -2694,11 +2837,11 @@ void launch_shade_kernel(const PassParams& p, uint32_t bounce, bool fused, hipSt
     const QueueBufs& nxt = p.q[(bounce + 1u) & 1u];
     const CameraParams cam = camera_params(p);
     with_bools(
-        [&](auto primary, auto fused_c, auto bvh, auto nee) {
-            k_shade<primary(), fused_c(), bvh(), nee()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.hit, cur, nxt,
-                                                                                p.radiance, p.counts, sp, cam, p.nee);
+        [&](auto primary, auto fused_c, auto bvh, auto nee, auto bsdf) {
+            k_shade<primary(), fused_c(), bvh(), nee(), bsdf()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, p.hit, cur, nxt,
+                                                                                        p.radiance, p.counts, sp, cam, p.nee);
         },
-        bounce == 0, fused, p.nodes != nullptr, p.nee.n_emit != 0u);
+        bounce == 0, fused, p.nodes != nullptr, p.nee.n_emit != 0u, p.bsdf != 0u);
 }
 }  // namespace
 
@@ -2709,10 +2852,10 @@ void launch_trace_tail(const PassParams& p, uint32_t bounce, hipStream_t s) {
     const ShadeParams sp = shade_params(p, bounce);
     const QueueBufs& cur = p.q[bounce & 1u];
     with_bools(
-        [&](auto bvh, auto nee) {
-            k_trace_tail<bvh(), nee()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
+        [&](auto bvh, auto nee, auto bsdf) {
+            k_trace_tail<bvh(), nee(), bsdf()><<<p.n_sub, kBlock, 0, s>>>(p.prims, p.nodes, p.n_prims, p.mats, cur, p.radiance, p.counts, sp, p.n_sub, p.nee);
         },
-        p.nodes != nullptr, p.nee.n_emit != 0u);
+        p.nodes != nullptr, p.nee.n_emit != 0u, p.bsdf != 0u);
 }
 
 // The first tier's chunks of a flat k_paths launch, longest first: chunk indices sorted by decreasing
@@ -2764,6 +2907,15 @@ const void* kp(K* kernel) {
 // nullptr: no such kernel (paths_variant never asks for one).
 const void* paths_kernel(const PathsVariant& v) {
     const bool env = v.env == 1;
+    if (v.bsdf) {  // the kBsdf forms (they read the camera's kind at run time): as the kJitter ones, and every emitter kind
+        if (v.env != 2 || v.simd_waves || v.chan || v.jitter || v.nee == kNeeNoSpheres) return nullptr;
+        if (!v.bvh) {
+            if (v.nee) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll, false, true>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll, false, true>);
+            return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, 0, false, true>) : kp(k_paths<false, false, 2, 0, 0, false, 0, false, true>);
+        }
+        if (v.nee) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll, false, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll, false, true>);
+        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, 0, false, true>) : kp(k_paths<false, true, 2, 0, 0, false, 0, false, true>);
+    }
     if (v.jitter) {  // the kJitter forms: the sky's kind at run time, no 8-wave and no channel-lane kernel
         if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee == kNeeNoSpheres)) return nullptr;
         if (!v.bvh) {
@@ -2798,6 +2950,19 @@ const void* paths_kernel(const PathsVariant& v) {
 // ... and k_frame's: 16 without the fused resolve, 9 with it (kRgba has no stats form)
 const void* frame_kernel(const FrameVariant& v) {
     const bool env = v.env == 1;
+    if (v.bsdf) {  // the kBsdf forms: kEnv 2, never the LDS-held form, every emitter kind; 8 and 4 with the fused resolve
+        if (v.env != 2 || v.small || v.nee == kNeeNoSpheres || (v.rgba && v.stats)) return nullptr;
+        if (v.rgba) {
+            if (v.nee) return v.bvh ? kp(k_frame<false, true, 2, 0, false, kNeeAll, true, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, true, true>);
+            return v.bvh ? kp(k_frame<false, true, 2, 0, false, 0, true, true>) : kp(k_frame<false, false, 2, 0, false, 0, true, true>);
+        }
+        if (v.nee) {
+            if (v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeAll, false, true>) : kp(k_frame<false, true, 2, 0, false, kNeeAll, false, true>);
+            return v.stats ? kp(k_frame<true, false, 2, 0, false, kNeeAll, false, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, false, true>);
+        }
+        if (v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, 0, false, true>) : kp(k_frame<false, true, 2, 0, false, 0, false, true>);
+        return v.stats ? kp(k_frame<true, false, 2, 0, false, 0, false, true>) : kp(k_frame<false, false, 2, 0, false, 0, false, true>);
+    }
     if (v.nee ? (v.env != 2 || v.small || (!v.bvh && v.nee != kNeeAll)) : v.env > 1) return nullptr;
     if (v.small && (!v.bvh || v.stats)) return nullptr;
     if (v.rgba) {

@@ -20,6 +20,8 @@ struct PathsVariant {
     bool chan;       // the channel-lane kernel of flat scenes whose chunks are all <= 16 pixels (a small row shard)
     int nee;         // 0, kNeeAll, or kNeeNoSpheres (a BVH scene without sphere lights)
     bool jitter = false;  // the kJitter form (a jittered camera): every path traces its camera segment; env 2 only
+    bool bsdf = false;    // the kBsdf form (a scene with material models): starts every path at bounce 0 too and reads
+                          // the camera's kind at run time, so `jitter` stays false; env 2, nee 0 or kNeeAll
 };
 struct FrameVariant {
     bool stats, bvh;
@@ -28,6 +30,7 @@ struct FrameVariant {
     int nee;
     bool rgba;   // the resolve fused into the frame; it has no stats form
     bool jitter = false;  // a jittered camera: the same kernels on hit_mode 0 (no camera-hit cache, no lists)
+    bool bsdf = false;    // the kBsdf kernels (a scene with material models): hit_mode 0, env 2, never `small`
 };
 
 inline int nee_variant(const PassParams& p) {
@@ -39,6 +42,12 @@ inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t firs
     const bool bvh = p.nodes != nullptr;
     const int nee = nee_variant(p);
     PathsVariant v{stats, bvh, nee ? 2 : (p.env ? 1 : 0), 0, false, nee};
+    if (p.bsdf) {  // one generic form per (stats, bvh, nee on or off), whatever the camera
+        v.env = 2;
+        v.nee = nee ? kNeeAll : 0;
+        v.bsdf = true;
+        return v;
+    }
     if (p.cam_mode == kCamJitter) {  // one generic form per (stats, bvh, nee): no 8-wave, no channel-lane kernel
         v.env = 2;
         v.jitter = true;
@@ -52,13 +61,15 @@ inline FrameVariant frame_variant(const PassParams& p, bool stats) {
     const bool rgba = p.rgba != nullptr;
     stats = stats && !rgba;
     const int nee = nee_variant(p);
+    if (p.bsdf) return FrameVariant{stats, p.nodes != nullptr, 2, false, nee ? kNeeAll : 0, rgba, p.cam_mode == kCamJitter, true};
     return FrameVariant{stats, p.nodes != nullptr, nee ? 2 : (p.env ? 1 : 0), frame_small_scene(p, stats), nee, rgba,
                         p.cam_mode == kCamJitter};
 }
 // k_frame's hit_mode for a launch: a jittered camera's segment differs per frame, so its launches neither
-// store nor read the camera-hit cache and take no lists, whatever the ctx holds
+// store nor read the camera-hit cache and take no lists, whatever the ctx holds; nor do the launches of a
+// scene with material models (the kBsdf kernels trace every camera segment)
 inline uint32_t frame_hit_mode(const PassParams& p, bool cache_valid, bool lists) {
-    if (p.cam_mode == kCamJitter) return 0u;
+    if (p.cam_mode == kCamJitter || p.bsdf) return 0u;
     return !cache_valid ? 1u : (lists ? 3u : 2u);
 }
 
@@ -69,11 +80,11 @@ struct JitKind {
 };
 constexpr JitKind kJitNone{-1, 0};
 inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.stats || v.jitter) return kJitNone;
+    if (!shape || v.bvh || v.stats || v.jitter || v.bsdf) return kJitNone;
     return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
 }
 inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.stats) return kJitNone;
+    if (!shape || v.bvh || v.stats || v.bsdf) return kJitNone;
     return JitKind{v.rgba ? (v.nee ? kJitFrameNeeRgba : kJitFrameRgba) : (v.nee ? kJitFrameNee : kJitFrame), v.env};
 }
 // The kinds a flat scene's renders may ask for: compiled ahead by spt_set_scene, waited for by
