@@ -165,7 +165,8 @@ struct CameraPose {
 // host (spt_camera_ray) and every kernel compile this one function. On the device a lane whose
 // operands are inside sqrt_unit's and div_ref's ranges (q in [2^-80, 2^40), so len in [2^-40, 2^20);
 // every numerator in [2^-100, 2^50] in magnitude — a zero one takes the general division, which keeps
-// its sign) runs those forms: the same bits (tests/cpp/test_device_math.hip).
+// its sign) runs those forms: the same bits (tests/cpp/test_device_rays.hip compares the device build
+// with the host's on cameras placed on either side of every term of the gate).
 __host__ __device__ inline F3 camera_ray_dir(const CameraPose& c, uint32_t x, uint32_t y, float jx, float jy,
                                              float inv_w, float inv_h, float aspect) {
     const float px = (float)x + jx;

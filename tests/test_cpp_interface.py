@@ -108,6 +108,34 @@ def test_device_sqrt_unit_exhaustive(exe):
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
 
 
+DEVICE_RAYS = os.path.join(ROOT, "tests", "cpp", "test_device_rays")
+
+
+def test_device_ray_inputs_reach_their_branches(exe):
+    """tests/cpp/test_device_rays --host (no kernel runs): the inputs it aims at spt_device.h's branch points
+    reach them — every coverage counter is non-zero, among them a `redo` lane, a disc = 0 lane and an
+    alpha = -0 lane — and the host builds of the camera, bounce, BSDF step and octa_texel match the oracle."""
+    r = subprocess.run([DEVICE_RAYS, "--host"], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
+    assert "host only" in r.stdout
+    for counter in ("redo=", "disc=0=", "alpha=-0="):
+        assert counter in r.stdout and counter + "0 " not in r.stdout, counter
+
+
+@pytest.mark.gpu
+def test_device_ray_steps_match_the_oracle(exe):
+    """spt_device.h on the GPU, function by function, bit for bit against the oracle's plain C: the camera's
+    fast path on both sides of every term of its gate, the intersectors' general and fast forms with the
+    `redo` protocol, sincos_2pi / bounce_dir, bsdf_scatter, light_sample and octa_texel.
+    (The oracle side takes about 2 s single-threaded on a slow core, under 1 s beside an MI355X, where the
+    whole run took 1.2 s: timeout 120 s.)"""
+    r = subprocess.run([DEVICE_RAYS], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
+    assert " 0 mismatches" in r.stdout and "first:" not in r.stdout
+
+
 REF_INCLUDE = "/root/reference/libs/render/include"
 CSRC = os.path.join(ROOT, "software-path-tracer_amd", "csrc")
 COMPAT = os.path.join(ROOT, "tests", "compat")  # glm declarations for the compile check only
