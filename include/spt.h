@@ -359,6 +359,81 @@ int spt_set_material_models(spt_ctx* ctx, const spt_material_model* models, uint
 int spt_bsdf_sample(const spt_material_model* model, const float d[3], const float n[3], int entering,
                     uint32_t flags, uint32_t* rng, float dir_out[3], int* transmitted, int* absorbed);
 
+/* ---- first-hit features and the denoiser (superset: the reference shows the noisy mean) -------------
+ * spt_render_features traces one camera ray per shard pixel — the reference's pinhole without a camera,
+ * the posed camera's ray through the pixel's corner (jx = jy = 0), through (0.5f, 0.5f) with
+ * SPT_CAMERA_JITTER: the bits spt_camera_ray gives; no RNG draw — finds its closest hit as spt_render
+ * does (smallest t >= 0.001, ties to the lowest index) and writes three float4 images, laid out and
+ * row-sharded as the accumulation buffer:
+ *   feat_a = (P.x, P.y, P.z, bits(material)),  P.c = o.c + t*d.c        miss: (0, 0, 0, bits 0xFFFFFFFF)
+ *   feat_b = (n.x, n.y, n.z, t)                                          miss: (0, 0, 0, +inf)
+ *   albedo = (albedo.r, albedo.g, albedo.b, bits(primitive))             miss: (0, 0, 0, bits 0xFFFFFFFF)
+ * material: spt_prim.material; primitive: the index into spt_set_scene's array; n: the shading normal,
+ * ng * (1.0f / sqrtf((ng.x*ng.x + ng.y*ng.y) + ng.z*ng.z)) with ng = P - centre for a sphere (outward,
+ * never flipped) and the stored normal of a quad or triangle flipped to face the ray. Material models do
+ * not change the images (a mirror reports its own surface). The buffers are allocated by the first call
+ * and kept until spt_set_scene, spt_update_prims, spt_configure or spt_set_camera invalidates them.
+ * Asynchronous on the ctx stream; touches neither the accumulation, the frame count, the one-frame
+ * kernel's camera-hit cache nor any spt_stats field. SPT_ERR_NO_SCENE / SPT_ERR_NOT_CONFIGURED as spt_render. */
+int spt_render_features(spt_ctx* ctx);
+/* Copy the shard's feature images to the host (n_pixels * 4 floats each; any pointer may be NULL),
+ * rendering them first if they are stale. Waits for the stream. */
+int spt_read_features(spt_ctx* ctx, float* feat_a, float* feat_b, float* albedo);
+/* Device pointers of the three images (any out pointer may be NULL) and the byte size of each, rendering
+ * them first if they are stale; valid until the next call that invalidates them. */
+int spt_features_device_ptr(spt_ctx* ctx, void** feat_a, void** feat_b, void** albedo, size_t* bytes);
+
+/* The denoiser: an edge-avoiding a-trous wavelet filter of the mean colour c = accum / (float)frame_count
+ * (all four channels), guided by feat_a and feat_b. `levels` passes; the first reads c, the others the
+ * pass before. Level l has step s = 1 << l, inv_c = 1.0f / (sigma_color * 2^-l) and
+ * inv_z = 1.0f / (sigma_plane * (float)s). All in fp32 without contraction, every '/' correctly rounded:
+ *   lum(v) = L / (1.0f + L),  L = (0.2126f*v.r + 0.7152f*v.g) + 0.0722f*v.b   (compressed: a firefly at
+ *   any value is an outlier);  dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  H = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ * A pixel p whose camera ray missed keeps c_p. A pixel that hit visits its 25 taps q = p + (dx, dy),
+ * j = 0..4 outer with dy = (j-2)*s, i = 0..4 inner with dx = (i-2)*s:
+ *   k  = H[j] * H[i]
+ *   dl = (lum(c_q) - lum(c_p)) * inv_c;  r = 1.0f / (1.0f + dl*dl);  wc = k * (r*r)
+ *   dn = fmaxf(dot(N_p, N_q), 0.0f), then dn = dn*dn normal_power_log2 times
+ *   e  = P_q - P_p;  pd = dot(N_p, e) * inv_z;  rz = 1.0f / (1.0f + pd*pd);  geo = dn * (rz*rz)
+ *   w  = wc * geo, and w = 0 unless q is inside the image and has p's material (a miss has none)
+ *   sum.c += w * c_q.c (c = r, g, b: multiply, then add);  sum_w += w
+ * and out.rgb = sum.rgb / sum_w, out.a = c_p.a (the centre tap has w > 0). */
+typedef struct spt_denoise_params {   /* 32 bytes */
+    uint32_t levels;             /* 1..6; default 5                                     */
+    float    sigma_color;        /* > 0, finite; default 1.0f                           */
+    float    sigma_plane;        /* > 0, finite, world units; default 0.05f             */
+    uint32_t normal_power_log2;  /* 0..7; default 5 (the normals' cosine to the 32nd)   */
+    uint32_t reserved[4];        /* must be 0                                           */
+} spt_denoise_params;
+/* Host only: the defaults above. SPT_ERR_INVALID for NULL. */
+int spt_denoise_params_default(spt_denoise_params* out);
+/* Filter the frames accumulated so far (frame_count: the divisor) into the ctx's denoised image; the
+ * features are rendered first if they are stale. params = NULL: the defaults. Asynchronous on the ctx
+ * stream; the accumulation, the frame count and the stats are untouched. SPT_ERR_NO_SCENE /
+ * SPT_ERR_NOT_CONFIGURED as spt_render; SPT_ERR_INVALID for frame_count == 0, a parameter out of range,
+ * a non-zero reserved word, or a ctx that renders a row shard (shard_count != 1: the filter needs the
+ * whole image). */
+int spt_denoise(spt_ctx* ctx, uint32_t frame_count, const spt_denoise_params* params);
+/* Measurement and tests (the image never depends on it): the kernel form of every level of later
+ * spt_denoise calls: 0 one thread per pixel with 25 global taps, 1 a residue class's tile staged in LDS,
+ * -1 (the default) whichever measured faster at each step. SPT_ERR_INVALID otherwise. */
+int spt_set_denoise_form(spt_ctx* ctx, int form);
+/* The last spt_denoise's image: copied to the host (n_pixels * 4 floats; waits for the stream), or its
+ * device pointer and byte size (valid until the next spt_denoise or spt_configure). SPT_ERR_INVALID
+ * before any spt_denoise since the last spt_configure. */
+int spt_read_denoised(spt_ctx* ctx, float* host_rgba);
+int spt_denoised_device_ptr(spt_ctx* ctx, void** dptr, size_t* bytes);
+/* spt_resolve_rgba8_exposure of the denoised image (it is a mean: divisor 1), into the registered host
+ * buffer directly when host_out is that buffer, through the staging copy otherwise; waits for the stream.
+ * SPT_ERR_INVALID before any spt_denoise. */
+int spt_resolve_denoised_rgba8(spt_ctx* ctx, float exposure, uint32_t* host_out);
+/* Host only, no device needed: the filter above on the caller's arrays by the function the kernels
+ * compile (csrc/spt_atrous.h atrous_pixel): the same bits as spt_denoise. rgba: the mean colour,
+ * feat_a / feat_b: the features, out: the result; width * height * 4 floats each (out may be rgba).
+ * params = NULL: the defaults. SPT_ERR_INVALID for a null array, a zero size or an invalid parameter. */
+int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
+                    const spt_denoise_params* params, float* out);
+
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */
 /* Miss radiance from an octahedral environment map instead of sample_sky's gradient (only while

@@ -166,6 +166,9 @@ EXPORTED_SYMBOLS = (
     "spt_specialize_scene", "spt_compile_flat_kernels", "spt_update_prims",
     "spt_set_camera", "spt_camera_look_at", "spt_camera_ray",
     "spt_set_material_models", "spt_bsdf_sample",
+    "spt_render_features", "spt_read_features", "spt_features_device_ptr",
+    "spt_denoise_params_default", "spt_denoise", "spt_set_denoise_form", "spt_read_denoised", "spt_denoised_device_ptr",
+    "spt_resolve_denoised_rgba8", "spt_atrous_host",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -191,6 +194,30 @@ class SptTuning(ctypes.Structure):
             if k not in dict(self._fields_):
                 raise TypeError(f"unknown spt_tuning field {k}")
             setattr(self, k, v)
+
+
+class DenoiseParams(ctypes.Structure):
+    """spt_denoise_params (32 bytes): the a-trous filter's levels (1..6), colour and plane-distance widths
+    (> 0) and the normal weight's exponent as log2 (0..7). DenoiseParams() holds the library's defaults
+    (spt_denoise_params_default); keyword arguments replace single fields."""
+    _fields_ = [
+        ("levels", ctypes.c_uint32),
+        ("sigma_color", ctypes.c_float),
+        ("sigma_plane", ctypes.c_float),
+        ("normal_power_log2", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        rc = load_library().spt_denoise_params_default(ctypes.byref(self))
+        if rc != SPT_OK:
+            raise SptError(f"spt_denoise_params_default -> {SPT_ERR.get(rc, rc)}")
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown spt_denoise_params field {k}")
+            setattr(self, k, v)
+
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -256,6 +283,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_bsdf_sample": ([P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), I, U32,
                              ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(I),
                              ctypes.POINTER(I)], I),
+        "spt_render_features": ([P], I),
+        "spt_read_features": ([P, P, P, P], I),
+        "spt_features_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P),
+                                     ctypes.POINTER(ctypes.c_size_t)], I),
+        "spt_denoise_params_default": ([ctypes.POINTER(DenoiseParams)], I),
+        "spt_denoise": ([P, U32, ctypes.POINTER(DenoiseParams)], I),
+        "spt_set_denoise_form": ([P, I], I),
+        "spt_read_denoised": ([P, P], I),
+        "spt_denoised_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)], I),
+        "spt_resolve_denoised_rgba8": ([P, ctypes.c_float, P], I),
+        "spt_atrous_host": ([P, P, P, U32, U32, ctypes.POINTER(DenoiseParams), P], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -358,6 +396,23 @@ def bsdf_sample(kind: int, param: float, d, n, entering: bool, state: int, flags
     if rc != SPT_OK:
         raise SptError(f"spt_bsdf_sample -> {SPT_ERR.get(rc, rc)}")
     return out, bool(tr.value), bool(ab.value), st.value
+
+
+def atrous_host(rgba: np.ndarray, feat_a: np.ndarray, feat_b: np.ndarray,
+                params: Optional[DenoiseParams] = None) -> np.ndarray:
+    """spt_atrous_host (host only): the denoiser's filter on (h, w, 4) float32 arrays — the mean colour and
+    the two feature images — by the function the kernels compile: the same bits as Context.denoise."""
+    c = np.ascontiguousarray(rgba, dtype=np.float32)
+    a = np.ascontiguousarray(feat_a, dtype=np.float32)
+    b = np.ascontiguousarray(feat_b, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 4 or a.shape != c.shape or b.shape != c.shape:
+        raise ValueError("atrous_host: rgba, feat_a and feat_b must be (height, width, 4) arrays of one shape")
+    out = np.zeros_like(c)
+    rc = load_library().spt_atrous_host(_ptr(c), _ptr(a), _ptr(b), c.shape[1], c.shape[0],
+                                        ctypes.byref(params) if params is not None else None, _ptr(out))
+    if rc != SPT_OK:
+        raise SptError(f"spt_atrous_host -> {SPT_ERR.get(rc, rc)}")
+    return out
 
 
 def build_scene(scene: "int | str") -> Tuple[np.ndarray, np.ndarray, SptEnv]:
@@ -600,6 +655,57 @@ class Context:
         m = material_models(models)
         self._check(self.lib.spt_set_material_models(self.h, m.ctypes.data, len(m)), "spt_set_material_models")
 
+    def render_features(self) -> None:
+        """spt_render_features: the first-hit feature images of the current scene, camera and configuration
+        (asynchronous; read them with read_features)."""
+        self._check(self.lib.spt_render_features(self.h), "spt_render_features")
+
+    def read_features(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """spt_read_features: (feat_a, feat_b, albedo), each (shard_pixels, 4) float32 — position and material
+        bits, shading normal and distance, albedo and primitive bits; view the bit lanes as uint32."""
+        n = self.shard_pixels
+        a, b, alb = (np.zeros((n, 4), dtype=np.float32) for _ in range(3))
+        self._check(self.lib.spt_read_features(self.h, _ptr(a), _ptr(b), _ptr(alb)), "spt_read_features")
+        return a, b, alb
+
+    def features_device_ptr(self) -> Tuple[int, int, int, int]:
+        """spt_features_device_ptr: (feat_a, feat_b, albedo, bytes of each)."""
+        a, b, alb, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.lib.spt_features_device_ptr(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(alb),
+                                                     ctypes.byref(n)), "spt_features_device_ptr")
+        return a.value or 0, b.value or 0, alb.value or 0, n.value
+
+    def denoise(self, frame_count: int, params: Optional[DenoiseParams] = None) -> None:
+        """spt_denoise: filter the mean of the frame_count frames accumulated so far into the ctx's denoised
+        image (asynchronous); params None: the defaults."""
+        self._check(self.lib.spt_denoise(self.h, frame_count, ctypes.byref(params) if params is not None else None),
+                    "spt_denoise")
+
+    def set_denoise_form(self, form: int) -> None:
+        """spt_set_denoise_form (measurement and tests): 0 the straight kernel form at every level of later
+        denoise calls, 1 the LDS-tiled one, -1 the library's choice per step. The image is the same."""
+        self._check(self.lib.spt_set_denoise_form(self.h, form), "spt_set_denoise_form")
+
+    def read_denoised(self) -> np.ndarray:
+        out = np.zeros((self.shard_pixels, 4), dtype=np.float32)
+        self._check(self.lib.spt_read_denoised(self.h, _ptr(out)), "spt_read_denoised")
+        return out
+
+    def denoised_device_ptr(self) -> Tuple[int, int]:
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.lib.spt_denoised_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n)), "spt_denoised_device_ptr")
+        return p.value or 0, n.value
+
+    def resolve_denoised_rgba8(self, exposure: float = 1.0, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """spt_resolve_denoised_rgba8: the denoised image as RGBA8 (into the registered buffer directly when
+        `out` is that array)."""
+        if out is None:
+            out = np.zeros(self.shard_pixels, dtype=np.uint32)
+        elif out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"] or out.size < self.shard_pixels:
+            raise SptError("resolve_denoised_rgba8: out must be a C-contiguous uint32 array of >= shard_pixels")
+        self._check(self.lib.spt_resolve_denoised_rgba8(self.h, exposure, _ptr(out)), "spt_resolve_denoised_rgba8")
+        return out
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -805,6 +911,13 @@ class HIPPathTracer(PathTracer):
         self._camera_dirty = False
         self._models = None
         self._models_dirty = False
+        self._denoise: Optional[DenoiseParams] = None
+
+    def set_denoise(self, params: Optional[DenoiseParams]) -> None:
+        """Not in the reference interface: while params is not None, get_render_result() returns the denoised
+        image (Context.denoise with these parameters) of the frames accumulated so far; None (the default)
+        returns the plain mean. render() and the accumulation are the same either way."""
+        self._denoise = params
 
     def set_scene(self, scene: Scene) -> None:
         self._scene = scene
@@ -884,6 +997,10 @@ class HIPPathTracer(PathTracer):
         if self._frame_count <= 0:
             raise SptError("No frames rendered yet")  # CPUPathTracer.cpp:89
         exposure = self._settings.getExposure() if self._settings_mode else 1.0
+        if self._denoise is not None:
+            self._ctx.denoise(self._frame_count, self._denoise)
+            self._result.image_buffer = self._ctx.resolve_denoised_rgba8(exposure)
+            return self._result
         self._result.image_buffer = self._ctx.resolve_rgba8(self._frame_count, exposure)
         return self._result
 

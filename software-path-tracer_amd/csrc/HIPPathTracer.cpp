@@ -72,7 +72,7 @@ namespace render
 		// (:61); settings mode: getSamplesPerPixel() such frames in one call (k_paths from 4)
 		const uint32_t n = m_settingsMode ? std::max<uint32_t>(1u, m_renderSettings->getSamplesPerPixel()) : 1u;
 		m_resolvedAt = 0;
-		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES)
+		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn)
 		{
 			// the App reads the result after every render() (App.cpp:230-240): a one-frame call's resolve
 			// rides in the frame's own launch, its pixels stored into the registered result buffer as their
@@ -113,10 +113,25 @@ namespace render
 		m_modelsChanged = true;
 	}
 
+	void HIPPathTracer::set_denoise(const spt_denoise_params *params)
+	{
+		m_denoiseOn = params != nullptr;
+		if (params)
+			m_denoise = *params;
+		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
+	}
+
 	const PathTracer::RenderResult &HIPPathTracer::get_render_result()
 	{
 		SPT_VERIFY(m_frameCount > 0, "No frames rendered yet");
 		const float exposure = m_settingsMode ? m_renderSettings->getExposure() : 1.0f;
+		if (m_denoiseOn)
+		{
+			// the filtered mean of the frames so far, resolved with divisor 1 (into the registered buffer)
+			SPT_CALL(m_ctx, spt_denoise(m_ctx, m_frameCount, &m_denoise));
+			SPT_CALL(m_ctx, spt_resolve_denoised_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
+			return m_render_result;
+		}
 		if (m_resolvedAt == m_frameCount && m_resolvedExposure == exposure)
 			return m_render_result; // resolved by render() (spt_render_resolve_rgba8), already in host memory
 		// device-side resolve: accum / frameCount, clamp, (uint8)(c * 255), rgba_to_uint32

@@ -61,6 +61,12 @@ namespace render
 		// (nullptr, 0) for all-diffuse. Kept across scene rebuilds; a change restarts the accumulation.
 		void set_material_models(const spt_material_model *models, uint32_t n);
 
+		// Not in the reference interface (it shows the noisy mean): while on, get_render_result() returns the
+		// denoised image (spt.h spt_denoise with these parameters; copied) of the frames accumulated so far.
+		// nullptr switches it off, which is the default. render() and the accumulation are the same either
+		// way, except that a one-frame render() does not fuse the plain resolve into its launch while on.
+		void set_denoise(const spt_denoise_params *params);
+
 	private:
 		void invalidate();
 		void rebuild_scene();
@@ -83,5 +89,7 @@ namespace render
 		bool m_cameraChanged = false;
 		std::vector<spt_material_model> m_models;  // set_material_models's (empty: all diffuse)
 		bool m_modelsChanged = false;
+		spt_denoise_params m_denoise{};            // set_denoise's, while m_denoiseOn
+		bool m_denoiseOn = false;
 	};
 } // namespace render

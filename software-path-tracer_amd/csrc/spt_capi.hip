@@ -18,6 +18,7 @@
 
 #include "scene.h"
 #include "spt.h"
+#include "spt_denoise.h"
 #include "spt_device.h"
 #include "spt_jit.h"
 #include "spt_kernels.h"
@@ -29,6 +30,7 @@ static_assert(kBvhStackMax == kBvhStackEntries, "scene.h and spt_kernels.h stack
 static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kMatDielectric == SPT_MAT_DIELECTRIC,
               "spt.h spt_material_kind and spt_device.h model_kind");
 static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
+static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes");
 
 namespace {
 
@@ -139,6 +141,20 @@ struct spt_ctx {
     bool fused = false;
 
     uint32_t frame_count = 0;
+
+    // spt_render_features: the first-hit images of the current scene, camera and configuration
+    // (configure-sized, allocated by the first call), and the caller's material index behind each device
+    // material (h_dev_mat, uploaded with the scene)
+    float4* feat_a = nullptr;
+    float4* feat_b = nullptr;
+    float4* feat_albedo = nullptr;
+    bool feat_valid = false;
+    uint32_t* d_mat_map = nullptr;
+    // spt_denoise: the filter's two ping-pong images (allocated by the first call) and which one holds
+    // the last call's result (-1: none)
+    float4* dn[2] = {nullptr, nullptr};
+    int dn_result = -1;
+    int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
 
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
@@ -255,6 +271,13 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->list_counts);
     c->hit_cache_valid = false;
     free_dev(c->resolved);
+    free_dev(c->feat_a);
+    free_dev(c->feat_b);
+    free_dev(c->feat_albedo);
+    c->feat_valid = false;
+    free_dev(c->dn[0]);
+    free_dev(c->dn[1]);
+    c->dn_result = -1;
 }
 
 // RCCL, resolved at run time (spt.h): the copy already in the process (PyTorch loads its own
@@ -327,6 +350,8 @@ void free_scene(spt_ctx* c) {
     free_dev(c->d_mats);
     free_dev(c->d_nodes);
     free_dev(c->d_emit);
+    free_dev(c->d_mat_map);
+    c->feat_valid = false;  // (the first hits were this scene's)
     c->n_prims = c->n_nodes = c->n_dev_nodes = c->n_emit = c->n_emit_spheres = 0;
     c->has_scene = false;
 }
@@ -726,6 +751,10 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     }
     SPT_HIP(c, hipMalloc(&c->d_mats, sizeof(DevMaterial) * n_mats));
     SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * n_mats, hipMemcpyHostToDevice));
+    if (dev_mat.empty())  // (a BVH scene keeps the caller's materials as they are)
+        for (uint32_t i = 0; i < n_mats; ++i) dev_mat.push_back(i);
+    SPT_HIP(c, hipMalloc(&c->d_mat_map, sizeof(uint32_t) * dev_mat.size()));
+    SPT_HIP(c, hipMemcpy(c->d_mat_map, dev_mat.data(), sizeof(uint32_t) * dev_mat.size(), hipMemcpyHostToDevice));
     if (!emit.empty()) {
         SPT_HIP(c, hipMalloc(&c->d_emit, sizeof(DevEmitter) * emit.size()));
         SPT_HIP(c, hipMemcpy(c->d_emit, emit.data(), sizeof(DevEmitter) * emit.size(), hipMemcpyHostToDevice));
@@ -758,8 +787,6 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     c->flat_rect = flat_rect;
     c->h_prims.swap(keep_prims);
     c->h_mats.swap(keep_mats);
-    if (dev_mat.empty())
-        for (uint32_t i = 0; i < n_mats; ++i) dev_mat.push_back(i);
     c->h_dev_mat.swap(dev_mat);
     c->h_dm.swap(dm);
     c->h_models.clear();  // a new scene's materials are all DIFFUSE
@@ -806,6 +833,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     for (uint32_t j = 0; j < n; ++j)
         if (indices[j] >= total) return fail(c, SPT_ERR_INVALID, "spt_update_prims: index out of range");
     c->hit_cache_valid = false;  // (moved primitives: k_frame traces the camera segments again)
+    c->feat_valid = false;       // (... and spt_render_features the first hits)
     c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
     // the edits are staged and committed to the host mirror only once the device holds them, so a
     // failed call leaves the ctx's scene as it was
@@ -968,6 +996,8 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
         SPT_HIP(c, hipMalloc(&c->resolved, sizeof(uint32_t) * std::max<size_t>(pixels, 1)));
     }
     c->hit_cache_valid = false;  // (a new image size, shard or flags: the camera hits are traced again)
+    c->feat_valid = false;
+    c->dn_result = -1;  // (no denoised image of this configuration yet)
     c->chunk_order_key = 0;
     const size_t qn = (size_t)cap * c->n_sub;
     if ((cfg->flags & SPT_FLAG_SORTED_RAYS) && qn && !c->ray_perm) {  // the sorted schedule's buffers
@@ -1312,6 +1342,7 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     c->hit_cache_valid = false;
     c->frame_lists = false;
     c->chunk_order_key = 0;
+    c->feat_valid = false;  // (the first hits were the previous camera's)
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
     return SPT_OK;
@@ -1362,6 +1393,193 @@ int spt_bsdf_sample(const spt_material_model* model, const float d[3], const flo
     dir_out[2] = s.dir.z;
     *transmitted = s.transmitted ? 1 : 0;
     *absorbed = s.absorbed ? 1 : 0;
+    return SPT_OK;
+}
+
+// ---- first-hit features and the denoiser ---------------------------------------------------------
+
+namespace {
+const spt_denoise_params kDenoiseDefaults = {5u, 1.0f, 0.05f, 5u, {0u, 0u, 0u, 0u}};
+// nullptr: valid
+const char* denoise_params_error(const spt_denoise_params& p) {
+    if (p.levels < 1u || p.levels > kAtrousMaxLevels) return "spt_denoise_params: levels outside 1..6";
+    if (!(p.sigma_color > 0.0f) || !std::isfinite(p.sigma_color)) return "spt_denoise_params: sigma_color must be > 0 and finite";
+    if (!(p.sigma_plane > 0.0f) || !std::isfinite(p.sigma_plane)) return "spt_denoise_params: sigma_plane must be > 0 and finite";
+    if (p.normal_power_log2 > kAtrousMaxNormalPower) return "spt_denoise_params: normal_power_log2 outside 0..7";
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_denoise_params: reserved must be 0";
+    return nullptr;
+}
+// the images are those of the current scene, camera and configuration (rendered now if they are not)
+int ensure_features(spt_ctx* c) {
+    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "features before spt_configure");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->feat_valid || c->pixels == 0) return SPT_OK;
+    if (!c->feat_a) {  // all three, or none
+        float4 *a = nullptr, *b = nullptr, *alb = nullptr;
+        const size_t bytes = sizeof(float4) * c->pixels;
+        if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess || hipMalloc(&alb, bytes) != hipSuccess) {
+            free_dev(a);
+            free_dev(b);
+            free_dev(alb);
+            (void)hipGetLastError();
+            return fail(c, SPT_ERR_HIP, "spt_render_features: allocation failed");
+        }
+        c->feat_a = a;
+        c->feat_b = b;
+        c->feat_albedo = alb;
+    }
+    launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, c->stream);
+    SPT_HIP(c, hipGetLastError());
+    c->feat_valid = true;
+    return SPT_OK;
+}
+}  // namespace
+
+int spt_render_features(spt_ctx* c) {
+    if (!c) return SPT_ERR_INVALID;
+    return ensure_features(c);
+}
+
+int spt_read_features(spt_ctx* c, float* feat_a, float* feat_b, float* albedo) {
+    if (!c) return SPT_ERR_INVALID;
+    const int rc = ensure_features(c);
+    if (rc != SPT_OK || c->pixels == 0) return rc;
+    const size_t bytes = sizeof(float4) * c->pixels;
+    if (feat_a) SPT_HIP(c, hipMemcpyAsync(feat_a, c->feat_a, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (feat_b) SPT_HIP(c, hipMemcpyAsync(feat_b, c->feat_b, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (albedo) SPT_HIP(c, hipMemcpyAsync(albedo, c->feat_albedo, bytes, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return SPT_OK;
+}
+
+int spt_features_device_ptr(spt_ctx* c, void** feat_a, void** feat_b, void** albedo, size_t* bytes) {
+    if (!c || !bytes) return SPT_ERR_INVALID;
+    const int rc = ensure_features(c);
+    if (rc != SPT_OK) return rc;
+    if (feat_a) *feat_a = c->feat_a;
+    if (feat_b) *feat_b = c->feat_b;
+    if (albedo) *albedo = c->feat_albedo;
+    *bytes = sizeof(float4) * (size_t)c->pixels;
+    return SPT_OK;
+}
+
+int spt_denoise_params_default(spt_denoise_params* out) {
+    if (!out) return SPT_ERR_INVALID;
+    *out = kDenoiseDefaults;
+    return SPT_OK;
+}
+
+int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* params) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_denoise before spt_configure");
+    const spt_denoise_params p = params ? *params : kDenoiseDefaults;
+    if (const char* msg = denoise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
+    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, "spt_denoise needs the whole image (shard_count 1)");
+    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+    // (the straight form's grid has a block row per 4 image rows)
+    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise: image taller than 262140 rows");
+    const int rc = ensure_features(c);
+    if (rc != SPT_OK || c->pixels == 0) return rc;
+    if (!c->dn[0]) {  // both, or none
+        float4 *a = nullptr, *b = nullptr;
+        if (hipMalloc(&a, sizeof(float4) * c->pixels) != hipSuccess || hipMalloc(&b, sizeof(float4) * c->pixels) != hipSuccess) {
+            free_dev(a);
+            free_dev(b);
+            (void)hipGetLastError();
+            return fail(c, SPT_ERR_HIP, "spt_denoise: allocation failed");
+        }
+        c->dn[0] = a;
+        c->dn[1] = b;
+    }
+    c->dn_result = -1;
+    const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
+    for (uint32_t l = 0; l < p.levels; ++l) {
+        const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
+        const float4* in = l == 0 ? c->accum : c->dn[(l - 1u) & 1u];
+        launch_atrous(forced >= 0 ? forced : atrous_form_of_step(lv.step), in, l == 0 ? (float)frame_count : 0.0f,
+                      c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, c->stream);
+        SPT_HIP(c, hipGetLastError());
+    }
+    c->dn_result = (int)((p.levels - 1u) & 1u);
+    return SPT_OK;
+}
+
+int spt_set_denoise_form(spt_ctx* c, int form) {
+    if (!c) return SPT_ERR_INVALID;
+    if (form != -1 && form != kAtrousStraight && form != kAtrousTiled)
+        return fail(c, SPT_ERR_INVALID, "spt_set_denoise_form: -1 (automatic), 0 (straight) or 1 (tiled)");
+    c->dn_form = form;
+    return SPT_OK;
+}
+
+int spt_read_denoised(spt_ctx* c, float* host_rgba) {
+    if (!c || !host_rgba) return SPT_ERR_INVALID;
+    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->dn[c->dn_result], sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return SPT_OK;
+}
+
+int spt_denoised_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
+    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
+    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
+    *dptr = c->dn[c->dn_result];
+    *bytes = sizeof(float4) * (size_t)c->pixels;
+    return SPT_OK;
+}
+
+int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
+    if (!c || !host_out) return SPT_ERR_INVALID;
+    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    const float4* img = c->dn[c->dn_result];
+    if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
+        // the registered buffer: the kernel's stores go straight to host memory over PCIe
+        launch_resolve(img, c->pixels, 1.0f, exposure, (uint32_t*)c->out_dev, c->stream);
+        SPT_HIP(c, hipGetLastError());
+    } else {
+        launch_resolve(img, c->pixels, 1.0f, exposure, c->resolved, c->stream);
+        SPT_HIP(c, hipGetLastError());
+        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, c->stream));
+    }
+    SPT_HIP(c, wait_frame(c));
+    return SPT_OK;
+}
+
+int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
+                    const spt_denoise_params* params, float* out) {
+    if (!rgba || !feat_a || !feat_b || !out || width == 0 || height == 0) return SPT_ERR_INVALID;
+    if ((uint64_t)width * height >= (1ull << 31)) return SPT_ERR_INVALID;
+    const spt_denoise_params p = params ? *params : kDenoiseDefaults;
+    if (denoise_params_error(p)) return SPT_ERR_INVALID;
+    const size_t n = (size_t)width * height;
+    const int w = (int)width, h = (int)height;
+    auto px = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
+    std::vector<float> buf[2] = {std::vector<float>(4 * n), std::vector<float>(4 * n)};
+    const float* in = rgba;
+    for (uint32_t l = 0; l < p.levels; ++l) {
+        const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
+        float* dst = buf[l & 1u].data();
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t at = (size_t)y * width + (size_t)x;
+                const float4 cp = px(in, at);
+                const float4 o = atrous_pixel(atrous_tap(cp, px(feat_a, at), px(feat_b, at)), cp.w, x, y, w, h, lv,
+                                              [&](int, int, int qx, int qy) {
+                                                  const size_t q = (size_t)qy * width + (size_t)qx;
+                                                  return atrous_tap(px(in, q), px(feat_a, q), px(feat_b, q));
+                                              });
+                dst[4 * at + 0] = o.x;
+                dst[4 * at + 1] = o.y;
+                dst[4 * at + 2] = o.z;
+                dst[4 * at + 3] = o.w;
+            }
+        in = dst;
+    }
+    std::memcpy(out, in, sizeof(float) * 4 * n);
     return SPT_OK;
 }
 

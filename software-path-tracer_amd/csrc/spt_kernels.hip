@@ -2763,6 +2763,64 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(const float4* __restri
     out[i] = g[((size_t)r * rows_max + lr) * width + x];
 }
 
+#ifndef __HIPCC_RTC__  // (not part of the run-time compiles)
+// ---------------------------------------------------------------------------------------------
+// First-hit features (spt_render_features, spt_denoise.h): one camera ray per shard pixel — the
+// reference pinhole, the posed camera through the pixel's corner, or through its centre for a jittered
+// one; no RNG draw — and its closest hit, k_extend<kBvh, true>'s, written as position and material,
+// shading normal (shade_hit's) and distance, albedo and primitive. Here because it calls the
+// intersectors; the filter that reads the images is spt_denoise.hip.
+// ---------------------------------------------------------------------------------------------
+template <bool kBvh>
+__global__ __launch_bounds__(kBlock) void k_features(const float4* __restrict__ prims, const float4* __restrict__ mats,
+                                                     const float4* __restrict__ nodes, uint32_t n_prims,
+                                                     const uint32_t* __restrict__ mat_map, CameraParams cam,
+                                                     float4* __restrict__ feat_a, float4* __restrict__ feat_b,
+                                                     float4* __restrict__ albedo) {
+    const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= cam.shard_pixels) return;
+    const uint32_t lrow = pix / cam.width;
+    const uint32_t x = pix - lrow * cam.width;
+    const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
+    F3 o{0.0f, 0.0f, 0.0f}, d;
+    if (cam.pose == nullptr) {
+        d = primary_dir(x, y, cam.inv_w, cam.inv_h, cam.aspect);
+    } else {
+        const CameraRecord r = camera_record(cam);
+        const float j = r.mode == kCamJitter ? 0.5f : 0.0f;
+        o = r.pose.o;
+        d = camera_ray_dir(r.pose, x, y, j, j, cam.inv_w, cam.inv_h, cam.aspect);
+    }
+    float t = kInf;
+    uint32_t k = kMiss;
+    if (kBvh) closest_tree(nodes, prims, o, d, t, k);
+    else closest_flat(prims, n_prims, o, d, t, k);
+    if (k == kMiss) {
+        feat_a[pix] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss));
+        feat_b[pix] = make_float4(0.0f, 0.0f, 0.0f, kInf);
+        albedo[pix] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss));
+        return;
+    }
+    const float4 pa = prims[4 * k + 0], pb = prims[4 * k + 1], pd = prims[4 * k + 3];
+    const F3 hit{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
+    const uint32_t type = meta_type(pd);
+    F3 ng;
+    if (type == 0u) {
+        ng = F3{hit.x - pa.x, hit.y - pa.y, hit.z - pa.z};  // a sphere's outward normal, never flipped
+    } else {
+        const float4 nv = type == 1u ? pb : pd;
+        ng = F3{nv.x, nv.y, nv.z};
+        if (dot3(ng, d) > 0.0f) ng = F3{-ng.x, -ng.y, -ng.z};  // two-sided: faces the ray
+    }
+    const float inv_len = inv_sqrt_ref(ng.x * ng.x + ng.y * ng.y + ng.z * ng.z);
+    const uint32_t m = meta_material(pd);
+    const float4 alb = mats[2 * m + 0];
+    feat_a[pix] = make_float4(hit.x, hit.y, hit.z, __uint_as_float(mat_map[m]));
+    feat_b[pix] = make_float4(ng.x * inv_len, ng.y * inv_len, ng.z * inv_len, t);
+    albedo[pix] = make_float4(alb.x, alb.y, alb.z, pb.w);  // pb.w: the index in the caller's array
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // host launchers
 #ifndef __HIPCC_RTC__
@@ -2770,6 +2828,7 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(const float4* __restri
 #include <cassert>
 #include <type_traits>
 
+#include "spt_denoise.h"
 #include "spt_launch_plan.h"
 namespace spt {
 // ---------------------------------------------------------------------------------------------
@@ -3101,6 +3160,16 @@ void launch_assemble_rows(const float4* gathered, float4* out, uint32_t width, u
     const uint32_t n = width * height;
     if (n == 0) return;
     k_assemble_rows<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>(gathered, out, width, height, world, rows_max);
+}
+
+void launch_features(const PassParams& p, const uint32_t* mat_map, float4* feat_a, float4* feat_b, float4* albedo,
+                     hipStream_t s) {
+    const uint32_t n = p.shard_pixels;
+    if (n == 0) return;
+    const CameraParams cam = camera_params(p);
+    const uint32_t nb = (n + kBlock - 1) / kBlock;
+    if (p.nodes != nullptr) k_features<true><<<nb, kBlock, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, mat_map, cam, feat_a, feat_b, albedo);
+    else k_features<false><<<nb, kBlock, 0, s>>>(p.prims, p.mats, p.nodes, p.n_prims, mat_map, cam, feat_a, feat_b, albedo);
 }
 
 #endif  // __HIPCC_RTC__
