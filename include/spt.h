@@ -179,6 +179,10 @@ typedef struct spt_stats {
     uint64_t stalled_waves;                   /* k_paths waves that stopped at their step loop's safety
                                                  bound (a logic error; spt_get_stats then fails with
                                                  SPT_ERR_HIP after filling *out)                   */
+    uint64_t view_cached;                     /* 1: the last k_paths launch ran over the view's cached
+                                                 bounce 0 (spt_tuning.view_cache; same results)    */
+    uint64_t view_live_pixels;                /* live pixels of the cached view (a camera hit whose
+                                                 path goes on); 0 while no view is cached          */
 } spt_stats;
 
 typedef struct spt_ctx spt_ctx;
@@ -513,6 +517,11 @@ typedef struct spt_tuning {
                                   background thread started by spt_set_scene, the generic kernels run
                                   until it is ready (a render call never waits on the compiler);
                                   1: compiled inside the first launch that needs it; -1: never          */
+    int32_t view_cache;        /* flat scenes, k_paths: every pixel's bounce 0 kept across the launches of a
+                                  view (scene, camera, sky, size, shard and configuration unchanged) in
+                                  compacted lists the launches then run over. 0: automatic, built behind
+                                  the first persistent call after a change; -1: never (every launch
+                                  computes bounce 0 itself)                                              */
 } spt_tuning;
 /* Applies to later calls; subqueues re-sizes at the next spt_configure. */
 int spt_set_tuning(spt_ctx* ctx, const spt_tuning* tuning);

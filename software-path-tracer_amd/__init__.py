@@ -143,6 +143,8 @@ class SptStats(ctypes.Structure):
         ("stack_bytes", ctypes.c_uint64),
         ("stack_need", ctypes.c_uint64),
         ("stalled_waves", ctypes.c_uint64),
+        ("view_cached", ctypes.c_uint64),
+        ("view_live_pixels", ctypes.c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -186,6 +188,7 @@ class SptTuning(ctypes.Structure):
         ("bvh_max_leaf", ctypes.c_uint32),
         ("bvh_bins", ctypes.c_uint32),
         ("specialize", ctypes.c_int32),
+        ("view_cache", ctypes.c_int32),
     ]
 
     def __init__(self, **kw):

@@ -118,7 +118,19 @@ struct spt_ctx {
     uint16_t* chunk_cost = nullptr;   // flat k_paths' first-tier chunk costs and order (PassParams)
     uint32_t* chunk_order = nullptr;
     uint64_t chunk_order_key = 0;     // 0: no order (cleared with the hit cache by a scene or size change)
-    bool frame_lists = false;      // ... and k_frame takes the compacted lists (hit_mode 3)
+    // Flat k_paths' view lists (spt_kernels.h ViewPlan): every pixel's bounce 0, compacted into live-pixel
+    // records and constant pixels. Built behind the first persistent launch after anything that changes a
+    // pixel's bounce 0 (wherever hit_cache_valid or chunk_order_key is cleared, and a new environment map);
+    // the persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
+    float4* view_live = nullptr;      // [3 * pixels] allocated by the first build
+    float4* view_const = nullptr;     // [pixels]
+    uint32_t* view_counts = nullptr;  // [2] live, constant; then the compaction's per-block scratch
+    uint32_t view_n[2] = {0, 0};      // view_counts[0..1], read back once per build
+    bool view_valid = false;
+    bool view_no_memory = false;      // the lists' allocation failed: the pixel plan runs until the next spt_configure
+    int32_t view_cache = 0;           // spt_tuning: 0 = automatic, -1 = never (every launch computes bounce 0 itself)
+    bool last_view_cached = false;    // the last persistent launch ran over the lists
+    bool frame_lists = false;     // ... and k_frame takes the compacted lists (hit_mode 3)
     uint4* live_rec = nullptr;     // ... compacted: the live pixels' records (kFrameHitCache 2)
     uint32_t* sky_pix = nullptr;   // ... the sky pixels' indices
     uint32_t* list_counts = nullptr;  // [2] live, sky; then the compaction's per-block scratch
@@ -266,6 +278,11 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->chunk_cost);
     free_dev(c->chunk_order);
     c->chunk_order_key = 0;
+    free_dev(c->view_live);
+    free_dev(c->view_const);
+    free_dev(c->view_counts);
+    c->view_valid = false;
+    c->view_no_memory = false;
     free_dev(c->live_rec);
     free_dev(c->sky_pix);
     free_dev(c->list_counts);
@@ -344,6 +361,7 @@ void free_comm(spt_ctx* c) {
 void free_scene(spt_ctx* c) {
     c->hit_cache_valid = false;  // (the camera hits were this scene's)
     c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
+    c->view_valid = false;   // (... and the view's bounce 0)
     free_dev(c->bvh_stack);
     c->bvh_stack_stride = 0;
     free_dev(c->d_prims);
@@ -835,6 +853,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     c->hit_cache_valid = false;  // (moved primitives: k_frame traces the camera segments again)
     c->feat_valid = false;       // (... and spt_render_features the first hits)
     c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
+    c->view_valid = false;   // (... and the view's bounce 0)
     // the edits are staged and committed to the host mirror only once the device holds them, so a
     // failed call leaves the ctx's scene as it was
     std::vector<spt_prim> all = c->h_prims;
@@ -999,6 +1018,7 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
     c->feat_valid = false;
     c->dn_result = -1;  // (no denoised image of this configuration yet)
     c->chunk_order_key = 0;
+    c->view_valid = false;  // (another size, shard, flags or bounce limit: another bounce 0 per pixel)
     const size_t qn = (size_t)cap * c->n_sub;
     if ((cfg->flags & SPT_FLAG_SORTED_RAYS) && qn && !c->ray_perm) {  // the sorted schedule's buffers
         SPT_HIP(c, hipMalloc(&c->ray_keys, sizeof(uint16_t) * qn));
@@ -1025,6 +1045,33 @@ int spt_reset(spt_ctx* c) {
 int spt_get_frame_count(const spt_ctx* c, uint32_t* fc) {
     if (!c || !fc) return SPT_ERR_INVALID;
     *fc = c->frame_count;
+    return SPT_OK;
+}
+
+// Build flat k_paths' view lists behind the persistent launch just enqueued (stream order) and read the
+// two counts back: they size the next launches' plans and grids. This waits for that launch, once per
+// view — on the first persistent call after a change only, as k_frame's lists do below. A failed
+// allocation is no error: the launches keep computing bounce 0 themselves.
+static int build_view_lists(spt_ctx* c, const PassParams& p) {
+    const size_t pixels = std::max<size_t>(c->pixels, 1);
+    if (!c->view_live) {
+        const size_t blocks = (pixels + kBlock - 1) / kBlock;
+        if (hipMalloc(&c->view_live, sizeof(float4) * 3 * pixels) != hipSuccess ||
+            hipMalloc(&c->view_const, sizeof(float4) * pixels) != hipSuccess ||
+            hipMalloc(&c->view_counts, sizeof(uint32_t) * (2 + blocks)) != hipSuccess) {
+            (void)hipGetLastError();
+            free_dev(c->view_live);
+            free_dev(c->view_const);
+            free_dev(c->view_counts);
+            c->view_no_memory = true;
+            return SPT_OK;
+        }
+    }
+    launch_view_lists(p, c->view_live, c->view_const, c->view_counts, c->view_counts + 2, c->stream);
+    SPT_HIP(c, hipGetLastError());
+    SPT_HIP(c, hipMemcpyAsync(c->view_n, c->view_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    c->view_valid = true;
     return SPT_OK;
 }
 
@@ -1055,7 +1102,12 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             p.chunk_cost = c->chunk_cost;
             p.chunk_order = c->chunk_order;
             p.chunk_order_key = &c->chunk_order_key;
-            c->last_specialized = launch_paths(p, c->counters, c->stream);
+            // a flat scene's view lists, once they are built (below): the launch runs over them
+            const bool view_scene = c->view_cache >= 0 && view_lists_scene(p);
+            const ViewPlan view{c->view_live, c->view_const, c->view_n[0], c->view_n[1], 0u};
+            const bool view_on = view_scene && c->view_valid;
+            c->last_specialized = launch_paths(p, c->counters, c->stream, view_on ? &view : nullptr);
+            c->last_view_cached = view_on;
             // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) c->chunk_order_key = 0;
@@ -1064,6 +1116,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
                 return SPT_ERR_HIP;
             }
             SPT_HIP(c, le);
+            if (view_scene && !c->view_valid && !c->view_no_memory && build_view_lists(c, p) != SPT_OK) return SPT_ERR_HIP;
             done += f;
             c->passes++;
         }
@@ -1307,6 +1360,7 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
         c->env_w = width;
         c->env_h = height;
     }
+    c->view_valid = false;  // (k_paths' view lists hold the sky pixels' radiance)
     if (c->configured) return spt_reset(c);  // a different sky: the accumulation restarts
     return SPT_OK;
 }
@@ -1342,6 +1396,7 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     c->hit_cache_valid = false;
     c->frame_lists = false;
     c->chunk_order_key = 0;
+    c->view_valid = false;  // (k_paths' view lists too)
     c->feat_valid = false;  // (the first hits were the previous camera's)
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
@@ -1370,6 +1425,7 @@ int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32
     c->hit_cache_valid = false;
     c->frame_lists = false;
     c->chunk_order_key = 0;
+    c->view_valid = false;  // (k_paths' view lists: the kBsdf kernels take none)
     if (c->configured) return spt_reset(c);  // other materials: the accumulation restarts
     return SPT_OK;
 }
@@ -1680,6 +1736,7 @@ int spt_set_profiling(spt_ctx* c, int mode) {
     // k_frame's compacted camera-hit lists were chosen for the kernels of the old counters setting
     // (frame_lists_scene: the counting kernels never hold a scene in LDS): decided again
     if (counters != c->counters) c->hit_cache_valid = false;
+    if (counters != c->counters) c->view_valid = false;  // (k_paths' view lists with them)
     c->counters = counters;
     return SPT_OK;
 }
@@ -1730,6 +1787,8 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     out->stack_bytes = c->stack_bytes;
     out->stack_need = c->bvh_stack_need;
     out->stalled_waves = tot[kTotStalled];
+    out->view_cached = c->last_view_cached ? 1u : 0u;
+    out->view_live_pixels = c->view_valid ? c->view_n[0] : 0u;
     if (tot[kTotStalled])
         return fail(c, SPT_ERR_HIP, "k_paths: " + std::to_string(tot[kTotStalled]) +
                                         " wave(s) stopped at the step bound with frames unaccumulated (a bug)");
@@ -1798,7 +1857,7 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     if (t->px_shift && (t->px_shift < 2 || t->px_shift > 5)) return fail(c, SPT_ERR_INVALID, "spt_tuning: px_shift 2..5");
     if (t->chunks_per_wave > 1024 || t->subqueues > 65536 || t->tail_bounce > kMaxBounces ||
         t->bvh_max_leaf > kBvhMaxLeaf || (t->bvh_bins && (t->bvh_bins < 2 || t->bvh_bins > 64)) ||
-        t->specialize < -1 || t->specialize > 1)
+        t->specialize < -1 || t->specialize > 1 || t->view_cache < -1 || t->view_cache > 0)
         return fail(c, SPT_ERR_INVALID, "spt_tuning: value out of range");
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1825,6 +1884,7 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     c->bvh_max_leaf = t->bvh_max_leaf;
     c->bvh_bins = t->bvh_bins;
     c->specialize = t->specialize;
+    c->view_cache = t->view_cache;
     return SPT_OK;
 }
 

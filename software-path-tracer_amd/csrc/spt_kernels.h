@@ -270,6 +270,24 @@ struct ChunkPlan {
     uint16_t* cost;
 };
 
+// Flat k_paths over a view's compacted lists (the kernels that keep a per-pixel bounce 0: not kJitter,
+// not kBsdf): bounce 0 of every pixel is the same in every launch of a view — scene, camera, size, shard
+// and configuration unchanged — so it is computed once (launch_view_lists) and the launches that follow
+// read it. `live`: 3 float4s per live pixel, PrimaryState r0, r1, r2 with the shard pixel index in r2.w
+// (unused by the step loop); `constant`: (Lc.xyz, shard pixel index bits) per constant pixel; both in
+// shard-pixel order. The ChunkPlan's tiers are then laid over the live list (every pixel of a chunk is
+// live), and n_sweep *sweep units* of kViewSweep constant pixels, one per lane, are queued behind the
+// first tier: chunk indices [plan.n[0], plan.n[0] + n_sweep). Passed as k_paths' LAST argument, so the
+// kernels that never read it keep their argument offsets and their machine code. live == nullptr: the
+// pixel plan, every chunk computes its pixels' bounce 0 itself.
+constexpr uint32_t kViewSweep = 64;
+struct ViewPlan {
+    const float4* live;
+    const float4* constant;
+    uint32_t n_live, n_const;
+    uint32_t n_sweep;
+};
+
 constexpr uint32_t kFrameRun = 128;          // k_frame: pixels per work unit, flat scenes
 constexpr uint32_t kFrameRunBvh = 64;        // ... BVH scenes
 constexpr uint32_t kFrameLdsStackMax = 16;   // k_frame kSmall: LDS stack entries per lane at most (8 B each)
@@ -298,7 +316,16 @@ void launch_accumulate(const PassParams& p, hipStream_t s);
 // flat scenes, persistent schedule: every frame of the call in one launch, accumulated in frame
 // order in registers (no queues, no radiance buffer); `stats` tallies segments per bounce
 // (true: the flat scene's specialized kernel ran, spt_jit.hip; false: the generic one)
-bool launch_paths(const PassParams& p, bool stats, hipStream_t s);
+// view: the view's compacted lists (n_sweep is set by the launch), or nullptr: the pixel plan
+bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view = nullptr);
+// the scenes and configurations whose k_paths keeps a per-pixel bounce 0 that a view's lists can hold
+inline bool view_lists_scene(const PassParams& p) {
+    return p.nodes == nullptr && p.n_prims != 0u && p.cam_mode != kCamJitter && p.bsdf == 0u;
+}
+// Build a view's lists on `s` (stream order): live / constant as in ViewPlan (room for shard_pixels
+// records each), counts[0] = live pixels, counts[1] = constant pixels, block_scratch: shard pixels / 256 words
+void launch_view_lists(const PassParams& p, float4* live, float4* constant, uint32_t* counts, uint32_t* block_scratch,
+                       hipStream_t s);
 bool launch_frame(const PassParams& p, bool stats, hipStream_t s);
 // k_frame holds this BVH scene whole in LDS (its kSmall form)
 inline bool frame_small_scene(const PassParams& p, bool stats) {

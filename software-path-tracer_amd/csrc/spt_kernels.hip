@@ -1509,9 +1509,11 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                                   unsigned long long* __restrict__ totals,
                                                   uint32_t* __restrict__ work, uint32_t* __restrict__ work_next,
                                                   ShadeParams sp, CameraParams cam, uint32_t n_frames, ChunkPlan plan,
-                                                  NeeParams nee) {
+                                                  NeeParams nee, ViewPlan view) {
     constexpr uint32_t kWaves = kBlock / 64u;
     constexpr bool kStart0 = kJitter || kBsdf;  // every path starts at bounce 0: no per-pixel primary state
+    // the instantiations that can run over a view's compacted lists (ViewPlan); the others never read `view`
+    constexpr bool kView = !kBvh && !kStart0;
     bake_config<kShape>(sp);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
@@ -1556,7 +1558,12 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     // waves' last chunks — the launch's tail — are short.
     uint32_t lane_slots = 0, lane_busy = 0;  // statistics: lane utilization of the tracing steps
     BvhCounters bvh_ctr;                     // statistics: BVH work of this lane's traced segments
-    const uint32_t n_chunks = plan.n[0] + plan.n[1] + plan.n[2];
+    uint32_t n_chunks = plan.n[0] + plan.n[1] + plan.n[2];
+    bool view_on = false;  // (wave-uniform) the launch runs over a view's compacted lists
+    if constexpr (kView) {
+        view_on = view.live != nullptr;
+        if (view_on) n_chunks += view.n_sweep;
+    }
     const uint32_t xcc = xcc_id();
     uint32_t heads_empty = 0;
     // The first tier is handed out longest first (ChunkPlan::order). A chunk's cost is its live pixels'
@@ -1574,12 +1581,37 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     uint32_t tl_chunks = 0, tl_pxs = 0, tl_live = 0;
 #endif
     for (;;) {
-        const uint32_t chunk = pull_unit(work, n_chunks, xcc, heads_empty);
+        uint32_t chunk = pull_unit(work, n_chunks, xcc, heads_empty);
         if (chunk >= n_chunks) break;
 #ifdef SPT_TIMELINE
         tl_last = wall_clock64();
         ++tl_chunks;
 #endif
+        if constexpr (kView) {
+            if (view_on && chunk >= plan.n[0]) {
+                const uint32_t unit = chunk - plan.n[0];
+                if (unit < view.n_sweep) {
+                    // a sweep unit: kViewSweep constant pixels of the view, one per lane; every frame adds
+                    // (Lc, 1) in frame order — the additions of a constant pixel in a chunk of the pixel plan
+                    const uint32_t i0 = unit * kViewSweep;
+                    if (kStats && lane == 0u) atomicAdd(&s_seg[0], n_frames * min(kViewSweep, view.n_const - i0));
+                    if (i0 + lane < view.n_const) {
+                        const float4 c = view.constant[i0 + lane];
+                        const uint32_t pix = __float_as_uint(c.w);
+                        float4 a = accum[pix];
+                        for (uint32_t f = 0; f < n_frames; ++f) a = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w);
+                        a.w = add_count(a.w, n_frames);
+                        accum[pix] = a;
+                    }
+#ifdef SPT_TIMELINE
+                    tl_pxs = 6u;  // (the timeline's last-chunk record: 64 pixels, none live)
+                    tl_live = 0u;
+#endif
+                    continue;
+                }
+                chunk -= view.n_sweep;  // the small tiers follow the sweep units
+            }
+        }
         uint32_t pxs, pix0;
         if (chunk < plan.n[0]) {
             pxs = plan.shift[0];
@@ -1592,7 +1624,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             pix0 = plan.start[2] + ((chunk - plan.n[0] - plan.n[1]) << pxs);
         }
         const uint32_t px = 1u << pxs;  // pixels of this chunk (1 to 32)
-        const uint32_t npx = min(px, cam.shard_pixels - pix0);
+        // (a view's tiers are laid over its live list: pix0 is then a live-list index)
+        const uint32_t npx = min(px, ((kView && view_on) ? view.n_live : cam.shard_pixels) - pix0);
         // Bounce 0 of every pixel, once per chunk. A pixel whose camera ray ends its path without an
         // RNG draw — a miss (the sky), or any hit when max_bounces <= 1 — is a *constant* pixel: every
         // frame's path of it returns the same radiance Lc, so it gets no path slots at all (C2: 61 %
@@ -1613,28 +1646,49 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         const bool ch_on = chmode && c0 < 4u && cp < npx;
         // pixel lanes: pixel `lane`'s accumulator; channel lanes: .x = channel c0, .y = channel c0 + 1
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        bool live_px = false;
+        PrimaryState ps;
+        uint32_t apix = pix0 + (chmode ? cp : lane);  // the shard pixel whose accumulator this lane holds
+        if constexpr (kView) {
+            // A view's live chunk: pixel lane j's bounce 0 is record pix0 + j of the live list, every pixel
+            // of the chunk is live, and the accumulators are those of the records' pixels (r2.w, which goes
+            // to s_px with the record: the stores after the step loop read it there, so no register holds
+            // it across the loop). The rest of the chunk runs as in the pixel plan.
+            if (view_on) {
+                uint32_t vpix = 0;
+                if (lane < npx) {
+                    const float4* rec = view.live + 3u * (size_t)(pix0 + lane);
+                    ps.r0 = rec[0];
+                    ps.r1 = rec[1];
+                    ps.r2 = rec[2];
+                    vpix = __float_as_uint(ps.r2.w);
+                    live_px = true;
+                }
+                apix = chmode ? (uint32_t)__shfl((int)vpix, (int)cp, 64) : vpix;
+            }
+        }
         if (ch_on) {
-            const float* af = reinterpret_cast<const float*>(accum) + 4u * (size_t)(pix0 + cp) + c0;
+            const float* af = reinterpret_cast<const float*>(accum) + 4u * (size_t)apix + c0;
             acc.x = af[0];
             if (pxs == kMaxChunkShift) acc.y = af[1];
         }
-        bool live_px = false;
-        PrimaryState ps;
         if (lane < npx) {
-            const uint32_t pix = pix0 + lane;
-            if (!chmode) acc = accum[pix];
-            const uint32_t lrow = pix / cam.width;
-            const uint32_t x = pix - lrow * cam.width;
-            const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
-            if constexpr (kStart0) {  // the pixel's state is its coordinates and seed: r0 = (x, y, 0, seed)
-                ps.r0 = make_float4(__uint_as_float(x), __uint_as_float(y), 0.f, __uint_as_float(x + y * cam.width));
-                ps.r1 = ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
-                live_px = true;
-            } else {
-                const CameraRay cr = camera_ray_xy<kShape>(cam, x, y, x + y * cam.width);
-                // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
-                ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
-                live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
+            if (!chmode) acc = accum[apix];
+            if (!(kView && view_on)) {  // (one block with the load above: the kernels without a view keep their code)
+                const uint32_t pix = pix0 + lane;
+                const uint32_t lrow = pix / cam.width;
+                const uint32_t x = pix - lrow * cam.width;
+                const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
+                if constexpr (kStart0) {  // the pixel's state is its coordinates and seed: r0 = (x, y, 0, seed)
+                    ps.r0 = make_float4(__uint_as_float(x), __uint_as_float(y), 0.f, __uint_as_float(x + y * cam.width));
+                    ps.r1 = ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    live_px = true;
+                } else {
+                    const CameraRay cr = camera_ray_xy<kShape>(cam, x, y, x + y * cam.width);
+                    // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
+                    ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
+                    live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
+                }
             }
         }
         // constant pixel's Lc: the sky radiance of a miss (0 + 1 * sky, or 0 without a sky), or after a hit
@@ -2173,11 +2227,19 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             plan.cost[chunk] = (uint16_t)min(65535u, (kBvh && kNee) ? ((steps_init - steps_left) * 4u + titer) >> 2
                                                                     : steps_init - steps_left);
         if (ch_on) {
-            float* af = reinterpret_cast<float*>(accum) + 4u * (size_t)(pix0 + cp) + c0;
+            uint32_t ap = pix0 + cp;
+            if constexpr (kView) {
+                if (view_on) ap = __float_as_uint(s_px[wave][2][cp].w);  // (a view: the record's pixel)
+            }
+            float* af = reinterpret_cast<float*>(accum) + 4u * (size_t)ap + c0;
             af[0] = acc.x;
             if (pxs == kMaxChunkShift) af[1] = acc.y;
         } else if (!chmode && lane < npx) {
-            accum[pix0 + lane] = acc;
+            uint32_t ap = pix0 + lane;
+            if constexpr (kView) {
+                if (view_on) ap = __float_as_uint(s_px[wave][2][lane].w);
+            }
+            accum[ap] = acc;
         }
     }
 #ifdef SPT_TIMELINE
@@ -2819,6 +2881,61 @@ __global__ __launch_bounds__(kBlock) void k_features(const float4* __restrict__ 
     feat_b[pix] = make_float4(ng.x * inv_len, ng.y * inv_len, ng.z * inv_len, t);
     albedo[pix] = make_float4(alb.x, alb.y, alb.z, pb.w);  // pb.w: the index in the caller's array
 }
+
+// ---------------------------------------------------------------------------------------------
+// A view's lists for flat k_paths (ViewPlan), once per view: bounce 0 of every shard pixel with the
+// device functions, the live / constant rule and the Lc expressions of k_paths' chunk prologue, in their
+// generic forms (kShape 0, kEnv 2: compiled offline, no run-time compile of its own). A shape-specialized
+// k_paths that then runs over the lists replaced a prologue of the <kShape, kEnv> forms, so the bits are
+// the same by the project's rule that the generic and the specialized kernels agree bit for bit (§3.1c;
+// tests/test_gpu_view_cache.py renders both), not by identical code. Compacted in shard-pixel order with k_frame's
+// pattern — blocks of 256 pixels count their live pixels (kScatter false), k_hit_scan scans the counts,
+// and each block computes its pixels again and scatters the records at the scanned offsets.
+// ---------------------------------------------------------------------------------------------
+template <bool kScatter>
+__global__ __launch_bounds__(kBlock) void k_view_lists(const float4* __restrict__ prims, const float4* __restrict__ mats,
+                                                       uint32_t n_prims, ShadeParams sp, CameraParams cam,
+                                                       uint32_t* __restrict__ block_live, float4* __restrict__ live,
+                                                       float4* __restrict__ constant) {
+    __shared__ uint32_t s_c[kBlock / 64u];
+    const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+    const bool in = pix < cam.shard_pixels;
+    bool live_px = false;
+    PrimaryState ps;
+    F3 lc{0.f, 0.f, 0.f};
+    if (in) {
+        const uint32_t lrow = pix / cam.width;
+        const uint32_t x = pix - lrow * cam.width;
+        const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
+        const CameraRay cr = camera_ray_xy<0>(cam, x, y, x + y * cam.width);
+        ps = primary_state<false, 2, 0>(prims, nullptr, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, StkP{nullptr});
+        const bool hit = (__float_as_uint(ps.r1.w) & kHitBit) != 0u;
+        live_px = hit && 1u < sp.max_bounces;
+        lc = (!live_px && hit) ? F3{ps.r4.x, ps.r4.y, ps.r4.z} : F3{ps.r1.x, ps.r1.y, ps.r1.z};
+    }
+    const unsigned long long b = __ballot(live_px);
+    const uint32_t w = threadIdx.x / 64u;
+    if (__lane_id() == 0u) s_c[w] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (!kScatter) {
+        if (threadIdx.x == 0u) {
+            uint32_t c = 0;
+            for (uint32_t k = 0; k < kBlock / 64u; ++k) c += s_c[k];
+            block_live[blockIdx.x] = c;
+        }
+        return;
+    }
+    uint32_t before = block_live[blockIdx.x];  // live pixels before this block (scanned)
+    for (uint32_t k = 0; k < w; ++k) before += s_c[k];
+    before += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    if (live_px) {
+        live[3u * (size_t)before + 0u] = ps.r0;
+        live[3u * (size_t)before + 1u] = ps.r1;
+        live[3u * (size_t)before + 2u] = make_float4(ps.r2.x, ps.r2.y, ps.r2.z, __uint_as_float(pix));
+    } else if (in) {
+        constant[pix - before] = make_float4(lc.x, lc.y, lc.z, __uint_as_float(pix));
+    }
+}
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -3063,7 +3180,7 @@ bool launch_persistent(hipFunction_t fn, const void* kernel, uint32_t grid, size
 }
 }  // namespace
 
-bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
+bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view_lists) {
     ShadeParams sp = shade_params(p, 0u);
     CameraParams cam = camera_params(p);
     const bool bvh = p.nodes != nullptr;
@@ -3075,7 +3192,19 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
     PathsVariant v = paths_variant(p, stats, kMaxChunkShift);
     hipFunction_t fn = jit_kernel(jit_kind(v, p.jit_shape), p);
     const int per_cu = blocks_per_cu(fn, paths_kernel(v), lds_scene);
-    ChunkPlan plan = make_chunk_plan(p.shard_pixels, resident_waves(per_cu, p.cu_count), p.chunks_per_wave, p.px_shift);
+    // A view's lists (flat scenes, ViewPlan): the plan over the live list and the sweep units. Its first
+    // tier has the pixel plan's chunk size, so the kernel chosen below is the pixel plan's too.
+    ViewPlan view{};
+    if (view_lists && view_lists->live && view_lists_scene(p)) view = *view_lists;
+    ChunkPlan plan;
+    if (view.live) {
+        const ViewChunkPlan vp = make_view_plan(p.shard_pixels, view.n_live, view.n_const, resident_waves(per_cu, p.cu_count),
+                                                p.chunks_per_wave, p.px_shift);
+        plan = vp.plan;
+        view.n_sweep = vp.n_sweep;
+    } else {
+        plan = make_chunk_plan(p.shard_pixels, resident_waves(per_cu, p.cu_count), p.chunks_per_wave, p.px_shift);
+    }
     // A launch records each first-tier chunk's cost, k_chunk_order sorts them behind it (stream order),
     // and the launches of the same plan that follow hand the first tier out longest first (C2 +4 %, with
     // NEE +3 %, the simulated N = 8 shard +5 %: profiles/r05_n_ab_chunk_order.txt; BVH scenes since
@@ -3083,7 +3212,7 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
     // The key names the plan; a scene or configuration change clears it (spt_capi.hip). The order
     // changes which wave traces a chunk, never a result.
     bool record = false;
-    const uint64_t order_key = chunk_order_key(plan, p.shard_pixels);
+    const uint64_t order_key = view.live ? view_order_key(plan, view.n_live) : chunk_order_key(plan, p.shard_pixels);
     if (!p.px_shift && p.chunk_cost && p.chunk_order && plan.n[0] > 1u) {
         if (*p.chunk_order_key == order_key) {
             plan.order = p.chunk_order;
@@ -3094,9 +3223,9 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s) {
     }
     v = paths_variant(p, stats, plan.shift[0]);
     if (v.chan) fn = jit_kernel(jit_kind(v, p.jit_shape), p);
-    const uint32_t grid = paths_grid(plan, bvh, per_cu, p.cu_count);
+    const uint32_t grid = paths_grid(plan, bvh, per_cu, p.cu_count, view.n_sweep);
     void* args[] = {(void*)&p.prims, (void*)&p.mats, (void*)&p.nodes, (void*)&p.n_prims, (void*)&p.accum, (void*)&p.totals,
-                    (void*)&p.work, (void*)&p.work_next, &sp, &cam, (void*)&p.n_frames, &plan, (void*)&p.nee};
+                    (void*)&p.work, (void*)&p.work_next, &sp, &cam, (void*)&p.n_frames, &plan, (void*)&p.nee, &view};
     const bool specialized = launch_persistent(fn, paths_kernel(v), grid, lds_scene, args, s);
     if (record) {
         k_chunk_order<<<1, 128, 0, s>>>(p.chunk_cost, plan.n[0], p.chunk_order);
@@ -3141,6 +3270,17 @@ void launch_hit_lists(const PassParams& p, uint32_t* block_scratch, hipStream_t 
     k_hit_scan<<<1, 1024, 0, s>>>(block_scratch, nb, n, const_cast<uint32_t*>(p.list_counts));
     k_hit_scatter<<<nb, kBlock, 0, s>>>(p.hit_cache, n, block_scratch, const_cast<uint4*>(p.live_rec),
                                         const_cast<uint32_t*>(p.sky_pix));
+}
+
+void launch_view_lists(const PassParams& p, float4* live, float4* constant, uint32_t* counts, uint32_t* block_scratch,
+                       hipStream_t s) {
+    const uint32_t n = p.shard_pixels, nb = (n + kBlock - 1u) / kBlock;
+    if (n == 0u) return;
+    const ShadeParams sp = shade_params(p, 0u);
+    const CameraParams cam = camera_params(p);
+    k_view_lists<false><<<nb, kBlock, 0, s>>>(p.prims, p.mats, p.n_prims, sp, cam, block_scratch, live, constant);
+    k_hit_scan<<<1, 1024, 0, s>>>(block_scratch, nb, n, counts);
+    k_view_lists<true><<<nb, kBlock, 0, s>>>(p.prims, p.mats, p.n_prims, sp, cam, block_scratch, live, constant);
 }
 
 void launch_resolve(const float4* accum, uint32_t n, float frames, float exposure, uint32_t* out, hipStream_t s) {

@@ -132,13 +132,65 @@ inline uint64_t chunk_order_key(const ChunkPlan& plan, uint32_t P) {
     return ((uint64_t)plan.n[0] << 37) | ((uint64_t)P << 5) | plan.shift[0];
 }
 
+
+// k_paths over a view's compacted lists (ViewPlan; flat scenes): the tiers laid over the `live` records
+// of the live list, and ceil(constant / kViewSweep) sweep units for the constant list, queued behind the
+// first tier (where the pixel plan hands out its zero-cost chunks).
+// The first tier's chunk size is the pixel plan's, from shard_pixels: the rule counts chunks per resident
+// wave of the whole image, and computed from the live count it falls to 8 pixels on Cornell 1080p
+// (805,896 live of 2,073,600), which measured -19 %. Each small tier gets the pixel plan's chunks per
+// wave scaled by the live fraction, so a wave's last chunks stay as many as they were per traced pixel
+// (the pixel plan's tail tiers cover the image's last pixels whatever they hold: on Cornell 1080p its
+// 8-pixel tier holds no live pixel at all).
+// (measurement builds: -DSPT_VIEW_TIER8=0 leaves the smallest tier to the remainder, the one A/B of the
+// view plan's tiers, profiles/view_cache_rates.txt)
+#ifndef SPT_VIEW_TIER8
+#define SPT_VIEW_TIER8 1
+#endif
+constexpr bool kViewTier8 = SPT_VIEW_TIER8 != 0;
+struct ViewChunkPlan {
+    ChunkPlan plan;
+    uint32_t n_sweep;
+};
+inline ViewChunkPlan make_view_plan(uint32_t shard_pixels, uint32_t live, uint32_t constant, uint32_t resident_waves,
+                                    uint32_t chunks_per_wave, uint32_t px_shift) {
+    ViewChunkPlan vp{};
+    ChunkPlan& plan = vp.plan;
+    vp.n_sweep = (constant + kViewSweep - 1u) / kViewSweep;
+    const ChunkPlan pixel_plan = make_chunk_plan(shard_pixels, resident_waves, chunks_per_wave, px_shift);
+    const uint32_t s0 = pixel_plan.shift[0], s1 = pixel_plan.shift[1], s2 = pixel_plan.shift[2];
+    plan.shift[0] = s0;
+    plan.shift[1] = s1;
+    plan.shift[2] = s2;
+    if (px_shift || s0 == kMinChunkShift) {
+        plan.n[0] = (uint32_t)(((uint64_t)live + (1u << s0) - 1u) >> s0);
+        return vp;
+    }
+    // chunks per small tier
+    const uint64_t tail = shard_pixels ? (uint64_t)chunks_per_wave * resident_waves * live / shard_pixels : 0u;
+    const uint32_t c_px = kViewTier8 ? (uint32_t)std::min<uint64_t>(live, tail << s2) : 0u;
+    const uint32_t b_px = (uint32_t)std::min<uint64_t>(live - c_px, tail << s1) & ~((1u << s1) - 1u);
+    const uint32_t a_px = (live - c_px - b_px) & ~((1u << s0) - 1u);
+    plan.n[0] = a_px >> s0;
+    plan.n[1] = b_px >> s1;
+    plan.start[1] = a_px;
+    plan.start[2] = a_px + b_px;
+    plan.n[2] = (live - a_px - b_px + (1u << s2) - 1u) >> s2;
+    return vp;
+}
+// names the view plan a recorded first-tier order belongs to (never a pixel plan's key: the top bit)
+inline uint64_t view_order_key(const ChunkPlan& plan, uint32_t live) {
+    return chunk_order_key(plan, live) | (1ull << 63);
+}
+
 constexpr uint32_t kBlockWaves = kBlock / 64u;
 // waves resident at once, from the occupancy query's blocks per CU
 inline uint32_t resident_waves(int per_cu, uint32_t cu_count) { return (uint32_t)per_cu * cu_count * kBlockWaves; }
 // k_paths: a persistent grid, as many blocks as are resident at once (the waves then pull chunks), but
-// no more waves than chunks (a BVH scene's global traversal stacks are sized for kMaxResidentWaves per CU)
-inline uint32_t paths_grid(const ChunkPlan& plan, bool bvh, int per_cu, uint32_t cu_count) {
-    const uint32_t chunks = plan.n[0] + plan.n[1] + plan.n[2];
+// no more waves than chunks (a BVH scene's global traversal stacks are sized for kMaxResidentWaves per CU);
+// sweep_units: a view plan's sweep units count as chunks
+inline uint32_t paths_grid(const ChunkPlan& plan, bool bvh, int per_cu, uint32_t cu_count, uint32_t sweep_units = 0u) {
+    const uint32_t chunks = plan.n[0] + plan.n[1] + plan.n[2] + sweep_units;
     const uint32_t needed = (chunks + kBlockWaves - 1u) / kBlockWaves;
     if (bvh) per_cu = std::min<int>(per_cu, (int)(kMaxResidentWaves / kBlockWaves));
     return std::min<uint32_t>(needed, (uint32_t)per_cu * cu_count);

@@ -1,0 +1,22 @@
+"""k_paths' plan over a view's compacted lists (spt_launch_plan.h make_view_plan), on the host: no GPU.
+
+tests/cpp/test_view_plan.cpp is compiled here with g++ (the plan header is pure host code; the HIP
+headers it includes for the vector types come from the ROCm install) and run: over a sweep of (pixels,
+live pixels, resident waves) every live and every constant index is covered exactly once, the first
+tier's chunk size is the pixel plan's, and Cornell 1080p's numbers are pinned.
+"""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_view_plan(tmp_path):
+    src = os.path.join(ROOT, "tests", "cpp", "test_view_plan.cpp")
+    exe = tmp_path / "test_view_plan"
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+                    "-I", os.path.join(ROOT, "software-path-tracer_amd", "csrc"), "-o", str(exe), src], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "view plan ok" in r.stdout
