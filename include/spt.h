@@ -183,6 +183,12 @@ typedef struct spt_stats {
                                                  bounce 0 (spt_tuning.view_cache; same results)    */
     uint64_t view_live_pixels;                /* live pixels of the cached view (a camera hit whose
                                                  path goes on); 0 while no view is cached          */
+    uint64_t flat_pairs;                      /* opposite wall pairs in the shape key of the specialized
+                                                 kernel that ran last (its closest hit tests one wall of
+                                                 each); 0 for the generic kernels                  */
+    uint64_t flat_pair_second_passes;         /* wave-level second passes of the paired wall test (some
+                                                 lane's ray starts outside the pair's slab: both walls
+                                                 tested); counted by k_paths' counting forms only  */
 } spt_stats;
 
 typedef struct spt_ctx spt_ctx;

@@ -1,7 +1,7 @@
 """Static instruction profile of one k_paths instantiation between the SPT_MARK comments of a
 -DSPT_STATIC_PROFILE build (analysis only: the markers constrain scheduling a little).
 
-    python scripts/static_profile.py [extra hipcc -D flags ...]
+    python scripts/static_profile.py [--no-pairs] [extra hipcc -D flags ...]
 
 Compiles the C2 shape-specialized flat kernel and the two BVH k_paths instantiations to assembly and
 prints, per section of the step loop, the VALU / SALU / LDS / scalar-memory / vector-memory
@@ -20,6 +20,10 @@ C2_SHAPE = 77445755138  # flat_shape_key of the Cornell box (spt_kernels.h)
 # ... with C2's launch configuration baked in (jit_config_key: 8 bounces, RR depth 2, sky, fast division)
 C2_SHAPE |= (1 << 37) | (8 << 38) | (2 << 44) | (1 << 50) | (1 << 52)
 C2_SHAPE |= 7 << 53  # every axis group of the box is walls (flat_rect_bits)
+if "--no-pairs" in sys.argv:  # the same kernel with every wall tested (the key before flat_wall_pairs)
+    sys.argv.remove("--no-pairs")
+else:
+    C2_SHAPE |= (1 | 1 << 2) << 57  # one opposite pair on x, one on y (flat_wall_pairs)
 INST = r"""#include "spt_kernels.hip"
 namespace spt {
 #define I(S, B, SH, W) template __global__ void k_paths<S, B, 0, SH, W>(const float4* __restrict__, const float4* __restrict__, \

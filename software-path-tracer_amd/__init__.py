@@ -145,6 +145,8 @@ class SptStats(ctypes.Structure):
         ("stalled_waves", ctypes.c_uint64),
         ("view_cached", ctypes.c_uint64),
         ("view_live_pixels", ctypes.c_uint64),
+        ("flat_pairs", ctypes.c_uint64),
+        ("flat_pair_second_passes", ctypes.c_uint64),
     ]
 
     def as_dict(self) -> dict:

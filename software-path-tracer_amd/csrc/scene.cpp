@@ -178,6 +178,38 @@ uint32_t flat_rect_bits(const std::vector<DevPrim>& sorted, const uint32_t ends[
     return bits;
 }
 
+uint32_t flat_wall_pairs(std::vector<DevPrim>& sorted, const uint32_t ends[kFlatKinds - 1], uint32_t rect_bits) {
+    uint32_t bits = 0;
+    for (int ax = 0; ax < 3; ++ax) {
+        if (!((rect_bits >> ax) & 1u)) continue;
+        const uint32_t b = ends[ax], e = ends[ax + 1], n = e - b;
+        if (e > sorted.size() || e < b || n < 2u) continue;
+        // the group's records by plane, lowest first (stable insertion: n < 64)
+        std::vector<uint32_t> ord;
+        for (uint32_t k = 0; k < n; ++k) {
+            uint32_t at = k;
+            while (at > 0 && sorted[b + k].a[ax] < sorted[b + ord[at - 1]].a[ax]) --at;
+            ord.insert(ord.begin() + at, k);
+        }
+        std::vector<DevPrim> out;
+        std::vector<bool> used(n, false);
+        uint32_t pairs = 0;
+        for (uint32_t i = 0, j = n - 1u; i < j && pairs < kFlatMaxPairs; ++i, --j) {
+            const DevPrim &lo = sorted[b + ord[i]], &hi = sorted[b + ord[j]];
+            if (!(lo.a[ax] < hi.a[ax])) break;  // one plane (or a NaN): nothing further in is a pair either
+            out.push_back(lo);
+            out.push_back(hi);
+            used[ord[i]] = used[ord[j]] = true;
+            ++pairs;
+        }
+        for (uint32_t k = 0; k < n; ++k)
+            if (!used[k]) out.push_back(sorted[b + k]);
+        std::copy(out.begin(), out.end(), sorted.begin() + b);
+        bits |= pairs << (2 * ax);
+    }
+    return bits;
+}
+
 void prepare_materials(const spt_material* mats, uint32_t n, std::vector<DevMaterial>& out) {
     out.assign(n, DevMaterial{});
     for (uint32_t i = 0; i < n; ++i) {

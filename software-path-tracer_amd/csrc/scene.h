@@ -82,6 +82,16 @@ void sort_flat_by_kind(const std::vector<DevPrim>& dp, std::vector<DevPrim>& sor
 // rectangle along the in-plane axes (the wall of a box: the two edge-basis products the device's short
 // form drops are exactly zero). Part of the flat shape key (spt_kernels.h flat_shape_key).
 uint32_t flat_rect_bits(const std::vector<DevPrim>& sorted, const uint32_t ends[kFlatKinds - 1]);
+// Opposite walls: in every axis group AX of the kind-major copy whose rect bit is set, the records are
+// reordered so that pairs of quads on strictly different planes come first, each as adjacent (lower
+// a[AX], higher a[AX]) records — the outermost planes first (lowest with highest, then the next two, so
+// pairs nest), at most kFlatMaxPairs — and the unpaired quads follow in their earlier order. Quads on one
+// plane are never paired. Returns the pair counts, 2 bits per axis (flat_shape_key's pair bits). The order
+// inside a group changes no result: the tie-break is the original index in b.w. A ray whose origin lies
+// between a pair's planes can only reach the wall it faces, which the specialized fast path uses
+// (spt_kernels.hip closest_flat).
+constexpr uint32_t kFlatMaxPairs = 3;
+uint32_t flat_wall_pairs(std::vector<DevPrim>& sorted, const uint32_t ends[kFlatKinds - 1], uint32_t rect_bits);
 
 // Binned-SAH BVH over the prepared primitives. Reorders `prims` into leaf order.
 // Boxes are padded outward by 1e-5 of the scene's coordinate magnitude, so the (rounded) slab test

@@ -93,6 +93,7 @@ struct spt_ctx {
     bool has_scene = false;
     uint32_t flat_ends = 0;  // PassParams::flat_ends
     uint32_t flat_rect = 0;  // flat_rect_bits of the kind-major copy (part of the shape key)
+    uint32_t flat_pairs = 0; // flat_wall_pairs of the kind-major copy (part of the shape key)
     bool fast_div = false;  // scene.cpp fast_division_ok: the flat loop's unscaled divisions apply
     uint64_t scene_bytes = 0;
     uint64_t stack_bytes = 0;  // the persistent kernels' global traversal stacks (BVH scenes)
@@ -228,6 +229,7 @@ struct spt_ctx {
     uint32_t* ray_bins = nullptr;
     uint32_t* ray_cursor = nullptr;
     bool last_specialized = false; // the last persistent / frame launch ran the specialized kernel
+    uint32_t last_pairs = 0;       // ... whose key held this many wall pairs (flat_shape_pairs)
 
     // multi-GPU (spt_comm_init / spt_gather_image)
     ncclComm_t comm = nullptr;
@@ -492,7 +494,7 @@ void next_work_set(spt_ctx* c, PassParams& p) {
 // The run-time specialized kernels' key of the ctx's flat scene: its shape and, once configured, the
 // launch configuration (spt_kernels.h jit_config_key).
 static uint64_t flat_jit_key(const spt_ctx* c) {
-    const uint64_t shape = flat_shape_key(c->flat_ends, c->n_prims, c->flat_rect);
+    const uint64_t shape = flat_shape_key(c->flat_ends, c->n_prims, c->flat_rect, c->flat_pairs);
     if (!c->configured) return shape;
     const uint32_t flags = (c->cfg.flags & ~spt::kFlagFastDiv) | (c->fast_div ? spt::kFlagFastDiv : 0u);
     return jit_config_key(shape, c->cfg.max_bounces, c->cfg.rr_depth, c->env.sky_enabled ? 1u : 0u, flags, c->has_camera);
@@ -754,13 +756,14 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
                                              " traversal stack entries (at most " + std::to_string(kBvhStackEntries) + ")");
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     free_scene(c);
-    uint32_t flat_ends = 0, flat_rect = 0;
+    uint32_t flat_ends = 0, flat_rect = 0, flat_pairs = 0;
     if (n_prims && n_prims <= kFlatSceneMax) {  // flat: the originals, then the kind-major copy
         std::vector<DevPrim> sorted;
         uint32_t ends[kFlatKinds - 1];
         sort_flat_by_kind(dp, sorted, ends);
         for (uint32_t g = 0; g + 1 < kFlatKinds; ++g) flat_ends |= ends[g] << (6 * g);
         flat_rect = flat_rect_bits(sorted, ends);
+        flat_pairs = flat_wall_pairs(sorted, ends, flat_rect);  // (reorders the axis groups: pairs first)
         dp.insert(dp.end(), sorted.begin(), sorted.end());
     }
     if (n_prims) {
@@ -803,6 +806,7 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     c->fast_div = fast_div;
     c->flat_ends = flat_ends;
     c->flat_rect = flat_rect;
+    c->flat_pairs = flat_pairs;
     c->h_prims.swap(keep_prims);
     c->h_mats.swap(keep_mats);
     c->h_dev_mat.swap(dev_mat);
@@ -1107,6 +1111,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             const ViewPlan view{c->view_live, c->view_const, c->view_n[0], c->view_n[1], 0u};
             const bool view_on = view_scene && c->view_valid;
             c->last_specialized = launch_paths(p, c->counters, c->stream, view_on ? &view : nullptr);
+            c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
             c->last_view_cached = view_on;
             // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
             const hipError_t le = hipGetLastError();
@@ -1149,6 +1154,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
                 c->fused = true;
             }
             c->last_specialized = launch_frame(p, c->counters, c->stream);
+            c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
             if (end_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
             SPT_HIP(c, hipGetLastError());
             if (!c->hit_cache_valid) c->frame_lists = false;
@@ -1789,6 +1795,8 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     out->stalled_waves = tot[kTotStalled];
     out->view_cached = c->last_view_cached ? 1u : 0u;
     out->view_live_pixels = c->view_valid ? c->view_n[0] : 0u;
+    out->flat_pairs = c->last_specialized ? c->last_pairs : 0u;
+    out->flat_pair_second_passes = tot[kTotPairSecond];
     if (tot[kTotStalled])
         return fail(c, SPT_ERR_HIP, "k_paths: " + std::to_string(tot[kTotStalled]) +
                                         " wave(s) stopped at the step bound with frames unaccumulated (a bug)");
@@ -1836,7 +1844,8 @@ int spt_compile_flat_kernels(const spt_prim* prims, uint32_t n_prims, int env_ma
     uint32_t ends[kFlatKinds - 1], flat_ends = 0;
     sort_flat_by_kind(dp, sorted, ends);
     for (uint32_t g = 0; g + 1 < kFlatKinds; ++g) flat_ends |= ends[g] << (6 * g);
-    const uint64_t key = flat_shape_key(flat_ends, n_prims, flat_rect_bits(sorted, ends));
+    const uint32_t flat_rect = flat_rect_bits(sorted, ends);
+    const uint64_t key = flat_shape_key(flat_ends, n_prims, flat_rect, flat_wall_pairs(sorted, ends, flat_rect));
     std::string out;
     const JitKindList kinds = jit_kinds_of_scene(false, env_map ? 1 : 0);  // (no emitters known here: the kinds without NEE)
     int built = 0;

@@ -480,6 +480,23 @@ __device__ __forceinline__ float isect_quad_axis_fast(float4 pa, float4 pc, floa
     return (t >= tmin && max(ua, ub) <= 0x3f800000u) ? t : kInf;
 }
 
+// isect_quad_axis_fast<AX, true> on the five record words it reads — q = a[AX], qu = a[U], qv = a[V],
+// cu = c[U], dv = d[V] — with the same operations in the same order: the same bits. For a wall whose
+// words are per-lane values (the paired test of closest_flat picks one wall of an opposite pair per lane).
+template <int AX>
+__device__ __forceinline__ float isect_rect_axis_fast(float q, float qu, float qv, float cu, float dv, F3 o, F3 d,
+                                                      RcpRef rAX, float tmin) {
+    constexpr int U = AX == 0 ? 1 : 0;
+    constexpr int V = AX == 2 ? 1 : 2;
+    const float t = div_ref(q - comp(o, AX), rAX);
+    const float hu = (comp(o, U) + t * comp(d, U)) - qu;
+    const float hv = (comp(o, V) + t * comp(d, V)) - qv;
+    const float al = hu * cu;
+    const float be = hv * dv;
+    const uint32_t ua = __float_as_uint(al + 0.0f), ub = __float_as_uint(be + 0.0f);
+    return (t >= tmin && max(ua, ub) <= 0x3f800000u) ? t : kInf;
+}
+
 // Parallelogram: a = (Q, D = n.Q), b = (n, -), c = (A, type | axis << 2), d = (B, -) (see scene.h).
 __device__ __forceinline__ float isect_quad(float4 pa, float4 pb, float4 pc, float4 pd, F3 o, F3 d,
                                             float tmin) {

@@ -9,13 +9,16 @@
 
 namespace spt {
 
-// The kernels compiled per flat scene shape: every one is <kStats = false, kBvh = false, env, shape, tail>.
-enum : int { kJitPaths, kJitFrame, kJitPathsChan, kJitPathsNee, kJitFrameNee, kJitFrameRgba, kJitFrameNeeRgba, kJitKinds };
+// The kernels compiled per flat scene shape: every one is <kStats, kBvh = false, env, shape, tail>, kStats
+// false but for the two counting k_paths of a shape with wall pairs (spt_launch_plan.h jit_kind).
+enum : int { kJitPaths, kJitFrame, kJitPathsChan, kJitPathsNee, kJitFrameNee, kJitFrameRgba, kJitFrameNeeRgba,
+             kJitPathsStats, kJitPathsNeeStats, kJitKinds };
 constexpr int kJitCallersEnv = -1;
 struct JitKindRow {
     const char* kernel;
     const char* tail;  // the template arguments after the shape
     int env;           // the kind's fixed kEnv, or kJitCallersEnv: 0 gradient sky, 1 environment map
+    bool stats;        // kStats: the counting form
 };
 constexpr JitKindRow kJitKindTable[kJitKinds] = {
     {"k_paths", "", kJitCallersEnv},
@@ -25,12 +28,14 @@ constexpr JitKindRow kJitKindTable[kJitKinds] = {
     {"k_frame", ", false, 1", 2},                    // kNee = kNeeAll
     {"k_frame", ", false, 0, true", kJitCallersEnv}, // kRgba (the fused resolve)
     {"k_frame", ", false, 1, true", 2},              // kNee = kNeeAll, kRgba
+    {"k_paths", "", kJitCallersEnv, true},           // kStats
+    {"k_paths", ", 0, false, 1", 2, true},           // kStats, kNee = kNeeAll
 };
 // the name expression hiprtc instantiates for (kind, env, shape)
 inline std::string jit_name_expr(int kind, int env, uint64_t shape) {
     const JitKindRow& k = kJitKindTable[kind];
-    return std::string("spt::") + k.kernel + "<false, false, " + std::to_string(k.env == kJitCallersEnv ? env : k.env) +
-           ", " + std::to_string((unsigned long long)shape) + "ull" + k.tail + ">";
+    return std::string("spt::") + k.kernel + (k.stats ? "<true, false, " : "<false, false, ") +
+           std::to_string(k.env == kJitCallersEnv ? env : k.env) + ", " + std::to_string((unsigned long long)shape) + "ull" + k.tail + ">";
 }
 
 // Compile the kernel for a flat scene shape (flat_shape_key) without loading it (no device needed);

@@ -16,12 +16,15 @@ constexpr uint32_t kMaxBounces = 32;
 constexpr uint32_t kFlagFastDiv = 1u << 30;  // internal ShadeParams flag: the scene passed fast_division_ok (scene.cpp)
 // statistics counters (u64): segments per bounce | radiance updates per bounce | k_paths lane slots
 // of its tracing steps | lanes that traced in them | BVH interior nodes visited | primitives tested |
-// NEE shadow rays traced | waves stopped by the step bound
+// NEE shadow rays traced | waves stopped by the step bound | second passes of the paired wall test
 constexpr uint32_t kTotShadow = 2 * kMaxBounces + 4;
 // k_paths waves that left their step loop at its safety bound with frames not yet accumulated (a logic
 // error: every path ends within max_bounces steps); always counted, reported by spt_get_stats
 constexpr uint32_t kTotStalled = 2 * kMaxBounces + 5;
-constexpr uint32_t kTotals = 2 * kMaxBounces + 6;
+// wave-level second passes of the paired wall test (closest_flat: some lane's origin outside a pair's
+// slab), counted by the counting forms of the specialized flat k_paths
+constexpr uint32_t kTotPairSecond = 2 * kMaxBounces + 6;
+constexpr uint32_t kTotals = 2 * kMaxBounces + 7;
 
 // Next-event estimation (SPT_FLAG_NEE): the emitter records (scene.h DevEmitter, spt_device.h
 // light_sample). Passed as every integrator kernel's LAST argument, so the kernels without NEE keep
@@ -151,8 +154,24 @@ constexpr uint32_t kCamJitter = 2;
 constexpr uint64_t kShapeValid = 1ull << 36;
 // (round 4) ... and 3 bits (53-55): the axis groups made of rectangles only (scene.h flat_rect_bits),
 // whose quads then take the short form without the per-quad scalar check
-__host__ __device__ constexpr uint64_t flat_shape_key(uint32_t flat_ends, uint32_t n_prims, uint32_t rect_bits = 0u) {
-    return kShapeValid | (uint64_t)(n_prims & 63u) << 30 | (flat_ends & 0x3fffffffu) | (uint64_t)(rect_bits & 7u) << 53;
+// ... and 6 bits (57-62): per axis, 2 bits, the opposite wall pairs at the head of its group (scene.h
+// flat_wall_pairs; 0-3, only in a group whose rect bit is set): the unrolled fast path tests one wall of each
+__host__ __device__ constexpr uint64_t flat_shape_key(uint32_t flat_ends, uint32_t n_prims, uint32_t rect_bits = 0u,
+                                                      uint32_t pair_bits = 0u) {
+    return kShapeValid | (uint64_t)(n_prims & 63u) << 30 | (flat_ends & 0x3fffffffu) | (uint64_t)(rect_bits & 7u) << 53 |
+           (uint64_t)(pair_bits & 63u) << 57;
+}
+// the wall pairs of axis ax (0..2) in a shape key, and of all three
+__host__ __device__ constexpr uint32_t flat_shape_pairs(uint64_t key, uint32_t ax) {
+    return (uint32_t)(key >> (57u + 2u * ax)) & 3u;
+}
+__host__ __device__ constexpr uint32_t flat_shape_pairs(uint64_t key) {
+    return flat_shape_pairs(key, 0u) + flat_shape_pairs(key, 1u) + flat_shape_pairs(key, 2u);
+}
+// A k_paths with wall pairs reads their LDS table (spt_kernels.hip make_pair_table), 2 entries of 2 float4
+// per pair, behind the launch-sized shading records, and its counting form keeps one count behind that
+__host__ __device__ constexpr uint32_t flat_pair_table_bytes(uint64_t key) {
+    return flat_shape_pairs(key) ? 64u * flat_shape_pairs(key) + 16u : 0u;
 }
 // ... plus the launch configuration the kernels read in their step loop, baked in as constants too
 // (round 4): max_bounces and rr_depth (6 bits each), the sky switch, SPT_FLAG_ABS_FLOAT and the scene's

@@ -66,9 +66,94 @@ __device__ __forceinline__ void closest_flat_exact(const float4* __restrict__ pr
 // and the compiler schedules the scalar record loads itself — it issues the loads of later
 // primitives while earlier ones are tested and reads only the words each test uses (C2: +7.6 %
 // over the run-time loop, whose loads are pinned to one round trip per primitive).
+//
+// Wall pairs (kPaired, a shape key with pair bits: scene.h flat_wall_pairs puts each axis group's
+// opposite pairs first, as (lower plane, higher plane) records). A ray whose origin lies between the
+// two planes of a pair, lo <= o[AX] <= hi, can only reach the wall it faces: for the other one the
+// numerator Q[AX] - o[AX] is zero or has the opposite sign of d[AX], so div_ref's t is <= 0 or below
+// 2^-59 in magnitude, isect_quad_axis_fast rejects it (t >= kTNear fails) and take(kInf) never lowers
+// the best hit (a key with t = inf gives kMiss whatever its index bits). So each lane tests only the
+// wall of the pair that its direction faces (|d[AX]| >= 2^-20 here, never zero), its five words read
+// from a small LDS table by `up`; if any lane of the wave starts outside the slab, the whole wave
+// tests the other wall too — both are exact tests of real quads, so that is always right.
+
+// The table: per pair two entries of two float4, lower plane first:
+// (a[AX], a[U], a[V], c[U]), (d[V], original index bits, 0, 0); the x pairs, then y, then z.
+template <uint64_t kShape>
+__device__ __forceinline__ void make_pair_table(const float4* __restrict__ prims, float4* tab) {
+    constexpr uint32_t kEnds = (uint32_t)(kShape & 0x3fffffffu), kN = (uint32_t)(kShape >> 30) & 63u;
+    constexpr uint32_t kE0 = 2u * flat_shape_pairs(kShape, 0u), kE1 = kE0 + 2u * flat_shape_pairs(kShape, 1u);
+    constexpr uint32_t kE2 = kE1 + 2u * flat_shape_pairs(kShape, 2u);
+    const uint32_t e = threadIdx.x;
+    if (e < kE2) {
+        const int ax = e < kE0 ? 0 : (e < kE1 ? 1 : 2);
+        const int u = ax == 0 ? 1 : 0, v = ax == 2 ? 1 : 2;  // isect_quad_axis_fast's U, V
+        const uint32_t first = ax == 0 ? 0u : (ax == 1 ? kE0 : kE1);
+        const uint32_t k = kN + ((kEnds >> (6 * ax)) & 63u) + (e - first);  // the kind-major copy's record
+        const float4 pa = prims[4 * k + 0], pb = prims[4 * k + 1], pc = prims[4 * k + 2], pd = prims[4 * k + 3];
+        tab[2 * e + 0] = make_float4(comp(pa, ax), comp(pa, u), comp(pa, v), comp(pc, u));
+        tab[2 * e + 1] = make_float4(comp(pd, v), pb.w, 0.0f, 0.0f);
+    }
+}
+
+// SPT_PAIR_FORM 1 (measurement builds): the lane's wall picked word by word from the two records' scalar
+// words (a v_mov and a v_cndmask each) instead of read from the LDS table. Measured on C2
+// (profiles/wall_pairs_rates.txt): +1.2 % over testing every wall, the table +6.9 %.
+#ifndef SPT_PAIR_FORM
+#define SPT_PAIR_FORM 0
+#endif
+
+// The kNP wall pairs at the head of axis group AX: kp = the group's first record, tab = the axis's
+// first table entry, `best` = closest_flat's running (t bits, original index) key. second: the counting
+// kernels' count of wave-level second passes (LDS), or null.
+template <int AX, uint32_t kNP>
+__device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, const float4* tab, F3 o, F3 d, RcpRef r,
+                                                uint64_t& best, uint32_t* second) {
+    if constexpr (kNP != 0u) {
+        constexpr int U = AX == 0 ? 1 : 0;
+        constexpr int V = AX == 2 ? 1 : 2;
+        const bool up = comp(d, AX) > 0.0f;
+        const float oa = comp(o, AX);
+        const float4* lane_tab = tab + (up ? 2 : 0);
+        const float4* other_tab = tab + (up ? 0 : 2);
+#pragma unroll
+        for (uint32_t p = 0; p < kNP; ++p) {
+            const float4 la = kp[8 * p + 0], ha = kp[8 * p + 4];  // the two walls' a = (Q, D): scalar loads
+            auto test = [&](const float4* t4, bool high) {
+#if SPT_PAIR_FORM == 1
+                (void)t4;
+                const float4 lb = kp[8 * p + 1], lc = kp[8 * p + 2], ld = kp[8 * p + 3];
+                const float4 hb = kp[8 * p + 5], hc = kp[8 * p + 6], hd = kp[8 * p + 7];
+                const float4 e0 = make_float4(high ? comp(ha, AX) : comp(la, AX), high ? comp(ha, U) : comp(la, U),
+                                              high ? comp(ha, V) : comp(la, V), high ? comp(hc, U) : comp(lc, U));
+                const float4 e1 = make_float4(high ? comp(hd, V) : comp(ld, V), high ? hb.w : lb.w, 0.0f, 0.0f);
+#else
+                (void)high;
+                const float4 e0 = t4[4 * p + 0], e1 = t4[4 * p + 1];
+#endif
+                const float t = isect_rect_axis_fast<AX>(e0.x, e0.y, e0.z, e0.w, e1.x, o, d, r, kTNear);
+                const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | __float_as_uint(e1.y);
+                best = key < best ? key : best;
+            };
+            test(lane_tab, up);
+            const bool inside = comp(la, AX) <= oa && oa <= comp(ha, AX);
+            if (__ballot(!inside) != 0ull) {
+                test(other_tab, !up);
+                // (one count per wave: the first active lane's, in LDS)
+                if (second && __lane_id() == (uint32_t)__ffsll((long long)__ballot(true)) - 1u) atomicAdd(second, 1u);
+            }
+        }
+    }
+}
 
 #define SPT_NOPIN(v) ((void)0)
-#define SPT_FLAT_GROUPS(UNROLL, PIN)                                                            \
+#define SPT_NOHEAD(AX, RD)
+// an axis group's wall pairs (its first 2 x pairs records), before the loop over the rest of the group
+#define SPT_PAIR_HEAD(AX, RD)                                                                   \
+    flat_pair_tests<AX, flat_shape_pairs(kShape, AX)>(kp + 4 * k, pair_tab + 4 * pair0, o, d, RD, best, second); \
+    k += 2u * flat_shape_pairs(kShape, AX);                                                     \
+    pair0 += flat_shape_pairs(kShape, AX);
+#define SPT_FLAT_GROUPS(UNROLL, PIN, HEAD)                                                      \
     {                                                                                           \
         uint32_t k = 0;                                                                         \
         UNROLL for (const uint32_t e = flat_ends & 63u; k < e; ++k) { /* spheres */             \
@@ -77,8 +162,11 @@ __device__ __forceinline__ void closest_flat_exact(const float4* __restrict__ pr
             PIN(pb);                                                                            \
             take(isect_sphere_fast(pa, pb.x, o, d, a, r2a, kTNear, redo), pb);                  \
         }                                                                                       \
+        HEAD(0, rdx)                                                                            \
         SPT_FLAT_GROUP(UNROLL, PIN, 6, (isect_quad_axis_fast<0, ((kRectBits >> 0) & 1u) != 0u>(pa, pc, pd, o, d, rdx, kTNear))) \
+        HEAD(1, rdy)                                                                            \
         SPT_FLAT_GROUP(UNROLL, PIN, 12, (isect_quad_axis_fast<1, ((kRectBits >> 1) & 1u) != 0u>(pa, pc, pd, o, d, rdy, kTNear))) \
+        HEAD(2, rdz)                                                                            \
         SPT_FLAT_GROUP(UNROLL, PIN, 18, (isect_quad_axis_fast<2, ((kRectBits >> 2) & 1u) != 0u>(pa, pc, pd, o, d, rdz, kTNear))) \
         SPT_FLAT_GROUP(UNROLL, PIN, 24, (isect_quad(pa, pb, pc, pd, o, d, kTNear)))              \
         UNROLL for (; k < n_prims; ++k) { /* triangles */                                       \
@@ -100,10 +188,11 @@ __device__ __forceinline__ void closest_flat_exact(const float4* __restrict__ pr
         take(TEST, pb);                                                                         \
     }
 
-template <uint64_t kShape = 0>
+template <uint64_t kShape = 0, bool kPaired = false>
 __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, uint32_t n_prims, F3 o, F3 d,
                                              float& best_t, uint32_t& best_k, bool fast_scene = false,
-                                             uint32_t flat_ends = 0u) {
+                                             uint32_t flat_ends = 0u, const float4* pair_tab = nullptr,
+                                             uint32_t* second = nullptr) {
     const float in_t = best_t;
     const uint32_t in_k = best_k;
     constexpr uint32_t kRectBits = (uint32_t)(kShape >> 53) & 7u;  // flat_shape_key
@@ -125,10 +214,18 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
                 const uint32_t flat_ends = (uint32_t)(kShape & 0x3fffffffu);
                 const uint32_t n_prims = (uint32_t)(kShape >> 30) & 63u;
                 const float4* __restrict__ kp = prims + 4 * n_prims;  // the kind-major copy
-                SPT_FLAT_GROUPS(_Pragma("unroll"), SPT_NOPIN)
+                if constexpr (kPaired && flat_shape_pairs(kShape) != 0u) {
+                    // the opposite wall pairs at the head of each axis group (flat_pair_tests), then the rest
+                    static_assert((((kShape >> 57) & 3u) == 0u || (kRectBits & 1u)) && (((kShape >> 59) & 3u) == 0u || (kRectBits & 2u)) &&
+                                  (((kShape >> 61) & 3u) == 0u || (kRectBits & 4u)), "wall pairs only in rectangle groups");
+                    uint32_t pair0 = 0;  // the axis's first pair in the table
+                    SPT_FLAT_GROUPS(_Pragma("unroll"), SPT_NOPIN, SPT_PAIR_HEAD)
+                } else {
+                    SPT_FLAT_GROUPS(_Pragma("unroll"), SPT_NOPIN, SPT_NOHEAD)
+                }
             } else {
                 const float4* __restrict__ kp = prims + 4 * n_prims;
-                SPT_FLAT_GROUPS(, SPT_PIN4)
+                SPT_FLAT_GROUPS(, SPT_PIN4, SPT_NOHEAD)
             }
             if (__ballot(redo) == 0ull || !redo) {
                 best_t = __uint_as_float((uint32_t)(best >> 32));
@@ -145,6 +242,8 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
 #undef SPT_FLAT_GROUP
 #undef SPT_FLAT_GROUPS
 #undef SPT_NOPIN
+#undef SPT_NOHEAD
+#undef SPT_PAIR_HEAD
 
 // BVH closest hit. Ties are broken on the primitive's ORIGINAL index (DevPrim b.w), so the result
 // equals closest_flat over the unreordered scene whatever the tree and the traversal order.
@@ -1535,6 +1634,15 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     __shared__ uint32_t s_shadow[kStats && kNee ? 1u : 1u];  // NEE shadow rays traced (statistics)
     if (kStats && kNee && threadIdx.x == 0u) s_shadow[0] = 0u;
     if (!kBvh) make_shade_recs(prims, mats, sp.n_prims, s_scene);
+    // a shape with wall pairs: their table behind the shading records, then the counting forms' count of
+    // second passes (launch_paths sizes the LDS: flat_pair_table_bytes)
+    constexpr uint32_t kPairs = kBvh ? 0u : flat_shape_pairs(kShape);
+    [[maybe_unused]] float4* const pair_tab = s_scene + 3u * ((uint32_t)(kShape >> 30) & 63u);
+    [[maybe_unused]] uint32_t* const pair_second = kStats ? (uint32_t*)(pair_tab + 4u * kPairs) : nullptr;
+    if constexpr (kPairs != 0u) {
+        make_pair_table<kShape>(prims, pair_tab);
+        if (kStats && threadIdx.x == 0u) *pair_second = 0u;
+    }
     // the next launch's work heads (stream order: the previous user of that set has finished)
     if (blockIdx.x == 0u && threadIdx.x < kWorkHeads) work_next[threadIdx.x * kWorkStride] = 0u;
     if (kStats && threadIdx.x < kMaxBounces) {
@@ -1994,7 +2102,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         best_k = tv.best_k;
                     } else {
                         SPT_MARK(closest);
-                        closest_flat<kShape>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends);
+                        closest_flat<kShape, true>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u,
+                                                   sp.flat_ends, pair_tab, pair_second);
                     }
                     if constexpr (kNee) {
                         if (!kInline && shadow) {  // the shadow ray: the estimate counts if nothing was hit before smax
@@ -2204,7 +2313,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     shadow = false;
                     float bt = smax;
                     uint32_t bk = kMiss;
-                    closest_flat<kShape>(prims, n_prims, o, nd, bt, bk, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends);
+                    closest_flat<kShape, true>(prims, n_prims, o, nd, bt, bk, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends,
+                                               pair_tab, pair_second);
                     if (!(bt < smax)) {
                         const uint32_t e = ring_entry(q);
                         L = F3{L.x + s_L[wave][0][e], L.y + s_L[wave][1][e], L.z + s_L[wave][2][e]};
@@ -2267,6 +2377,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             if (s_rmw[threadIdx.x]) atomicAdd(&totals[kMaxBounces + threadIdx.x], (unsigned long long)s_rmw[threadIdx.x]);
         }
         if (kNee && threadIdx.x == 0u && s_shadow[0]) atomicAdd(&totals[kTotShadow], (unsigned long long)s_shadow[0]);
+        if constexpr (kPairs != 0u)
+            if (threadIdx.x == 0u && *pair_second) atomicAdd(&totals[kTotPairSecond], (unsigned long long)*pair_second);
     }
 }
 
@@ -3184,7 +3296,8 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
     ShadeParams sp = shade_params(p, 0u);
     CameraParams cam = camera_params(p);
     const bool bvh = p.nodes != nullptr;
-    const size_t lds_scene = bvh ? 0 : sizeof(float4) * 3u * p.n_prims;  // make_shade_recs
+    // make_shade_recs; a specialized kernel with wall pairs: make_pair_table and the second-pass count
+    const size_t lds_scene = bvh ? 0 : sizeof(float4) * 3u * p.n_prims + flat_pair_table_bytes(p.jit_shape);
     // The channel-lane kernel (kChan) is chosen by the plan's first chunk size, and the plan is made from
     // the occupancy: so the occupancy asked here, which sizes the plan AND the grid, is that of the kernel
     // without kChan (first_shift = kMaxChunkShift), also when the kChan kernel then runs. Whether asking

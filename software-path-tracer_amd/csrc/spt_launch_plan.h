@@ -75,12 +75,15 @@ inline uint32_t frame_hit_mode(const PassParams& p, bool cache_valid, bool lists
 
 // The variant's kernel compiled for a flat scene's shape (spt_jit.h), and the env to ask for it with;
 // kind < 0: there is none (a BVH scene, statistics, or no shape), the offline-compiled kernel runs.
+// The counting k_paths of a shape with wall pairs (flat_shape_pairs) is compiled for the shape too, on first
+// use: it then runs the paired wall test the timed kernel runs, and counts its second passes.
 struct JitKind {
     int kind, env;
 };
 constexpr JitKind kJitNone{-1, 0};
 inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.stats || v.jitter || v.bsdf) return kJitNone;
+    if (!shape || v.bvh || v.jitter || v.bsdf) return kJitNone;
+    if (v.stats) return flat_shape_pairs(shape) ? JitKind{v.nee ? kJitPathsNeeStats : kJitPathsStats, v.env} : kJitNone;
     return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
 }
 inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
