@@ -1,8 +1,8 @@
 # Build of the MI355X path-tracing integrator (no cmake needed: hipcc + g++ only).
 #
 #   make            libspt_hip.so (C-ABI + gfx950 kernels) and libspt_render.so (C++ render::PathTracer backend)
-#   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so) and its restatement with
-#                   material models (tests/cpp/libref_materials.so)
+#   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so), its restatement with
+#                   material models (tests/cpp/libref_materials.so) and the lens's device check (tests/cpp/test_device_lens)
 #   make cpp-tests  the C++ interface test driver (tests/cpp)
 #
 # Every float operation on the hot path is compiled with -ffp-contract=off, on the device and on the
@@ -58,7 +58,8 @@ $(RLIB): $(RENDER_SRCS) $(LIB) $(wildcard include/render/*.h) $(CSRC)/HIPPathTra
 	$(CXX) $(CXXFLAGS) -std=c++20 -shared -o $@ $(RENDER_SRCS) -L$(PKG) -lspt_hip -Wl,-rpath,'$$ORIGIN'
 
 REFMAT := tests/cpp/libref_materials.so
-oracle: $(REFMAT)
+DEVLENS := tests/cpp/test_device_lens
+oracle: $(REFMAT) $(DEVLENS)
 
 oracle/build/libcpu_ref.so: oracle/cpu_ref.c oracle/cpu_ref.h include/spt.h oracle/Makefile
 	$(MAKE) -C oracle
@@ -70,11 +71,17 @@ $(REFMAT): tests/cpp/ref_materials.c oracle/cpu_ref.h include/spt.h oracle/build
 	$(CC) -O2 $(FPFLAGS) -fPIC -std=c11 -Wall -Wextra -Iinclude -shared -o $@ tests/cpp/ref_materials.c \
 	  -Loracle/build -lcpu_ref -lm -Wl,-rpath,'$$ORIGIN/../../oracle/build'
 
+# GPU program (run by tests/test_gpu_lens.py; --host, run by tests/test_lens_host.py: its inputs' coverage, no
+# GPU): spt_device.h's camera_lens_ray, the device build against the host build; test infrastructure, built with
+# the oracle
+$(DEVLENS): tests/cpp/test_device_lens.hip $(CSRC)/spt_device.h
+	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
+
 cpp-tests: $(RLIB) oracle
 	$(MAKE) -C tests/cpp
 
 clean:
 	rm -rf $(OBJ) $(LIB) $(RLIB)
 	$(MAKE) -C oracle clean
-	rm -f $(REFMAT)
+	rm -f $(REFMAT) $(DEVLENS)
 	-$(MAKE) -C tests/cpp clean

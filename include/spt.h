@@ -315,6 +315,46 @@ int spt_camera_look_at(const float eye[3], const float target[3], const float up
 int spt_camera_ray(const spt_camera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
                    float jx, float jy, float o[3], float d[3]);
 
+/* ---- thin lens (superset: depth of field) -----------------------------------------------------------
+ * A lens belongs to the ctx's camera: an aperture of `radius` (world units) and a `focus_distance` f.
+ * In focus is the plane of the points origin + f * p, p the un-normalized image-plane vector above (for a
+ * spt_camera_look_at camera, |w| = 1: the plane at distance f in front of the eye). The ctx derives, in
+ * double and rounded once,  a = (float)(radius / |u|),  b = (float)(radius / |v|)  (|u| = sqrt((u.x*u.x +
+ * u.y*u.y) + u.z*u.z); 0 for a zero vector). A path's ray, in fp32 without contraction, with correctly
+ * rounded sqrtf and '/', px ... p as above (jx = jy = 0 or the two jitter draws first):
+ *   u1 = random_float(rng);  u2 = random_float(rng);
+ *   r = sqrtf(u1);  phi = 2.0f * pi_f * u2;  (sp, cp) = the integrator's fp64 sin and cos of (double)phi;
+ *   lx = (float)((double)r * cp);  ly = (float)((double)r * sp);  ax = lx * a;  ay = ly * b;
+ *   off.c = ax * u.c + ay * v.c;   o.c = origin.c + off.c;   t.c = f * p.c - off.c;
+ *   len = sqrtf((t.x*t.x + t.y*t.y) + t.z*t.z);  d.c = t.c / len
+ * and trace_ray continues with the RNG state after these draws: per path the jitter's two draws (if set),
+ * the lens's two, then everything as without a lens. Every schedule gives the same bits. A lens camera
+ * renders as a jittered one does (a camera ray per path: no camera-hit cache, no view cache). The
+ * first-hit features stay the chief ray's — the same camera's without a lens. */
+typedef struct spt_lens {   /* 16 bytes */
+    float radius;           /* the aperture's, world units; finite, >= 0; 0: no lens */
+    float focus_distance;   /* finite, > 0 */
+    uint32_t reserved[2];   /* must be 0 */
+} spt_lens;
+/* Set the lens of the ctx's camera (copied); NULL or radius == 0 removes it, bit for bit what the ctx
+ * rendered before it had one. SPT_ERR_INVALID without a camera (spt_set_camera first: the reference's
+ * pinhole has no lens), for a non-finite or negative radius, a non-finite or non-positive
+ * focus_distance, or a non-zero reserved word. Resets the progressive accumulation and the caches of the
+ * camera's rays as spt_set_camera does; the feature images stay valid. spt_set_camera(ctx, camera) keeps
+ * the lens (a and b follow the new u and v), spt_set_camera(ctx, NULL) drops it; kept across spt_configure. */
+int spt_set_camera_lens(spt_ctx* ctx, const spt_lens* lens);
+/* Host only: the lens ray (o, d) of pixel (x, y) with jitter (jx, jy) and aperture sample (u1, u2), by
+ * the function the kernels compile (csrc/spt_device.h camera_lens_ray): the same bits. u1 and u2 are
+ * random_float values, in [0, 1] (the sine and cosine are stated for phi in [0, 2 pi] only);
+ * SPT_ERR_INVALID outside that, NaN included, and for an invalid lens. */
+int spt_camera_lens_ray(const spt_camera* camera, const spt_lens* lens, uint32_t width, uint32_t height,
+                        uint32_t x, uint32_t y, float jx, float jy, float u1, float u2, float o[3], float d[3]);
+/* Host only: the focus distance that puts the point at distance t along the camera ray of pixel (x, y)
+ * with jitter (jx, jy) in focus: (float)(t / |p|), p in double from the camera's float fields.
+ * SPT_ERR_INVALID for a non-finite t or t <= 0. With spt_read_features' feat_b.w as t: click to focus. */
+int spt_camera_focus_at_hit(const spt_camera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                            float jx, float jy, float t, float* focus_distance);
+
 /* ---- materials (superset, north_star "BRDF + light sampling": the reference shades one Lambertian
  * surface of albedo 0.7, CPUPathTracer.cpp:260-274) -----------------------------------------------
  * Each material of the scene has a model beside its albedo and emission: DIFFUSE (the reference's

@@ -103,6 +103,15 @@ class SptCamera(ctypes.Structure):
     ]
 
 
+class SptLens(ctypes.Structure):
+    """spt_lens: the aperture's radius (world units) and the focus distance of a camera's thin lens; 16 bytes."""
+    _fields_ = [
+        ("radius", ctypes.c_float),
+        ("focus_distance", ctypes.c_float),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
 CAMERA_JITTER = 1  # SPT_CAMERA_JITTER
 SPT_MAX_BOUNCES = 32
 
@@ -169,6 +178,7 @@ EXPORTED_SYMBOLS = (
     "spt_comm_destroy", "spt_set_tuning",
     "spt_specialize_scene", "spt_compile_flat_kernels", "spt_update_prims",
     "spt_set_camera", "spt_camera_look_at", "spt_camera_ray",
+    "spt_set_camera_lens", "spt_camera_lens_ray", "spt_camera_focus_at_hit",
     "spt_set_material_models", "spt_bsdf_sample",
     "spt_render_features", "spt_read_features", "spt_features_device_ptr",
     "spt_denoise_params_default", "spt_denoise", "spt_set_denoise_form", "spt_read_denoised", "spt_denoised_device_ptr",
@@ -284,6 +294,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                 ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(SptCamera)], I),
         "spt_camera_ray": ([ctypes.POINTER(SptCamera), U32, U32, U32, U32, ctypes.c_float, ctypes.c_float,
                             ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], I),
+        "spt_set_camera_lens": ([P, ctypes.POINTER(SptLens)], I),
+        "spt_camera_lens_ray": ([ctypes.POINTER(SptCamera), ctypes.POINTER(SptLens), U32, U32, U32, U32,
+                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], I),
+        "spt_camera_focus_at_hit": ([ctypes.POINTER(SptCamera), U32, U32, U32, U32, ctypes.c_float, ctypes.c_float,
+                                     ctypes.c_float, ctypes.POINTER(ctypes.c_float)], I),
         "spt_set_material_models": ([P, P, U32], I),
         "spt_bsdf_sample": ([P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), I, U32,
                              ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(I),
@@ -375,6 +391,44 @@ def camera_ray(cam: SptCamera, width: int, height: int, x: int, y: int, jx: floa
     if rc != SPT_OK:
         raise SptError(f"spt_camera_ray -> {SPT_ERR.get(rc, rc)}")
     return o, d
+
+
+def _lens(lens, focus_distance=None) -> SptLens:
+    """An SptLens from one, or from (radius, focus_distance)."""
+    if isinstance(lens, SptLens):
+        return lens
+    out = SptLens()
+    out.radius, out.focus_distance = float(lens), float(focus_distance)
+    return out
+
+
+def camera_lens_ray(cam: SptCamera, lens, width: int, height: int, x: int, y: int, jx: float = 0.0, jy: float = 0.0,
+                    u1: float = 0.0, u2: float = 0.0):
+    """spt_camera_lens_ray (host only): origin and direction (two float32 arrays of 3) of the ray of pixel
+    (x, y) with jitter (jx, jy) from the point (u1, u2) of the aperture of `lens` (an SptLens or a
+    (radius, focus_distance) pair), from the function the kernels compile: the same bits."""
+    l = lens if isinstance(lens, SptLens) else _lens(*lens)
+    o = np.zeros(3, dtype=np.float32)
+    d = np.zeros(3, dtype=np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    rc = load_library().spt_camera_lens_ray(ctypes.byref(cam), ctypes.byref(l), width, height, x, y, float(jx),
+                                            float(jy), float(u1), float(u2), o.ctypes.data_as(fp),
+                                            d.ctypes.data_as(fp))
+    if rc != SPT_OK:
+        raise SptError(f"spt_camera_lens_ray -> {SPT_ERR.get(rc, rc)}")
+    return o, d
+
+
+def camera_focus_at_hit(cam: SptCamera, width: int, height: int, x: int, y: int, t: float, jx: float = 0.0,
+                        jy: float = 0.0) -> float:
+    """spt_camera_focus_at_hit (host only): the focus distance that puts the point at distance t along the
+    camera ray of pixel (x, y) with jitter (jx, jy) in focus."""
+    f = ctypes.c_float()
+    rc = load_library().spt_camera_focus_at_hit(ctypes.byref(cam), width, height, x, y, float(jx), float(jy),
+                                                float(t), ctypes.byref(f))
+    if rc != SPT_OK:
+        raise SptError(f"spt_camera_focus_at_hit -> {SPT_ERR.get(rc, rc)}")
+    return f.value
 
 
 def material_models(models) -> np.ndarray:
@@ -476,6 +530,7 @@ class Context:
         self.width = self.height = 0
         self.cfg = SptConfig()
         self._out_reg = None  # the array registered by register_host_output
+        self._camera: Optional[SptCamera] = None  # a copy of set_camera's (focus_at)
 
     def _check(self, rc: int, what: str) -> None:
         if rc != SPT_OK:
@@ -649,6 +704,35 @@ class Context:
         """spt_set_camera: the camera of later renders (look_at), or None for the reference's pinhole at
         the origin; resets the accumulation."""
         self._check(self.lib.spt_set_camera(self.h, ctypes.byref(cam) if cam is not None else None), "spt_set_camera")
+        # (for focus_at; a copy: the ctx copied it too)
+        self._camera = SptCamera.from_buffer_copy(cam) if cam is not None else None
+
+    def set_camera_lens(self, radius=None, focus_distance: float = 1.0) -> None:
+        """spt_set_camera_lens: a thin lens on the ctx's camera — the aperture's radius in world units (or an
+        SptLens) and the distance of the plane in focus — or None / radius 0 for none; resets the accumulation.
+        set_camera(cam) keeps the lens, set_camera(None) drops it."""
+        if radius is None:
+            self._check(self.lib.spt_set_camera_lens(self.h, None), "spt_set_camera_lens")
+            return
+        lens = _lens(radius, focus_distance)
+        self._check(self.lib.spt_set_camera_lens(self.h, ctypes.byref(lens)), "spt_set_camera_lens")
+
+    def focus_at(self, x: int, y: int) -> Optional[float]:
+        """Click to focus: the focus distance that puts what pixel (x, y) of the full image shows — its first
+        hit (read_features) — in focus, or None where its chief ray misses the scene. Needs a camera, and
+        row y on this ctx's shard."""
+        if self._camera is None:
+            raise SptError("focus_at needs a camera (set_camera)")
+        w, h = self.width, self.height
+        rank, count = int(self.cfg.shard_rank), max(1, int(self.cfg.shard_count))
+        if not (0 <= x < w and 0 <= y < h) or y % count != rank:
+            raise SptError("focus_at: the pixel is outside the image or on another ctx's rows")
+        _, feat_b, _ = self.read_features()
+        t = float(feat_b.reshape(-1, w, 4)[y // count, x, 3])
+        if not np.isfinite(t):
+            return None
+        j = 0.5 if self._camera.flags & CAMERA_JITTER else 0.0
+        return camera_focus_at_hit(self._camera, w, h, x, y, t, j, j)
 
     def set_material_models(self, models) -> None:
         """spt_set_material_models: one model per material of the current scene — a MATERIAL_MODEL_DTYPE array
@@ -914,6 +998,8 @@ class HIPPathTracer(PathTracer):
         self._settings_mode = settings_mode
         self._camera: Optional[SptCamera] = None
         self._camera_dirty = False
+        self._lens: Optional[SptLens] = None
+        self._lens_dirty = False
         self._models = None
         self._models_dirty = False
         self._denoise: Optional[DenoiseParams] = None
@@ -932,6 +1018,19 @@ class HIPPathTracer(PathTracer):
         reference's; the accumulation restarts there."""
         self._camera = cam
         self._camera_dirty = True
+        if cam is None:
+            # the lens goes with its camera, set or pending, at this moment (as HIPPathTracer::set_camera); the
+            # removal stays pending, for the ctx keeps its lens if a new camera arrives before the next render()
+            self._lens = None
+            self._lens_dirty = True
+
+    def set_lens(self, radius=None, focus_distance: float = 1.0) -> None:
+        """Not in the reference interface: a thin lens on the camera (Context.set_camera_lens) from the next
+        render() on, or None / radius 0 for none; the accumulation restarts there. It needs a camera
+        (set_camera), stays when the camera moves and goes with it at the moment of set_camera(None): a lens
+        set before that call, applied or still pending, is dropped."""
+        self._lens = None if radius is None else _lens(radius, focus_distance)
+        self._lens_dirty = True
 
     def set_material_models(self, models) -> None:
         """Not in the reference interface: one model per material of the scene (Context.set_material_models; the
@@ -975,6 +1074,11 @@ class HIPPathTracer(PathTracer):
             self._frame_count = 0
             self._camera_dirty = False
             self._ctx.set_camera(self._camera)
+        if self._lens_dirty:
+            self._frame_count = 0
+            self._lens_dirty = False
+            if self._lens is not None or self._camera is not None:  # (no camera: the ctx has no lens either)
+                self._ctx.set_camera_lens(self._lens)
         if self._frame_count == 0:
             self._ctx.reset()
         if needs_rebuild:

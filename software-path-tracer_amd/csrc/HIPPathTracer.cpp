@@ -105,6 +105,22 @@ namespace render
 		if (camera)
 			m_camera = *camera;
 		m_cameraChanged = true;
+		if (!camera)
+		{
+			// the lens goes with its camera, set or pending, at this moment. The ctx drops its own only when
+			// render() hands it the cleared camera; if a new camera arrives before that, the ctx would keep
+			// its lens across it, so the removal stays pending and render() sends it once a camera is back
+			m_hasLens = false;
+			m_lensChanged = true;
+		}
+	}
+
+	void HIPPathTracer::set_lens(const spt_lens *lens)
+	{
+		m_hasLens = lens != nullptr;
+		if (lens)
+			m_lens = *lens;
+		m_lensChanged = true;
 	}
 
 	void HIPPathTracer::set_material_models(const spt_material_model *models, uint32_t n)
@@ -209,6 +225,17 @@ namespace render
 			// another view: a fresh accumulation, and nothing resolved for it yet
 			SPT_CALL(m_ctx, spt_set_camera(m_ctx, m_hasCamera ? &m_camera : nullptr));
 			m_cameraChanged = false;
+			m_frameCount = 0;
+			m_resolvedAt = 0;
+			m_outputDirty = true;
+		}
+		if (m_lensChanged)
+		{
+			// (after the camera: a lens needs one) other camera rays: a fresh accumulation too
+			// (removing the lens of no camera is nothing to do: the ctx has none either)
+			if (m_hasLens || m_hasCamera)
+				SPT_CALL(m_ctx, spt_set_camera_lens(m_ctx, m_hasLens ? &m_lens : nullptr));
+			m_lensChanged = false;
 			m_frameCount = 0;
 			m_resolvedAt = 0;
 			m_outputDirty = true;

@@ -55,6 +55,13 @@ namespace render
 		void set_camera(const spt_camera *camera);
 		void clear_camera() { set_camera(nullptr); }
 
+		// Not in the reference interface: a thin lens on that camera (spt.h spt_lens; copied) from the
+		// next render() on, which restarts the accumulation; nullptr or radius 0 removes it. It needs a
+		// camera (render() fails without one), stays when the camera moves, and goes with clear_camera() at
+		// the moment of that call: a lens set before it, applied or still pending, is dropped.
+		void set_lens(const spt_lens *lens);
+		void clear_lens() { set_lens(nullptr); }
+
 		// Not in the reference interface (it shades one Lambertian 0.7, CPUPathTracer.cpp:260-274): the
 		// material models of the next render() on (spt.h spt_material_model; copied), one per material of
 		// the uploaded scene — this backend's scenes have the single reference material, so n is 1 — or
@@ -87,6 +94,9 @@ namespace render
 		spt_camera m_camera{};             // set_camera's, while m_hasCamera
 		bool m_hasCamera = false;
 		bool m_cameraChanged = false;
+		spt_lens m_lens{};                 // set_lens's, while m_hasLens
+		bool m_hasLens = false;
+		bool m_lensChanged = false;
 		std::vector<spt_material_model> m_models;  // set_material_models's (empty: all diffuse)
 		bool m_modelsChanged = false;
 		spt_denoise_params m_denoise{};            // set_denoise's, while m_denoiseOn

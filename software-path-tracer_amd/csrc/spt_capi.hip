@@ -173,6 +173,9 @@ struct spt_ctx {
     bool has_camera = false;
     spt_camera camera{};
     float4* d_camera = nullptr;  // its device record (PassParams::cam_pose), allocated by the first spt_set_camera
+    // spt_set_camera_lens: the camera's thin lens, or none; kept across spt_configure and spt_set_camera(cam)
+    bool has_lens = false;
+    spt_lens lens{};
 
     // spt_set_material_models: one model per material of h_mats, or empty (all DIFFUSE). The device
     // materials carry each model as one word (DevMaterial::albedo[3], spt_device.h model_kind); h_dm is
@@ -514,6 +517,37 @@ static uint32_t sphere_emitters(const std::vector<DevEmitter>& emit) {
 }
 static bool nee_active(const spt_ctx* c) { return c->configured && (c->cfg.flags & SPT_FLAG_NEE) && c->n_emit != 0u; }
 
+// PassParams::cam_mode of the ctx's camera (has_camera)
+static uint32_t camera_mode(const spt_ctx* c) {
+    return ((c->camera.flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed) | (c->has_lens ? kCamLens : 0u);
+}
+// A lens's (a, b, f) on a camera: a = radius / |u|, b = radius / |v| in double, rounded once (a vanishing
+// axis gives 0: the aperture has no extent along it)
+static CameraLens lens_scalars(const spt_camera& cam, const spt_lens& lens) {
+    auto len = [](const float v[3]) {
+        return std::sqrt(((double)v[0] * v[0] + (double)v[1] * v[1]) + (double)v[2] * v[2]);
+    };
+    const double lu = len(cam.u), lv = len(cam.v);
+    return CameraLens{lu > 0.0 ? (float)((double)lens.radius / lu) : 0.0f,
+                      lv > 0.0 ? (float)((double)lens.radius / lv) : 0.0f, lens.focus_distance};
+}
+// Rewrite the camera's device record — (origin, mode), (u, a), (v, b), (w, f) — from the ctx's camera and
+// lens; a launch in flight reads the old one, so the stream is drained first
+static int write_camera_record(spt_ctx* c) {
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (!c->d_camera) SPT_HIP(c, hipMalloc(&c->d_camera, 4 * sizeof(float4)));
+    const spt_camera& cam = c->camera;
+    const CameraLens l = c->has_lens ? lens_scalars(cam, c->lens) : CameraLens{0.0f, 0.0f, 0.0f};
+    const uint32_t mode = camera_mode(c);
+    float4 rec[4] = {make_float4(cam.origin[0], cam.origin[1], cam.origin[2], 0.0f),
+                     make_float4(cam.u[0], cam.u[1], cam.u[2], l.a), make_float4(cam.v[0], cam.v[1], cam.v[2], l.b),
+                     make_float4(cam.w[0], cam.w[1], cam.w[2], l.f)};
+    std::memcpy(&rec[0].w, &mode, sizeof(mode));
+    SPT_HIP(c, hipMemcpy(c->d_camera, rec, sizeof(rec), hipMemcpyHostToDevice));
+    return SPT_OK;
+}
+
 // Start compiling a configured flat scene's specialized kernels in the background (a new shape or a new
 // configuration): frames rendered before they are ready run the generic kernels.
 static void prefetch_flat(const spt_ctx* c) {
@@ -584,7 +618,7 @@ PassParams base_params(spt_ctx* c) {
     // NEE only with the flag and something to sample (otherwise the oracle's integrator is the plain one)
     p.nee = NeeParams{c->d_emit, nee_active(c) ? c->n_emit : 0u, c->n_emit_spheres};
     if (c->has_camera) {
-        p.cam_mode = (c->camera.flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed;
+        p.cam_mode = camera_mode(c);
         p.cam_pose = c->d_camera;
     }
     p.bsdf = c->bsdf ? 1u : 0u;
@@ -1143,8 +1177,8 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             p.live_rec = c->live_rec;
             p.sky_pix = c->sky_pix;
             p.list_counts = c->list_counts;
-            // (a jittered camera: hit_mode 0, the camera segment traced per frame; no cache, no lists, no wait)
-            const bool jitter = p.cam_mode == kCamJitter || p.bsdf != 0u;  // (and so do material models)
+            // (a jittered or lens camera: hit_mode 0, the camera segment traced per frame; no cache, no lists, no wait)
+            const bool jitter = cam_per_path(p.cam_mode) || p.bsdf != 0u;  // (and so do material models)
             p.hit_mode = frame_hit_mode(p, c->hit_cache_valid, c->frame_lists);
             p.live_pixels = c->live_pixels;
             if (c->fuse_frames != 0.0f && done + 1u == n_frames) {  // the call's last frame resolves as it ends
@@ -1385,17 +1419,15 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
         if (cam->flags & ~(uint32_t)SPT_CAMERA_JITTER) return fail(c, SPT_ERR_INVALID, "camera: unknown flags");
         if (cam->reserved[0] | cam->reserved[1] | cam->reserved[2])
             return fail(c, SPT_ERR_INVALID, "camera: reserved must be 0");
-        // the device record: (origin, mode), (u, 0), (v, 0), (w, 0); a launch in flight reads the old one
-        SPT_HIP(c, hipSetDevice(c->device));
-        SPT_HIP(c, hipStreamSynchronize(c->stream));
-        if (!c->d_camera) SPT_HIP(c, hipMalloc(&c->d_camera, 4 * sizeof(float4)));
-        const uint32_t mode = (cam->flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed;
-        float4 rec[4] = {make_float4(cam->origin[0], cam->origin[1], cam->origin[2], 0.0f),
-                         make_float4(cam->u[0], cam->u[1], cam->u[2], 0.0f), make_float4(cam->v[0], cam->v[1], cam->v[2], 0.0f),
-                         make_float4(cam->w[0], cam->w[1], cam->w[2], 0.0f)};
-        std::memcpy(&rec[0].w, &mode, sizeof(mode));
-        SPT_HIP(c, hipMemcpy(c->d_camera, rec, sizeof(rec), hipMemcpyHostToDevice));
+        // the device record; a lens stays, on the new camera's u and v
+        const spt_camera old = c->camera;
         c->camera = *cam;
+        if (const int rc = write_camera_record(c); rc != SPT_OK) {
+            c->camera = old;
+            return rc;
+        }
+    } else {
+        c->has_lens = false;  // (the reference's pinhole has no lens)
     }
     c->has_camera = cam != nullptr;
     // the camera hits k_frame cached and the chunk costs k_paths recorded were the previous camera's
@@ -1406,6 +1438,39 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     c->feat_valid = false;  // (the first hits were the previous camera's)
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
+    return SPT_OK;
+}
+
+// nullptr: valid
+static const char* lens_error(const spt_lens& l) {
+    if (!std::isfinite(l.radius) || l.radius < 0.0f) return "lens: radius must be finite and >= 0";
+    if (!std::isfinite(l.focus_distance) || !(l.focus_distance > 0.0f)) return "lens: focus_distance must be finite and > 0";
+    if (l.reserved[0] | l.reserved[1]) return "lens: reserved must be 0";
+    return nullptr;
+}
+
+int spt_set_camera_lens(spt_ctx* c, const spt_lens* lens) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->has_camera) return fail(c, SPT_ERR_INVALID, "spt_set_camera_lens without a camera (spt_set_camera)");
+    if (lens)
+        if (const char* msg = lens_error(*lens)) return fail(c, SPT_ERR_INVALID, msg);
+    const bool had = c->has_lens;
+    const spt_lens old = c->lens;
+    c->has_lens = lens != nullptr && lens->radius != 0.0f;  // (radius 0: the pinhole, and its kernels)
+    if (c->has_lens) c->lens = *lens;
+    if (const int rc = write_camera_record(c); rc != SPT_OK) {
+        c->has_lens = had;
+        c->lens = old;
+        return rc;
+    }
+    // as spt_set_camera: what k_frame cached and k_paths recorded were the previous camera rays'. The
+    // feature images stay: they are the chief ray's, whatever the lens (k_features)
+    c->hit_cache_valid = false;
+    c->frame_lists = false;
+    c->chunk_order_key = 0;
+    c->view_valid = false;
+    prefetch_flat(c);
+    if (c->configured) return spt_reset(c);
     return SPT_OK;
 }
 
@@ -1695,6 +1760,45 @@ int spt_camera_ray(const spt_camera* cam, uint32_t width, uint32_t height, uint3
     d[0] = dir.x;
     d[1] = dir.y;
     d[2] = dir.z;
+    return SPT_OK;
+}
+
+int spt_camera_lens_ray(const spt_camera* cam, const spt_lens* lens, uint32_t width, uint32_t height, uint32_t x,
+                        uint32_t y, float jx, float jy, float u1, float u2, float o[3], float d[3]) {
+    if (!cam || !lens || !o || !d || width == 0 || height == 0) return SPT_ERR_INVALID;
+    if (lens_error(*lens)) return SPT_ERR_INVALID;
+    // the aperture sample is a pair of random_float values: sincos_2pi is stated for phi in [0, 2 pi]
+    if (!(u1 >= 0.0f && u1 <= 1.0f) || !(u2 >= 0.0f && u2 <= 1.0f)) return SPT_ERR_INVALID;
+    const CameraPose pose{F3{cam->origin[0], cam->origin[1], cam->origin[2]}, F3{cam->u[0], cam->u[1], cam->u[2]},
+                          F3{cam->v[0], cam->v[1], cam->v[2]}, F3{cam->w[0], cam->w[1], cam->w[2]}};
+    F3 org;
+    const F3 dir = camera_lens_ray(pose, lens_scalars(*cam, *lens), x, y, jx, jy, u1, u2, 1.0f / (float)width,
+                                   1.0f / (float)height, (float)width / (float)height, org);
+    o[0] = org.x;
+    o[1] = org.y;
+    o[2] = org.z;
+    d[0] = dir.x;
+    d[1] = dir.y;
+    d[2] = dir.z;
+    return SPT_OK;
+}
+
+int spt_camera_focus_at_hit(const spt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float jx,
+                            float jy, float t, float* focus_distance) {
+    if (!cam || !focus_distance || width == 0 || height == 0) return SPT_ERR_INVALID;
+    if (!std::isfinite(t) || !(t > 0.0f)) return SPT_ERR_INVALID;
+    // |p| of the pixel's image-plane vector, the formula of camera_ray_dir in double
+    const double px = (double)x + (double)jx, py = (double)y + (double)jy;
+    const double sx = ((px / (double)width) * 2.0 - 1.0) * ((double)width / (double)height);
+    const double sy = (1.0 - py / (double)height) * 2.0 - 1.0;
+    double q = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double p = (sx * (double)cam->u[a] + sy * (double)cam->v[a]) + (double)cam->w[a];
+        q += p * p;
+    }
+    const double len = std::sqrt(q);
+    if (!(len > 0.0) || !std::isfinite(len)) return SPT_ERR_INVALID;
+    *focus_distance = (float)((double)t / len);
     return SPT_OK;
 }
 

@@ -191,6 +191,68 @@ __host__ __device__ inline F3 camera_ray_dir(const CameraPose& c, uint32_t x, ui
     return F3{p.x / len, p.y / len, p.z / len};
 }
 
+// A thin lens on a posed camera (spt_set_camera_lens): a = radius / |u|, b = radius / |v| (the host's,
+// in double, rounded once) turn the camera's tan-scaled u and v into the aperture's axes, and f is the
+// focus distance: the points o + f * p, p the un-normalized image-plane vector of camera_ray_dir, are
+// in focus.
+struct CameraLens {
+    float a, b, f;
+};
+template <bool kSmemCoef>
+__host__ __device__ inline void sincos_2pi(double phi, double& s, double& c);
+
+// The lens form of camera_ray_dir: the ray from the point (u1, u2) of the aperture — a uniform point of
+// the disc, r = sqrtf(u1), phi = 2 pi u2 as bounce_dir_frame draws its direction — through the point of
+// the focus plane the pinhole ray of (x + jx, y + jy) meets. `o` receives the origin, the direction is
+// returned. fp32, no contraction, correctly rounded sqrtf and '/', sin and cos by sincos_2pi: DESIGN.md
+// "Thin lens" states the expressions, and the host (spt_camera_lens_ray) and every kernel compile this
+// one function. On the device u1 = +0 or in [2^-96, inf) takes sqrt_unit (every random_float does), and
+// the normalization takes sqrt_unit / div_ref under camera_ray_dir's gate (q in [2^-80, 2^40), every
+// numerator in [2^-100, 2^50] in magnitude); other lanes take the general routines. The same bits
+// (tests/cpp/test_device_lens.hip compares the device build with the host's on either side of every
+// term of both gates).
+template <bool kSmemCoef = false>
+__host__ __device__ inline F3 camera_lens_ray(const CameraPose& c, CameraLens l, uint32_t x, uint32_t y, float jx,
+                                              float jy, float u1, float u2, float inv_w, float inv_h, float aspect,
+                                              F3& o) {
+    const float px = (float)x + jx;
+    const float py = (float)y + jy;
+    const float u = px * inv_w;
+    const float v = 1.0f - py * inv_h;
+    const float sx = (u * 2.0f - 1.0f) * aspect;
+    const float sy = v * 2.0f - 1.0f;
+    const F3 p{(sx * c.u.x + sy * c.v.x) + c.w.x, (sx * c.u.y + sy * c.v.y) + c.w.y, (sx * c.u.z + sy * c.v.z) + c.w.z};
+    float r;
+#ifdef __HIP_DEVICE_COMPILE__
+    if ((uint32_t)(__float_as_uint(u1) == 0u) | (uint32_t)(__float_as_uint(u1) - 0x0f800000u < 0x7f800000u - 0x0f800000u))
+        r = sqrt_unit(u1);
+    else
+#endif
+        r = sqrtf(u1);
+    const float phi = 2.0f * kPiF * u2;
+    double sp, cp;
+    sincos_2pi<kSmemCoef>((double)phi, sp, cp);
+    const float lx = (float)((double)r * cp);
+    const float ly = (float)((double)r * sp);
+    const float ax = lx * l.a;
+    const float ay = ly * l.b;
+    const F3 off{ax * c.u.x + ay * c.v.x, ax * c.u.y + ay * c.v.y, ax * c.u.z + ay * c.v.z};
+    o = F3{c.o.x + off.x, c.o.y + off.y, c.o.z + off.z};
+    const F3 t{l.f * p.x - off.x, l.f * p.y - off.y, l.f * p.z - off.z};  // (o + f p) - (o + off)
+    const float q = (t.x * t.x + t.y * t.y) + t.z * t.z;
+#ifdef __HIP_DEVICE_COMPILE__
+    auto in_range = [](float a) {  // 2^-100 <= |a| <= 2^50 (on the magnitude's bits)
+        return (uint32_t)((__float_as_uint(a) & 0x7fffffffu) - 0x0d800000u <= 0x58800000u - 0x0d800000u);
+    };
+    if (((uint32_t)(q >= 0x1p-80f) & (uint32_t)(q < 0x1p40f) & in_range(t.x) & in_range(t.y) & in_range(t.z))) {
+        const RcpRef rr = rcp_ref(sqrt_unit(q));
+        return F3{div_ref(t.x, rr), div_ref(t.y, rr), div_ref(t.z, rr)};
+    }
+#endif
+    const float len = sqrtf(q);
+    return F3{t.x / len, t.y / len, t.z / len};
+}
+
 // sample_sky, CPUPathTracer.cpp:286-292: glm::mix(horizon, zenith, t).
 __device__ __forceinline__ F3 sample_sky(float dir_y, float4 horizon, float4 zenith) {
     const float t = 0.5f * (dir_y + 1.0f);

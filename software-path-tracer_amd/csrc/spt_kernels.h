@@ -131,8 +131,8 @@ struct PassParams {
     uint32_t* chunk_order;       // [shard pixels] first-tier chunk indices, costliest first
     uint64_t* chunk_order_key;   // (host) the plan the order was sorted for, 0 = none (launch_paths)
     // the camera (spt_set_camera): kCamReference: the reference's pinhole at the origin (primary_dir);
-    // otherwise cam_pose (device memory) holds (origin, cam_mode bits), (u, 0), (v, 0), (w, 0) of the
-    // spt_camera (spt_device.h camera_ray_dir)
+    // otherwise cam_pose (device memory) holds (origin, cam_mode bits), (u, a), (v, b), (w, f) of the
+    // spt_camera (spt_device.h camera_ray_dir) and its lens (camera_lens_ray; 0, 0, 0 without one)
     uint32_t cam_mode;
     uint32_t bsdf;  // (below; here it fills the padding before the pointer: PassParams keeps its size)
     const float4* cam_pose;
@@ -145,9 +145,15 @@ struct PassParams {
 // on that (k_paths' per-pixel bounce 0 and constant pixels, k_frame's hit cache and lists) stays.
 // kCamJitter: the ray goes through a point of the pixel drawn per path (the path's first two draws):
 // k_paths runs its kJitter form, k_frame and the wavefront kernels trace the camera segment as any other.
+// kCamLens: a bit or-ed onto kCamPosed or kCamJitter (spt_set_camera_lens): the ray starts at a point of
+// the aperture drawn per path (two draws, after the jitter's), so it is a per-path ray like the jittered
+// camera's and runs the same forms; the record's lanes [1].w, [2].w, [3].w hold the CameraLens (a, b, f).
 constexpr uint32_t kCamReference = 0;
 constexpr uint32_t kCamPosed = 1;
 constexpr uint32_t kCamJitter = 2;
+constexpr uint32_t kCamLens = 4;
+// this camera's ray is per path (jittered, through a lens, or both), not per pixel
+__host__ __device__ constexpr bool cam_per_path(uint32_t cam_mode) { return (cam_mode & (kCamJitter | kCamLens)) != 0u; }
 
 // A flat scene's shape, the compile-time key of its specialized persistent kernels (spt_jit.hip):
 // its kind groups' ends (PassParams::flat_ends, 30 bits), the primitive count (6 bits), a valid bit.
@@ -339,7 +345,7 @@ void launch_accumulate(const PassParams& p, hipStream_t s);
 bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view = nullptr);
 // the scenes and configurations whose k_paths keeps a per-pixel bounce 0 that a view's lists can hold
 inline bool view_lists_scene(const PassParams& p) {
-    return p.nodes == nullptr && p.n_prims != 0u && p.cam_mode != kCamJitter && p.bsdf == 0u;
+    return p.nodes == nullptr && p.n_prims != 0u && !cam_per_path(p.cam_mode) && p.bsdf == 0u;
 }
 // Build a view's lists on `s` (stream order): live / constant as in ViewPlan (room for shard_pixels
 // records each), counts[0] = live pixels, counts[1] = constant pixels, block_scratch: shard pixels / 256 words

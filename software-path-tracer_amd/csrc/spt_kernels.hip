@@ -676,11 +676,12 @@ struct CameraParams {
     const float4* pose = nullptr;
 };
 
-// The posed camera of a launch: (origin, mode bits), (u, 0), (v, 0), (w, 0) at c.pose (not nullptr), read
+// The posed camera of a launch: (origin, mode bits), (u, a), (v, b), (w, f) at c.pose (not nullptr), read
 // by scalar loads the compiler cannot hoist (the records are constant for the launch).
 struct CameraRecord {
     CameraPose pose;
-    uint32_t mode;  // kCamPosed or kCamJitter
+    uint32_t mode;  // kCamPosed or kCamJitter, with kCamLens or not
+    CameraLens lens;  // (kCamLens)
 };
 __device__ __forceinline__ CameraRecord camera_record(const CameraParams& c) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -691,40 +692,50 @@ __device__ __forceinline__ CameraRecord camera_record(const CameraParams& c) {
 #endif
     const float4 a = p[0], u = p[1], v = p[2], w = p[3];
     return CameraRecord{CameraPose{F3{a.x, a.y, a.z}, F3{u.x, u.y, u.z}, F3{v.x, v.y, v.z}, F3{w.x, w.y, w.z}},
-                        __float_as_uint(a.w)};
+                        __float_as_uint(a.w), CameraLens{u.w, v.w, w.w}};
 }
 
 struct CameraRay {
     F3 o, d;
-    uint32_t seed;  // the path's RNG state: the seed, advanced by the two jitter draws of kCamJitter
+    uint32_t seed;  // the path's RNG state: the seed, advanced by the jitter's two draws and the lens's two
 };
 
 // The camera ray of pixel (x, y) (y: the full-image row) for a path whose RNG state is `rng`: the
 // reference's pinhole; a posed camera through the pixel's corner; or through the point (jx, jy) of the
-// pixel, the path's first two draws.
+// pixel, the path's first two draws; with a lens, from the point of the aperture the path's next two
+// draws give (camera_lens_ray).
 // kShape: a kernel compiled with its launch configuration in the key (jit_config_key) knows whether the
 // launch has a camera; without one its code is the reference camera's alone, and the pointer is dead.
-template <uint64_t kShape = 0>
+// kLens false: a caller that only runs with a per-pixel camera ray (k_paths' per-pixel bounce 0 and the
+// view lists, which a lens camera never launches: cam_per_path) keeps its code without the lens's.
+template <uint64_t kShape = 0, bool kLens = true>
 __device__ __forceinline__ CameraRay camera_ray_xy(const CameraParams& c, uint32_t x, uint32_t y, uint32_t rng) {
     const bool has_camera = (kShape & kConfigValid) != 0 ? (kShape & kConfigCamera) != 0 : c.pose != nullptr;
     if (!has_camera) return CameraRay{F3{0.0f, 0.0f, 0.0f}, primary_dir(x, y, c.inv_w, c.inv_h, c.aspect), rng};
     const CameraRecord r = camera_record(c);
     float jx = 0.0f, jy = 0.0f;
-    if (r.mode == kCamJitter) {
+    if (r.mode & kCamJitter) {
         jx = random_float(rng);
         jy = random_float(rng);
+    }
+    if (kLens && (r.mode & kCamLens)) {
+        const float u1 = random_float(rng);
+        const float u2 = random_float(rng);
+        F3 o;
+        const F3 d = camera_lens_ray<true>(r.pose, r.lens, x, y, jx, jy, u1, u2, c.inv_w, c.inv_h, c.aspect, o);
+        return CameraRay{o, d, rng};
     }
     return CameraRay{r.pose.o, camera_ray_dir(r.pose, x, y, jx, jy, c.inv_w, c.inv_h, c.aspect), rng};
 }
 
-template <uint64_t kShape = 0>
+template <uint64_t kShape = 0, bool kLens = true>
 __device__ __forceinline__ CameraRay camera_ray(const CameraParams& c, uint32_t pid) {
     const uint32_t f = pid / c.shard_pixels;
     const uint32_t pix = pid - f * c.shard_pixels;
     const uint32_t lrow = pix / c.width;
     const uint32_t x = pix - lrow * c.width;
     const uint32_t y = c.shard_rank + c.shard_count * lrow;
-    return camera_ray_xy<kShape>(c, x, y, rng_seed(x, y, c.width, c.first_frame + f + 1u));
+    return camera_ray_xy<kShape, kLens>(c, x, y, rng_seed(x, y, c.width, c.first_frame + f + 1u));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1365,8 +1376,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_tail(const float4* __restrict_
 // launch). A slot is only handed out while its frame fits in the ring, so a long path holds back
 // at most kRing frames. HBM traffic per launch: 32 B per pixel (accum read + write).
 //
-// Unless the camera jitters (kCamJitter: the kJitter form below), the camera ray of a pixel has no
-// jitter (:63-69; a posed camera's neither), so its first segment is the same in every
+// Unless the camera jitters or has a lens (cam_per_path: the kJitter form below), the camera ray of a
+// pixel has no jitter (:63-69; a posed camera's neither), so its first segment is the same in every
 // frame: everything up to the random bounce direction (closest hit, Ng, n, emission, albedo, the
 // tangent frame of get_random_bounche, the offset origin) is computed once per pixel at the start
 // of the launch and kept in LDS. A frame's path starts from that state: only the RNG-dependent
@@ -1589,9 +1600,10 @@ __device__ __forceinline__ void advance_rays(const float4* __restrict__ nodes, c
 // every emitter kind; kNeeNoSpheres (BVH scenes whose emitter table holds no sphere) leaves the sphere
 // sample out of the kernel: its fp64 registers cost the BVH step loop spills (C4 NEE -4.4 %, record
 // r05_x), the flat kernels nothing.
-// kJitter: a jittered camera (kCamJitter). A path's camera ray depends on its own first two draws, so
+// kJitter: a camera whose ray is per path (cam_per_path: jittered, a lens, or both; read at run time:
+// camera_ray_xy). A path's camera ray depends on its own first two or four draws, so
 // there is no per-pixel bounce 0 and no constant pixel: every pixel of a chunk is live, and a slot
-// hand-out starts its path at bounce 0 — the seed, the two jitter draws, the camera ray, T = 1, L = 0 —
+// hand-out starts its path at bounce 0 — the seed, the camera's draws, the camera ray, T = 1, L = 0 —
 // which the step then traces and shades like any other segment (with kNee its emission counts as the
 // camera segment's). The ring and the frame-ordered accumulation are unchanged. Generic kernels only,
 // run with kEnv = 2.
@@ -1792,7 +1804,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     ps.r1 = ps.r2 = make_float4(0.f, 0.f, 0.f, 0.f);
                     live_px = true;
                 } else {
-                    const CameraRay cr = camera_ray_xy<kShape>(cam, x, y, x + y * cam.width);
+                    const CameraRay cr = camera_ray_xy<kShape, false>(cam, x, y, x + y * cam.width);
                     // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
                     ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
                     live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
@@ -2215,20 +2227,13 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 const float4 p0 = s_px[wave][0][r];
                 if constexpr (kStart0) {  // bounce 0 itself: the path's first two draws place its camera ray
                     rng = rng_seed(__float_as_uint(p0.w), 0u, 0u, frame);
-                    if constexpr (kBsdf) {  // whichever camera the launch has (a jittered one draws here)
-                        const CameraRay cr = camera_ray_xy<0>(cam, __float_as_uint(p0.x), __float_as_uint(p0.y), rng);
-                        o = cr.o;
-                        d = cr.d;
-                        rng = cr.seed;
-                        spec = false;
-                    } else {
-                    const float jx = random_float(rng);
-                    const float jy = random_float(rng);
-                    const CameraPose pose = camera_record(cam).pose;
-                    o = pose.o;
-                    d = camera_ray_dir(pose, __float_as_uint(p0.x), __float_as_uint(p0.y), jx, jy, cam.inv_w, cam.inv_h,
-                                       cam.aspect);
-                    }
+                    // whichever camera the launch has: kBsdf any, kJitter a per-path one (cam_per_path) — a
+                    // jittered one draws its point of the pixel here, a lens its point of the aperture
+                    const CameraRay cr = camera_ray_xy<0>(cam, __float_as_uint(p0.x), __float_as_uint(p0.y), rng);
+                    o = cr.o;
+                    d = cr.d;
+                    rng = cr.seed;
+                    if constexpr (kBsdf) spec = false;
                     T = F3{1.f, 1.f, 1.f};
                     L = F3{0.f, 0.f, 0.f};
                     bc = 0u;
@@ -2451,7 +2456,7 @@ __global__ __launch_bounds__(kBlock, kSmall ? kFrameWavesSmall : (kBvh ? kPathsW
         const uint32_t n_sky = __builtin_amdgcn_readfirstlane(cam.list_counts[1]);
         for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_sky; i += sky_blocks * kBlock) {
             const uint32_t px = cam.sky_pix[i];
-            const CameraRay cr = camera_ray<kShape>(cam, px);
+            const CameraRay cr = camera_ray<kShape, false>(cam, px);  // (hit_mode 3: never a per-path camera)
             float4 a = accum[px];
             // shade_hit's miss with T = 1 on L = 0 (CPUPathTracer.cpp:231-235), then :77-80
             F3 lc{0.f, 0.f, 0.f};
@@ -2961,7 +2966,8 @@ __global__ __launch_bounds__(kBlock) void k_features(const float4* __restrict__ 
         d = primary_dir(x, y, cam.inv_w, cam.inv_h, cam.aspect);
     } else {
         const CameraRecord r = camera_record(cam);
-        const float j = r.mode == kCamJitter ? 0.5f : 0.0f;
+        // (a lens leaves the images alone: they are the chief ray's, through the aperture's centre)
+        const float j = (r.mode & ~kCamLens) == kCamJitter ? 0.5f : 0.0f;
         o = r.pose.o;
         d = camera_ray_dir(r.pose, x, y, j, j, cam.inv_w, cam.inv_h, cam.aspect);
     }
@@ -3019,7 +3025,7 @@ __global__ __launch_bounds__(kBlock) void k_view_lists(const float4* __restrict_
         const uint32_t lrow = pix / cam.width;
         const uint32_t x = pix - lrow * cam.width;
         const uint32_t y = cam.shard_rank + cam.shard_count * lrow;
-        const CameraRay cr = camera_ray_xy<0>(cam, x, y, x + y * cam.width);
+        const CameraRay cr = camera_ray_xy<0, false>(cam, x, y, x + y * cam.width);
         ps = primary_state<false, 2, 0>(prims, nullptr, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, StkP{nullptr});
         const bool hit = (__float_as_uint(ps.r1.w) & kHitBit) != 0u;
         live_px = hit && 1u < sp.max_bounces;

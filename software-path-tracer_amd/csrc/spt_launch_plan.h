@@ -19,7 +19,8 @@ struct PathsVariant {
     int simd_waves;  // 0, or kBvhSmallWaves: the 8-wave kernel of small BVH scenes
     bool chan;       // the channel-lane kernel of flat scenes whose chunks are all <= 16 pixels (a small row shard)
     int nee;         // 0, kNeeAll, or kNeeNoSpheres (a BVH scene without sphere lights)
-    bool jitter = false;  // the kJitter form (a jittered camera): every path traces its camera segment; env 2 only
+    bool jitter = false;  // the kJitter form (a per-path camera ray: jittered, a lens, or both — cam_per_path): every path
+                          // traces its camera segment; env 2 only
     bool bsdf = false;    // the kBsdf form (a scene with material models): starts every path at bounce 0 too and reads
                           // the camera's kind at run time, so `jitter` stays false; env 2, nee 0 or kNeeAll
 };
@@ -29,7 +30,7 @@ struct FrameVariant {
     bool small;  // a BVH scene held whole in LDS (frame_small_scene)
     int nee;
     bool rgba;   // the resolve fused into the frame; it has no stats form
-    bool jitter = false;  // a jittered camera: the same kernels on hit_mode 0 (no camera-hit cache, no lists)
+    bool jitter = false;  // a per-path camera ray (cam_per_path): the same kernels on hit_mode 0 (no camera-hit cache, no lists)
     bool bsdf = false;    // the kBsdf kernels (a scene with material models): hit_mode 0, env 2, never `small`
 };
 
@@ -48,7 +49,7 @@ inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t firs
         v.bsdf = true;
         return v;
     }
-    if (p.cam_mode == kCamJitter) {  // one generic form per (stats, bvh, nee): no 8-wave, no channel-lane kernel
+    if (cam_per_path(p.cam_mode)) {  // one generic form per (stats, bvh, nee): no 8-wave, no channel-lane kernel
         v.env = 2;
         v.jitter = true;
         return v;
@@ -61,15 +62,15 @@ inline FrameVariant frame_variant(const PassParams& p, bool stats) {
     const bool rgba = p.rgba != nullptr;
     stats = stats && !rgba;
     const int nee = nee_variant(p);
-    if (p.bsdf) return FrameVariant{stats, p.nodes != nullptr, 2, false, nee ? kNeeAll : 0, rgba, p.cam_mode == kCamJitter, true};
+    if (p.bsdf) return FrameVariant{stats, p.nodes != nullptr, 2, false, nee ? kNeeAll : 0, rgba, cam_per_path(p.cam_mode), true};
     return FrameVariant{stats, p.nodes != nullptr, nee ? 2 : (p.env ? 1 : 0), frame_small_scene(p, stats), nee, rgba,
-                        p.cam_mode == kCamJitter};
+                        cam_per_path(p.cam_mode)};
 }
-// k_frame's hit_mode for a launch: a jittered camera's segment differs per frame, so its launches neither
+// k_frame's hit_mode for a launch: a jittered or lens camera's segment differs per frame, so its launches neither
 // store nor read the camera-hit cache and take no lists, whatever the ctx holds; nor do the launches of a
 // scene with material models (the kBsdf kernels trace every camera segment)
 inline uint32_t frame_hit_mode(const PassParams& p, bool cache_valid, bool lists) {
-    if (p.cam_mode == kCamJitter || p.bsdf) return 0u;
+    if (cam_per_path(p.cam_mode) || p.bsdf) return 0u;
     return !cache_valid ? 1u : (lists ? 3u : 2u);
 }
 
