@@ -157,7 +157,11 @@ typedef struct spt_stats {
     uint64_t tail_launches;
     uint64_t tail_bounce;                     /* bounces >= this run in k_trace_tail          */
     uint64_t fused;                           /* 1: extend+shade fused per bounce (shade_ms)  */
-    double persistent_ms;                     /* k_paths time (profiling)                     */
+    double persistent_ms;                     /* k_paths time (profiling). A split launch
+                                                 (view_split) counts as one launch, timed from the
+                                                 earlier of its halves' starts to the later of their
+                                                 ends; consecutive split launches overlap, so the sum
+                                                 over launches may exceed the wall time            */
     uint64_t persistent_launches;
     uint64_t schedule;                        /* SPT_SCHEDULE_* the last spt_render used      */
     uint64_t lane_slots;                      /* k_paths: 64 x wave tracing steps              */
@@ -189,6 +193,9 @@ typedef struct spt_stats {
     uint64_t flat_pair_second_passes;         /* wave-level second passes of the paired wall test (some
                                                  lane's ray starts outside the pair's slab: both walls
                                                  tested); counted by k_paths' counting forms only  */
+    uint64_t view_split;                      /* 1: the last k_paths launch ran as two launches over the
+                                                 two halves of the cached view, on two streams
+                                                 (spt_tuning.split_streams; same results)          */
 } spt_stats;
 
 typedef struct spt_ctx spt_ctx;
@@ -246,7 +253,9 @@ int spt_synchronize(spt_ctx* ctx);
 int spt_shard_pixels(const spt_ctx* ctx, uint64_t* n_pixels);
 /* Copy the shard's float RGBA accumulation (n_pixels * 4 floats, row-major over the shard's rows). */
 int spt_read_accum(spt_ctx* ctx, float* host_rgba);
-/* Device pointer / byte size of the accumulation buffer (valid until the next spt_configure). */
+/* Device pointer / byte size of the accumulation buffer (valid until the next spt_configure). Work the
+ * caller enqueues on the ctx's stream may read it between renders: from this call until the next
+ * spt_configure every split launch (spt_tuning.split_streams) waits for the ctx's stream first. */
 int spt_accum_device_ptr(spt_ctx* ctx, void** dptr, size_t* bytes);
 /* Stream-ordered device-to-device copy of the accumulation buffer (n_pixels * 16 bytes) to `dst`,
  * e.g. into a caller-owned tensor that a collective then gathers. */
@@ -568,6 +577,18 @@ typedef struct spt_tuning {
                                   compacted lists the launches then run over. 0: automatic, built behind
                                   the first persistent call after a change; -1: never (every launch
                                   computes bounce 0 itself)                                              */
+    int32_t split_streams;     /* flat scenes, k_paths over a cached view: each launch as two, over the two
+                                  halves of the view's lists, on two streams of the ctx's own, so that a
+                                  launch's blocks move in while the waves of the launch before it run out of
+                                  work (disjoint pixels need no order; each pixel's frames stay in stream
+                                  order within its half). The ctx stream waits on both halves before
+                                  spt_render returns, so work ordered behind the call sees the finished
+                                  render; the halves wait on the ctx stream only after another ctx call used
+                                  it, or on every call once spt_accum_device_ptr handed the sums out (the
+                                  caller's own readers on the stream are then ordered before the next
+                                  render's writes, as without the split). Decided once per spt_render call.
+                                  0: automatic (launches of at least 2^24 live-pixel frames); 1: whenever a view is
+                                  cached; -1: never                                                     */
 } spt_tuning;
 /* Applies to later calls; subqueues re-sizes at the next spt_configure. */
 int spt_set_tuning(spt_ctx* ctx, const spt_tuning* tuning);

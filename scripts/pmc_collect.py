@@ -1,6 +1,6 @@
 """Collate rocprofv3 PMC passes of one bench launch shape into profiles/pmc_r02.json.
 
-    python scripts/pmc_collect.py OUT.json LABEL DIR [DIR ...]
+    python scripts/pmc_collect.py [--halves KERNEL] OUT.json LABEL DIR [DIR ...]
 
 Each DIR holds one `rocprofv3 --pmc ... --kernel-trace --output-format csv` run of the SAME bench
 command (one pass per counter group: FETCH_SIZE | WRITE_SIZE | SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES
@@ -11,6 +11,11 @@ dispatches (the warm-up and timed launches of one shape) of:
   valu_insts, salu_insts, waves                                (SQ counters, summed over the chip)
   duration_ns   = End_Timestamp - Start_Timestamp of the dispatch (median; duration_mean_ns: the mean)
   clock_ghz     = GRBM_GUI_ACTIVE / 8 XCDs / duration           (MI355X_MICROARCH.md, DVFS paragraph)
+--halves KERNEL: the launches of kernels whose name contains KERNEL run as two dispatches, one per half of a
+split view (spt_tuning.split_streams), and bench.py counts such a pair as ONE launch: their record is then the
+pair's — counters, bytes and durations are twice the per-dispatch medians (the two halves do the same work to
+within a chunk; counter collection runs dispatches one at a time, so the duration is that of the halves run one
+after the other, not overlapped) — with `dispatches_per_launch: 2` beside them; the clock is a ratio and stays.
 The record is keyed by LABEL (bench.py pmc_label: scene, size, bounces, ranks, frames per launch) and
 stamped with the kernel-source hash bench.py checks, so it never describes another kernel or shape.
 """
@@ -35,7 +40,11 @@ def kernel_source_hash() -> str:  # the same hash as bench.py's
 
 
 def main():
-    out, label, dirs = sys.argv[1], sys.argv[2], sys.argv[3:]
+    argv = sys.argv[1:]
+    halves = None
+    if argv and argv[0] == "--halves":
+        halves, argv = argv[1], argv[2:]
+    out, label, dirs = argv[0], argv[1], argv[2:]
     vals = collections.defaultdict(lambda: collections.defaultdict(list))
     dur = collections.defaultdict(list)
     for d in dirs:
@@ -64,6 +73,12 @@ def main():
             rec["thread_cycles_valu"] = med.get("SQ_THREAD_CYCLES_VALU")
         if "GRBM_GUI_ACTIVE" in med and rec["duration_ns"]:
             rec["clock_ghz"] = round(med["GRBM_GUI_ACTIVE"] / 8.0 / rec["duration_ns"], 4)
+        if halves and halves in name:  # a launch is two dispatches: the record is the launch's
+            for k in ("traffic_bytes", "fetch_bytes", "write_bytes", "duration_ns", "duration_mean_ns", "valu_insts",
+                      "salu_insts", "waves", "thread_cycles_valu"):
+                if rec.get(k) is not None:
+                    rec[k] = 2.0 * rec[k]
+            rec["dispatches_per_launch"] = 2
         kernels[name] = rec
     table = json.load(open(out)) if os.path.exists(out) else {}
     table[label] = {"kernel_source": kernel_source_hash(), "kernels": kernels}

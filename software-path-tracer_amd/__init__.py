@@ -156,6 +156,7 @@ class SptStats(ctypes.Structure):
         ("view_live_pixels", ctypes.c_uint64),
         ("flat_pairs", ctypes.c_uint64),
         ("flat_pair_second_passes", ctypes.c_uint64),
+        ("view_split", ctypes.c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -201,6 +202,7 @@ class SptTuning(ctypes.Structure):
         ("bvh_bins", ctypes.c_uint32),
         ("specialize", ctypes.c_int32),
         ("view_cache", ctypes.c_int32),
+        ("split_streams", ctypes.c_int32),
     ]
 
     def __init__(self, **kw):

@@ -63,6 +63,23 @@ struct EventPair {
     int kind = 0;  // 0 extend, 1 shade, 2 other, 3 tail, 4 persistent
     uint32_t bounce = 0;
     uint32_t launches = 1;  // kind 4: the launches between a and b (> 1 for a SPT_PROFILE_SPAN pair)
+    // kind 4, a split launch (ViewHalf): the second half's pair, on its stream; the launch's time is
+    // (latest end - earliest start) of the two pairs
+    hipEvent_t a2 = nullptr, b2 = nullptr;
+};
+
+// One half of a split view (spt_launch_plan.h make_view_split): the k_paths launches over it run on a
+// stream of their own, with everything a launch writes besides its pixels' sums kept per half.
+struct ViewHalf {
+    hipStream_t stream = nullptr;  // non-blocking, created with the ctx
+    hipEvent_t done = nullptr;     // behind the half's last launch of a call: the ctx stream waits on it (the join)
+    uint16_t* cost = nullptr;      // the half's first-tier chunk costs and order (PassParams), [pixels / 2 + 64]
+    uint32_t* order = nullptr;
+    uint64_t order_key = 0;        // 0: no order. Cleared when the view's lists are built (every clear of the ctx's
+                                   // chunk_order_key comes with view_valid = false, so the lists are rebuilt before
+                                   // a half launches again), with the buffers, and by a failed launch
+    uint32_t* work = nullptr;      // 2 sets of kWorkWords of its own (k_paths zeroes work_next in stream order:
+    uint32_t work_parity = 0;      // a set is never shared across streams)
 };
 
 }  // namespace
@@ -70,7 +87,22 @@ struct EventPair {
 struct spt_ctx {
     int device = -1;
     hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    // The stream the caller's work is ordered on. Everything but the split launches' join reaches it through
+    // on_stream(), which marks it dirty for the next split launch's fork (stream_dirty below).
+    hipStream_t user_stream = nullptr;
+    // Split k_paths launches (spt_tuning.split_streams): a view's lists in two halves on two streams.
+    ViewHalf half[2];
+    hipEvent_t fork_ev = nullptr;   // on the ctx stream: what the half streams wait on after anything else ran there
+    // Set by every use of the ctx stream (on_stream) — every entry point that enqueues on it, drains it before
+    // changing what a launch reads, or replaces it — and cleared by a split launch's fork: two split renders
+    // with nothing between them fork without a wait, so call k+1's halves overlap call k's.
+    bool stream_dirty = true;
+    int32_t split_streams = 0;      // spt_tuning: -1 never, 0 automatic, 1 always when a view is valid
+    bool last_view_split = false;   // the last persistent launch was split
+    // spt_accum_device_ptr handed the sums' address out (until the next spt_configure frees it): the caller may
+    // read them with work of its own on its stream that no ctx call sees, so every split launch forks, as if
+    // the stream were always dirty (it then waits for that work; the overlap across calls is given up)
+    bool accum_shared = false;
     std::string err;
     uint32_t cu_count = 256;
 
@@ -248,6 +280,13 @@ struct spt_ctx {
 
 namespace {
 
+// The ctx stream, for anything that is about to enqueue on it, wait for it or replace it: the one place
+// that marks it dirty (spt_ctx::stream_dirty). Only the split launches' join takes user_stream directly.
+hipStream_t& on_stream(spt_ctx* c) {
+    c->stream_dirty = true;
+    return c->user_stream;
+}
+
 int fail(spt_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
@@ -283,6 +322,11 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->chunk_cost);
     free_dev(c->chunk_order);
     c->chunk_order_key = 0;
+    for (ViewHalf& h : c->half) {
+        free_dev(h.cost);
+        free_dev(h.order);
+        h.order_key = 0;
+    }
     free_dev(c->view_live);
     free_dev(c->view_const);
     free_dev(c->view_counts);
@@ -382,9 +426,21 @@ void free_scene(spt_ctx* c) {
 int flush_events(spt_ctx* c) {
     if (c->pending.empty()) return SPT_OK;
     SPT_HIP(c, hipEventSynchronize(c->pending.back().b));
+    if (c->pending.back().b2) SPT_HIP(c, hipEventSynchronize(c->pending.back().b2));
     for (auto& e : c->pending) {
         float ms = 0.0f;
-        SPT_HIP(c, hipEventElapsedTime(&ms, e.a, e.b));
+        if (e.a2) {
+            // a split launch: from the earlier of the halves' starts to the later of their ends
+            // (hipEventElapsedTime works between events of different streams)
+            float lead = 0.0f, end_a = 0.0f, end_b = 0.0f;
+            SPT_HIP(c, hipEventElapsedTime(&lead, e.a, e.a2));
+            const hipEvent_t start = lead >= 0.0f ? e.a : e.a2;
+            SPT_HIP(c, hipEventElapsedTime(&end_a, start, e.b));
+            SPT_HIP(c, hipEventElapsedTime(&end_b, start, e.b2));
+            ms = std::max(end_a, end_b);
+        } else {
+            SPT_HIP(c, hipEventElapsedTime(&ms, e.a, e.b));
+        }
         if (e.kind == 0) {
             c->ext_ms += ms;
             c->ext_ms_b[e.bounce] += ms;
@@ -402,13 +458,21 @@ int flush_events(spt_ctx* c) {
         } else {
             c->other_ms += ms;
         }
+        if (e.a2) {  // back to the pool as the two pairs they were
+            EventPair second;
+            second.a = e.a2;
+            second.b = e.b2;
+            c->free_events.push_back(second);
+            e.a2 = e.b2 = nullptr;
+        }
         c->free_events.push_back(e);
     }
     c->pending.clear();
     return SPT_OK;
 }
 
-int begin_event(spt_ctx* c, EventPair& out, int kind, uint32_t bounce = 0) {
+// a pair from the pool, nothing recorded yet
+int take_events(spt_ctx* c, EventPair& out, int kind, uint32_t bounce = 0) {
     if (c->free_events.empty()) {
         EventPair e;
         SPT_HIP(c, hipEventCreate(&e.a));
@@ -420,12 +484,17 @@ int begin_event(spt_ctx* c, EventPair& out, int kind, uint32_t bounce = 0) {
     out.kind = kind;
     out.bounce = bounce;
     out.launches = 1;  // (a pooled pair may have been a span)
-    SPT_HIP(c, hipEventRecord(out.a, c->stream));
+    return SPT_OK;
+}
+
+int begin_event(spt_ctx* c, EventPair& out, int kind, uint32_t bounce = 0) {
+    if (take_events(c, out, kind, bounce) != SPT_OK) return SPT_ERR_HIP;
+    SPT_HIP(c, hipEventRecord(out.a, on_stream(c)));
     return SPT_OK;
 }
 
 int end_event(spt_ctx* c, EventPair& e) {
-    SPT_HIP(c, hipEventRecord(e.b, c->stream));
+    SPT_HIP(c, hipEventRecord(e.b, on_stream(c)));
     c->pending.push_back(e);
     if (c->pending.size() >= 4096) return flush_events(c);
     return SPT_OK;
@@ -535,7 +604,7 @@ static CameraLens lens_scalars(const spt_camera& cam, const spt_lens& lens) {
 // lens; a launch in flight reads the old one, so the stream is drained first
 static int write_camera_record(spt_ctx* c) {
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     if (!c->d_camera) SPT_HIP(c, hipMalloc(&c->d_camera, 4 * sizeof(float4)));
     const spt_camera& cam = c->camera;
     const CameraLens l = c->has_lens ? lens_scalars(cam, c->lens) : CameraLens{0.0f, 0.0f, 0.0f};
@@ -688,14 +757,21 @@ int spt_create(spt_ctx** out, int device_id) {
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&c->counts, sizeof(uint32_t) * 2 * (kMaxBounces + 1) * c->n_sub) != hipSuccess ||
         hipMalloc(&c->totals, sizeof(unsigned long long) * kTotals) != hipSuccess ||
-        hipMalloc(&c->work, sizeof(uint32_t) * 2 * kWorkWords) != hipSuccess ||
-        hipMemset(c->work, 0, sizeof(uint32_t) * 2 * kWorkWords) != hipSuccess ||
+        // (work heads: the ctx stream's two sets, then two per view half)
+        hipMalloc(&c->work, sizeof(uint32_t) * 6 * kWorkWords) != hipSuccess ||
+        hipMemset(c->work, 0, sizeof(uint32_t) * 6 * kWorkWords) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->half[0].stream, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->half[1].stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->half[0].done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->half[1].done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) != hipSuccess ||
         hipMemset(c->totals, 0, sizeof(unsigned long long) * kTotals) != hipSuccess ||
         hipMemset(c->counts, 0, sizeof(uint32_t) * 2 * (kMaxBounces + 1) * c->n_sub) != hipSuccess) {
         spt_destroy(c);
         return SPT_ERR_HIP;
     }
-    c->stream = c->own_stream;
+    for (uint32_t h = 0; h < 2u; ++h) c->half[h].work = c->work + (2u + 2u * h) * kWorkWords;
+    on_stream(c) = c->own_stream;
     *out = c;
     return SPT_OK;
 }
@@ -703,12 +779,16 @@ int spt_create(spt_ctx** out, int device_id) {
 void spt_destroy(spt_ctx* c) {
     if (!c) return;
     if (c->device >= 0) (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (on_stream(c)) (void)hipStreamSynchronize(on_stream(c));
+    for (ViewHalf& h : c->half)  // (joined into the ctx stream; a failed call may have left one unjoined)
+        if (h.stream) (void)hipStreamSynchronize(h.stream);
     for (auto& e : c->pending) c->free_events.push_back(e);
     if (c->span_open) c->free_events.push_back(c->span_ev);
     for (auto& e : c->free_events) {
         if (e.a) (void)hipEventDestroy(e.a);
         if (e.b) (void)hipEventDestroy(e.b);
+        if (e.a2) (void)hipEventDestroy(e.a2);
+        if (e.b2) (void)hipEventDestroy(e.b2);
     }
     free_buffers(c);
     free_scene(c);
@@ -719,6 +799,11 @@ void spt_destroy(spt_ctx* c) {
     free_dev(c->d_camera);
     free_dev(c->work);
     if (c->out_host) (void)hipHostUnregister(c->out_host);
+    for (ViewHalf& h : c->half) {
+        if (h.done) (void)hipEventDestroy(h.done);
+        if (h.stream) (void)hipStreamDestroy(h.stream);
+    }
+    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -728,8 +813,8 @@ const char* spt_last_error(const spt_ctx* c) { return c ? c->err.c_str() : "null
 int spt_set_stream(spt_ctx* c, void* hip_stream) {
     if (!c) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    on_stream(c) = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     return SPT_OK;
 }
 
@@ -788,7 +873,7 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     if (stack_need > kBvhStackEntries)
         return fail(c, SPT_ERR_CAPACITY, "spt_set_scene: the BVH needs " + std::to_string(stack_need) +
                                              " traversal stack entries (at most " + std::to_string(kBvhStackEntries) + ")");
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     free_scene(c);
     uint32_t flat_ends = 0, flat_rect = 0, flat_pairs = 0;
     if (n_prims && n_prims <= kFlatSceneMax) {  // flat: the originals, then the kind-major copy
@@ -928,7 +1013,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     const void* node_data = dtree.bytes.data();
     const uint64_t node_bytes = dtree.bytes.size();
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     // Every allocation the edit needs comes first — a grown node array (the 4-wide collapse opens the
     // largest children first, so refitted areas can change its node count), the emitter array, deeper
     // traversal stacks — and only once all of them have succeeded is anything copied or swapped in: a
@@ -1009,7 +1094,7 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
         return fail(c, SPT_ERR_INVALID, "shard_rank must be < shard_count");
     if ((uint64_t)cfg->width * cfg->height >= (1ull << 31)) return fail(c, SPT_ERR_INVALID, "image too large");
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     const uint32_t rows = cfg->shard_rank < cfg->height
                               ? (cfg->height - cfg->shard_rank + cfg->shard_count - 1) / cfg->shard_count
                               : 0u;
@@ -1024,6 +1109,7 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
     const uint32_t cap = sub_capacity((uint64_t)fpp * pixels, c->n_sub);
     const bool realloc = !c->configured || pixels != c->pixels || fpp != c->frames_per_pass || c->sub_alloc != c->n_sub;
     c->cfg = *cfg;
+    c->accum_shared = false;  // (a pointer handed out before is no longer valid: spt.h)
     c->rows = rows;
     c->pixels = pixels;
     c->frames_per_pass = fpp;
@@ -1075,7 +1161,7 @@ int spt_reset(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_reset before spt_configure");
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemsetAsync(c->accum, 0, sizeof(float4) * std::max<size_t>(c->pixels, 1), c->stream));
+    SPT_HIP(c, hipMemsetAsync(c->accum, 0, sizeof(float4) * std::max<size_t>(c->pixels, 1), on_stream(c)));
     c->frame_count = 0;
     return SPT_OK;
 }
@@ -1105,11 +1191,175 @@ static int build_view_lists(spt_ctx* c, const PassParams& p) {
             return SPT_OK;
         }
     }
-    launch_view_lists(p, c->view_live, c->view_const, c->view_counts, c->view_counts + 2, c->stream);
+    launch_view_lists(p, c->view_live, c->view_const, c->view_counts, c->view_counts + 2, on_stream(c));
     SPT_HIP(c, hipGetLastError());
-    SPT_HIP(c, hipMemcpyAsync(c->view_n, c->view_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipMemcpyAsync(c->view_n, c->view_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     c->view_valid = true;
+    for (ViewHalf& h : c->half) h.order_key = 0;  // (the halves' chunk orders were the old lists')
+    return SPT_OK;
+}
+
+// ---- split launches: a view's lists in two halves on two streams (spt_launch_plan.h make_view_split) ----
+// Consecutive k_paths launches in one stream leave wave slots idle: when launch k's waves run out of
+// chunks, launch k+1 is enqueued but stream order keeps it out until the last wave of k has left. A pixel's
+// frames must be added in order, but two launches over disjoint pixels need no order at all: half A's
+// launches follow each other on half[0].stream, half B's on half[1].stream, and nothing waits across the
+// halves, so each launch's blocks move in as the waves of the launch before it leave.
+// Ordering against everything else is by events, never by a host wait:
+//   fork  a split launch that finds the ctx stream dirty (something ran on it, or drained it to change what
+//         a launch reads, since the last fork: on_stream) makes both half streams wait on it first;
+//   join  a call that launched halves makes the ctx stream wait on them before it returns, so whatever the
+//         caller orders behind the call on its stream sees the finished render. The wait sits in the ctx
+//         stream and does not hold the half streams back.
+// Whether a call's launches are split is decided once per call (spt_launch_plan.h split_call_wanted), never
+// per launch: a call never goes from split launches back to a whole one.
+
+// The halves' cost and order buffers, allocated by the first split launch of a configuration: a half holds at
+// most half the live list plus half a chunk, and its first tier at most a chunk per record. false: no memory
+// (the launch runs unsplit).
+static bool half_buffers(spt_ctx* c) {
+    const size_t n = (size_t)c->pixels / 2u + 64u;
+    for (ViewHalf& h : c->half) {
+        if (h.cost && h.order) continue;
+        if (hipMalloc(&h.cost, sizeof(uint16_t) * n) != hipSuccess || hipMalloc(&h.order, sizeof(uint32_t) * n) != hipSuccess) {
+            (void)hipGetLastError();
+            free_dev(h.cost);
+            free_dev(h.order);
+            return false;
+        }
+        h.order_key = 0;
+    }
+    return true;
+}
+
+// One persistent launch as two: `whole` is the view's lists, p the launch's parameters (its work heads and
+// chunk buffers are replaced by each half's own). launched[h]: half h got a launch (an empty half gets none).
+static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, bool launched[2]) {
+    const ViewSplit sp = make_view_split(whole.n_live, whole.n_const, 1u << kMaxChunkShift);
+    EventPair span_ev;
+    if (c->profiling && c->span && begin_persistent(c, span_ev) != SPT_OK) return SPT_ERR_HIP;  // (the span's begin: ctx stream)
+    if (c->stream_dirty || c->accum_shared) {  // fork
+        SPT_HIP(c, hipEventRecord(c->fork_ev, c->user_stream));
+        for (ViewHalf& h : c->half) SPT_HIP(c, hipStreamWaitEvent(h.stream, c->fork_ev, 0));
+        c->stream_dirty = false;
+    }
+    // No small tail tiers under the split (unless spt_tuning.chunks_per_wave asks for them): the tiers square
+    // off a launch's end at two and four times a 32-pixel chunk's drain per pixel, and here the other half's
+    // next launch fills that end anyway. Measured: C2 +1.5 %, the N = 8 shard +2.3 % over
+    // the split with both tiers. The live records left over by the first tier still go to the last tier.
+    if (!c->chunks_per_wave) p.chunks_per_wave = 0u;
+    const bool timed = c->profiling && !c->span;
+    EventPair ev[2];
+    int n_ev = 0;
+    int rc = SPT_OK;
+    for (uint32_t h = 0; h < 2u && rc == SPT_OK; ++h) {
+        if (view_half_empty(sp, h)) continue;
+        ViewHalf& vh = c->half[h];
+        const ViewPlan view{whole.live + 3u * (size_t)sp.live_at[h], whole.constant + sp.const_at[h],
+                            sp.live_at[h + 1] - sp.live_at[h], sp.const_at[h + 1] - sp.const_at[h], 0u};
+        p.work = vh.work + vh.work_parity * kWorkWords;
+        p.work_next = vh.work + (vh.work_parity ^ 1u) * kWorkWords;
+        vh.work_parity ^= 1u;
+        p.chunk_cost = vh.cost;
+        p.chunk_order = vh.order;
+        p.chunk_order_key = &vh.order_key;
+        if (timed) {
+            if (take_events(c, ev[n_ev], 4) != SPT_OK) return SPT_ERR_HIP;
+            ++n_ev;
+            if (hipEventRecord(ev[n_ev - 1].a, vh.stream) != hipSuccess) rc = fail(c, SPT_ERR_HIP, "k_paths (split): hipEventRecord");
+        }
+        c->last_specialized = launch_paths(p, c->counters, vh.stream, &view, h + 1u);
+        launched[h] = true;
+        // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            vh.order_key = 0;
+            rc = fail(c, SPT_ERR_HIP, std::string("k_paths (split): ") + hipGetErrorString(le));
+        }
+        if (timed && hipEventRecord(ev[n_ev - 1].b, vh.stream) != hipSuccess) rc = fail(c, SPT_ERR_HIP, "k_paths (split): hipEventRecord");
+    }
+    c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
+    if (rc != SPT_OK) {
+        for (int i = 0; i < n_ev; ++i) c->free_events.push_back(ev[i]);
+        for (ViewHalf& h : c->half) h.order_key = 0;
+        return rc;
+    }
+    if (n_ev) {  // one persistent launch: the two pairs as one record
+        if (n_ev == 2) {
+            ev[0].a2 = ev[1].a;
+            ev[0].b2 = ev[1].b;
+        }
+        c->pending.push_back(ev[0]);
+        if (c->pending.size() >= 4096) return flush_events(c);
+    }
+    return SPT_OK;
+}
+
+// the join: the ctx stream waits on the halves launched since the last join (not through on_stream: the wait
+// orders nothing a later fork would have to wait for). Every half is tried even if one fails.
+static int join_halves(spt_ctx* c, bool launched[2]) {
+    int rc = SPT_OK;
+    for (uint32_t h = 0; h < 2u; ++h) {
+        if (!launched[h]) continue;
+        launched[h] = false;
+        hipError_t e = hipEventRecord(c->half[h].done, c->half[h].stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->user_stream, c->half[h].done, 0);
+        if (e != hipSuccess) rc = fail(c, SPT_ERR_HIP, std::string("k_paths (split) join: ") + hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// The persistent schedule's launches of one spt_render call: one per <= kPersistentMaxFrames frames, every
+// path of the call, accumulated in frame order in-kernel (fewer, longer launches amortize each launch's
+// tail). launched[]: the view halves with launches the ctx stream has not been joined with yet; whatever this
+// returns, the caller joins them.
+static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, uint32_t n_frames, bool launched[2]) {
+    uint32_t done = 0;
+    while (done < n_frames) {
+        const uint32_t f = std::min(kPersistentMaxFrames, n_frames - done);
+        p.first_frame = first_frame + done;
+        p.n_frames = f;
+        p.n_paths = f * c->pixels;
+        // a flat scene's view lists, once they are built (below): the launch runs over them
+        const bool view_scene = c->view_cache >= 0 && view_lists_scene(p);
+        const ViewPlan view{c->view_live, c->view_const, c->view_n[0], c->view_n[1], 0u};
+        const bool view_on = view_scene && c->view_valid;
+        // ... in two halves on two streams (the first persistent launch of a view stays whole on the ctx
+        // stream: it builds the lists). Decided for the call, not for the launch: the same answer for every
+        // launch of the call once the lists exist.
+        if (view_on && split_call_wanted(c->split_streams, c->view_n[0], n_frames, kPersistentMaxFrames) && half_buffers(c)) {
+            c->last_view_cached = c->last_view_split = true;
+            const int rc = launch_paths_split(c, p, view, launched);
+            if (rc != SPT_OK) return rc;
+            done += f;
+            c->passes++;
+            continue;
+        }
+        // a whole launch on the ctx stream: behind any halves still in flight (they write the same pixels)
+        if (join_halves(c, launched) != SPT_OK) return SPT_ERR_HIP;
+        c->last_view_split = false;
+        EventPair ev;
+        if (begin_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
+        next_work_set(c, p);
+        p.chunk_cost = c->chunk_cost;
+        p.chunk_order = c->chunk_order;
+        p.chunk_order_key = &c->chunk_order_key;
+        c->last_specialized = launch_paths(p, c->counters, on_stream(c), view_on ? &view : nullptr);
+        c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
+        c->last_view_cached = view_on;
+        // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) c->chunk_order_key = 0;
+        if (end_persistent(c, ev) != SPT_OK) {
+            c->chunk_order_key = 0;
+            return SPT_ERR_HIP;
+        }
+        SPT_HIP(c, le);
+        if (view_scene && !c->view_valid && !c->view_no_memory && build_view_lists(c, p) != SPT_OK) return SPT_ERR_HIP;
+        done += f;
+        c->passes++;
+    }
     return SPT_OK;
 }
 
@@ -1126,39 +1376,16 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
     PassParams p = base_params(c);
     uint32_t done = 0;
     if (schedule_persistent(c, n_frames)) {
-        // one launch per <= kPersistentMaxFrames frames: every path of the call, accumulated in frame
-        // order in-kernel (fewer, longer launches amortize each launch's tail)
         c->last_schedule = SPT_SCHEDULE_PERSISTENT;
-        while (done < n_frames) {
-            const uint32_t f = std::min(kPersistentMaxFrames, n_frames - done);
-            p.first_frame = first_frame + done;
-            p.n_frames = f;
-            p.n_paths = f * c->pixels;
-            EventPair ev;
-            if (begin_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
-            next_work_set(c, p);
-            p.chunk_cost = c->chunk_cost;
-            p.chunk_order = c->chunk_order;
-            p.chunk_order_key = &c->chunk_order_key;
-            // a flat scene's view lists, once they are built (below): the launch runs over them
-            const bool view_scene = c->view_cache >= 0 && view_lists_scene(p);
-            const ViewPlan view{c->view_live, c->view_const, c->view_n[0], c->view_n[1], 0u};
-            const bool view_on = view_scene && c->view_valid;
-            c->last_specialized = launch_paths(p, c->counters, c->stream, view_on ? &view : nullptr);
-            c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
-            c->last_view_cached = view_on;
-            // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) c->chunk_order_key = 0;
-            if (end_persistent(c, ev) != SPT_OK) {
-                c->chunk_order_key = 0;
-                return SPT_ERR_HIP;
-            }
-            SPT_HIP(c, le);
-            if (view_scene && !c->view_valid && !c->view_no_memory && build_view_lists(c, p) != SPT_OK) return SPT_ERR_HIP;
-            done += f;
-            c->passes++;
+        bool launched[2] = {false, false};
+        const int rc = render_persistent(c, p, first_frame, n_frames, launched);
+        const std::string err = c->err;
+        const int joined = join_halves(c, launched);  // (also behind a failed launch: the ctx stream is never left unjoined)
+        if (rc != SPT_OK) {
+            c->err = err;  // (the launch's message, not the join's)
+            return rc;
         }
+        if (joined != SPT_OK) return joined;
         c->frames += n_frames;
         c->paths += (uint64_t)n_frames * c->pixels;
         c->frame_count += n_frames;
@@ -1187,19 +1414,19 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
                 p.rgba_exposure = c->fuse_exposure;
                 c->fused = true;
             }
-            c->last_specialized = launch_frame(p, c->counters, c->stream);
+            c->last_specialized = launch_frame(p, c->counters, on_stream(c));
             c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
             if (end_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
             SPT_HIP(c, hipGetLastError());
             if (!c->hit_cache_valid) c->frame_lists = false;
             if (!jitter && !c->hit_cache_valid && frame_lists_scene(p, c->counters)) {  // compacted once (stream order)
-                launch_hit_lists(p, c->list_counts + 2, c->stream);
+                launch_hit_lists(p, c->list_counts + 2, on_stream(c));
                 SPT_HIP(c, hipGetLastError());
                 // the live count sizes the next launches' grids: read back once per scene / configuration
                 // (this waits for the frame just launched, ~0.1 ms, on the first frame after a change only)
                 SPT_HIP(c, hipMemcpyAsync(&c->live_pixels, c->list_counts, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                          c->stream));
-                SPT_HIP(c, hipStreamSynchronize(c->stream));
+                                          on_stream(c)));
+                SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
                 c->frame_lists = c->pixels - c->live_pixels >= c->pixels / kFrameListsMinSkyDiv;
             }
             if (!jitter) c->hit_cache_valid = true;  // (stream order: the next launch reads what this one stored)
@@ -1219,35 +1446,35 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
         p.n_paths = f * c->pixels;
         EventPair ev;
         if (c->cfg.max_bounces == 0) {  // no segment traced: every path's radiance is 0
-            SPT_HIP(c, hipMemsetAsync(c->radiance, 0, sizeof(float4) * (size_t)p.n_paths, c->stream));
-            SPT_HIP(c, hipMemsetAsync(c->counts, 0, sizeof(uint32_t) * 2 * (kMaxBounces + 1) * c->n_sub, c->stream));
+            SPT_HIP(c, hipMemsetAsync(c->radiance, 0, sizeof(float4) * (size_t)p.n_paths, on_stream(c)));
+            SPT_HIP(c, hipMemsetAsync(c->counts, 0, sizeof(uint32_t) * 2 * (kMaxBounces + 1) * c->n_sub, on_stream(c)));
         }
         const uint32_t wave_bounces = std::min(c->cfg.max_bounces, schedule_tail(c));
         const bool fused = schedule_fused(c);
         for (uint32_t b = 0; b < wave_bounces; ++b) {
             if (fused) {  // extend + shade in one launch (timed as "shade")
                 if (c->profiling && !c->span && begin_event(c, ev, 1, b) != SPT_OK) return SPT_ERR_HIP;
-                launch_bounce(p, b, c->stream);
+                launch_bounce(p, b, on_stream(c));
                 if (c->profiling && !c->span && end_event(c, ev) != SPT_OK) return SPT_ERR_HIP;
                 continue;
             }
             if (c->profiling && !c->span && begin_event(c, ev, 0, b) != SPT_OK) return SPT_ERR_HIP;
             if ((c->cfg.flags & SPT_FLAG_SORTED_RAYS) && b > 0 && c->n_nodes && c->ray_perm)
-                launch_extend_sorted(p, b, c->stream);  // the binning is timed with the extend it serves
+                launch_extend_sorted(p, b, on_stream(c));  // the binning is timed with the extend it serves
             else
-                launch_extend(p, b, c->stream);
+                launch_extend(p, b, on_stream(c));
             if (c->profiling && !c->span && end_event(c, ev) != SPT_OK) return SPT_ERR_HIP;
             if (c->profiling && !c->span && begin_event(c, ev, 1, b) != SPT_OK) return SPT_ERR_HIP;
-            launch_shade(p, b, c->stream);
+            launch_shade(p, b, on_stream(c));
             if (c->profiling && !c->span && end_event(c, ev) != SPT_OK) return SPT_ERR_HIP;
         }
         if (wave_bounces < c->cfg.max_bounces) {  // thinned queues: finish every path in one launch
             if (c->profiling && !c->span && begin_event(c, ev, 3, wave_bounces) != SPT_OK) return SPT_ERR_HIP;
-            launch_trace_tail(p, wave_bounces, c->stream);
+            launch_trace_tail(p, wave_bounces, on_stream(c));
             if (c->profiling && !c->span && end_event(c, ev) != SPT_OK) return SPT_ERR_HIP;
         }
         if (c->profiling && !c->span && begin_event(c, ev, 2) != SPT_OK) return SPT_ERR_HIP;
-        launch_accumulate(p, c->stream);
+        launch_accumulate(p, on_stream(c));
         if (c->profiling && !c->span && end_event(c, ev) != SPT_OK) return SPT_ERR_HIP;
         SPT_HIP(c, hipGetLastError());
         done += f;
@@ -1261,7 +1488,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
 
 // The caller waits for the frame (spt_synchronize, the resolves)
 // (polling an event recorded after the frame instead measured the same)
-static hipError_t wait_frame(spt_ctx* c) { return hipStreamSynchronize(c->stream); }
+static hipError_t wait_frame(spt_ctx* c) { return hipStreamSynchronize(on_stream(c)); }
 
 int spt_synchronize(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
@@ -1282,8 +1509,8 @@ int spt_read_accum(spt_ctx* c, float* host_rgba) {
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pixels == 0) return SPT_OK;
-    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, c->stream));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     return SPT_OK;
 }
 
@@ -1292,6 +1519,7 @@ int spt_accum_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
     *dptr = c->accum;
     *bytes = sizeof(float4) * (size_t)c->pixels;
+    c->accum_shared = true;
     return SPT_OK;
 }
 
@@ -1300,7 +1528,7 @@ int spt_copy_accum_device(spt_ctx* c, void* dst) {
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pixels == 0) return SPT_OK;
-    SPT_HIP(c, hipMemcpyAsync(dst, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(dst, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, on_stream(c)));
     return SPT_OK;
 }
 
@@ -1316,12 +1544,12 @@ int spt_resolve_rgba8_exposure(spt_ctx* c, uint32_t frame_count, float exposure,
     if (c->pixels == 0) return SPT_OK;
     if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
         // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, (uint32_t*)c->out_dev, c->stream);
+        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, (uint32_t*)c->out_dev, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     } else {
-        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, c->resolved, c->stream);
+        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, c->resolved, on_stream(c));
         SPT_HIP(c, hipGetLastError());
-        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, c->stream));
+        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
     }
     SPT_HIP(c, wait_frame(c));
     return SPT_OK;
@@ -1354,7 +1582,7 @@ int spt_register_host_output(spt_ctx* c, void* host_out, size_t bytes) {
     if ((host_out == nullptr) != (bytes == 0)) return fail(c, SPT_ERR_INVALID, "host output: pointer and size disagree");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->out_host) {
-        SPT_HIP(c, hipStreamSynchronize(c->stream));  // no resolve may still be writing it
+        SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // no resolve may still be writing it
         const hipError_t e = hipHostUnregister(c->out_host);
         c->out_host = c->out_dev = nullptr;
         c->out_bytes = 0;
@@ -1380,7 +1608,7 @@ int spt_assemble_rows(spt_ctx* c, const void* gathered, void* out) {
     SPT_HIP(c, hipSetDevice(c->device));
     const uint32_t world = c->cfg.shard_count;
     const uint32_t rows_max = (c->cfg.height + world - 1) / world;
-    launch_assemble_rows((const float4*)gathered, (float4*)out, c->cfg.width, c->cfg.height, world, rows_max, c->stream);
+    launch_assemble_rows((const float4*)gathered, (float4*)out, c->cfg.width, c->cfg.height, world, rows_max, on_stream(c));
     SPT_HIP(c, hipGetLastError());
     return SPT_OK;
 }
@@ -1390,7 +1618,7 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
     if (rgba && (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 28)))
         return fail(c, SPT_ERR_INVALID, "environment map: bad size");
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     free_dev(c->d_env);
     c->env_w = c->env_h = 0;
     if (rgba) {
@@ -1484,7 +1712,7 @@ int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32
             if (const char* msg = model_error(models[i])) return fail(c, SPT_ERR_INVALID, msg);
     }
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));  // (a launch in flight reads the old words)
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (a launch in flight reads the old words)
     const std::vector<spt_material_model> old = c->h_models;
     if (models) c->h_models.assign(models, models + n);
     else c->h_models.clear();
@@ -1556,7 +1784,7 @@ int ensure_features(spt_ctx* c) {
         c->feat_b = b;
         c->feat_albedo = alb;
     }
-    launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, c->stream);
+    launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, on_stream(c));
     SPT_HIP(c, hipGetLastError());
     c->feat_valid = true;
     return SPT_OK;
@@ -1573,10 +1801,10 @@ int spt_read_features(spt_ctx* c, float* feat_a, float* feat_b, float* albedo) {
     const int rc = ensure_features(c);
     if (rc != SPT_OK || c->pixels == 0) return rc;
     const size_t bytes = sizeof(float4) * c->pixels;
-    if (feat_a) SPT_HIP(c, hipMemcpyAsync(feat_a, c->feat_a, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (feat_b) SPT_HIP(c, hipMemcpyAsync(feat_b, c->feat_b, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (albedo) SPT_HIP(c, hipMemcpyAsync(albedo, c->feat_albedo, bytes, hipMemcpyDeviceToHost, c->stream));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (feat_a) SPT_HIP(c, hipMemcpyAsync(feat_a, c->feat_a, bytes, hipMemcpyDeviceToHost, on_stream(c)));
+    if (feat_b) SPT_HIP(c, hipMemcpyAsync(feat_b, c->feat_b, bytes, hipMemcpyDeviceToHost, on_stream(c)));
+    if (albedo) SPT_HIP(c, hipMemcpyAsync(albedo, c->feat_albedo, bytes, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     return SPT_OK;
 }
 
@@ -1626,7 +1854,7 @@ int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* para
         const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
         const float4* in = l == 0 ? c->accum : c->dn[(l - 1u) & 1u];
         launch_atrous(forced >= 0 ? forced : atrous_form_of_step(lv.step), in, l == 0 ? (float)frame_count : 0.0f,
-                      c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, c->stream);
+                      c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     }
     c->dn_result = (int)((p.levels - 1u) & 1u);
@@ -1645,8 +1873,8 @@ int spt_read_denoised(spt_ctx* c, float* host_rgba) {
     if (!c || !host_rgba) return SPT_ERR_INVALID;
     if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->dn[c->dn_result], sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, c->stream));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->dn[c->dn_result], sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     return SPT_OK;
 }
 
@@ -1665,12 +1893,12 @@ int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
     const float4* img = c->dn[c->dn_result];
     if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
         // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch_resolve(img, c->pixels, 1.0f, exposure, (uint32_t*)c->out_dev, c->stream);
+        launch_resolve(img, c->pixels, 1.0f, exposure, (uint32_t*)c->out_dev, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     } else {
-        launch_resolve(img, c->pixels, 1.0f, exposure, c->resolved, c->stream);
+        launch_resolve(img, c->pixels, 1.0f, exposure, c->resolved, on_stream(c));
         SPT_HIP(c, hipGetLastError());
-        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, c->stream));
+        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
     }
     SPT_HIP(c, wait_frame(c));
     return SPT_OK;
@@ -1854,7 +2082,7 @@ int spt_set_profiling(spt_ctx* c, int mode) {
 int spt_get_stats(spt_ctx* c, spt_stats* out) {
     if (!c || !out) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     if (flush_events(c) != SPT_OK) return SPT_ERR_HIP;
     unsigned long long tot[kTotals];
     SPT_HIP(c, hipMemcpy(tot, c->totals, sizeof(tot), hipMemcpyDeviceToHost));
@@ -1901,6 +2129,7 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     out->view_live_pixels = c->view_valid ? c->view_n[0] : 0u;
     out->flat_pairs = c->last_specialized ? c->last_pairs : 0u;
     out->flat_pair_second_passes = tot[kTotPairSecond];
+    out->view_split = c->last_view_split ? 1u : 0u;
     if (tot[kTotStalled])
         return fail(c, SPT_ERR_HIP, "k_paths: " + std::to_string(tot[kTotStalled]) +
                                         " wave(s) stopped at the step bound with frames unaccumulated (a bug)");
@@ -1910,7 +2139,7 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
 int spt_stats_clear(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     if (flush_events(c) != SPT_OK) return SPT_ERR_HIP;
     SPT_HIP(c, hipMemset(c->totals, 0, sizeof(unsigned long long) * kTotals));
     c->frames = c->paths = c->passes = 0;
@@ -1970,10 +2199,11 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     if (t->px_shift && (t->px_shift < 2 || t->px_shift > 5)) return fail(c, SPT_ERR_INVALID, "spt_tuning: px_shift 2..5");
     if (t->chunks_per_wave > 1024 || t->subqueues > 65536 || t->tail_bounce > kMaxBounces ||
         t->bvh_max_leaf > kBvhMaxLeaf || (t->bvh_bins && (t->bvh_bins < 2 || t->bvh_bins > 64)) ||
-        t->specialize < -1 || t->specialize > 1 || t->view_cache < -1 || t->view_cache > 0)
+        t->specialize < -1 || t->specialize > 1 || t->view_cache < -1 || t->view_cache > 0 || t->split_streams < -1 ||
+        t->split_streams > 1)
         return fail(c, SPT_ERR_INVALID, "spt_tuning: value out of range");
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     const uint32_t n_sub = t->subqueues ? t->subqueues : c->cu_count * 12u;
     if (n_sub != c->n_sub) {  // the wavefront schedule's per-sub-queue counters: the new buffer first,
         // swapped in only once it exists (a failed allocation leaves the ctx as it was)
@@ -1998,6 +2228,7 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     c->bvh_bins = t->bvh_bins;
     c->specialize = t->specialize;
     c->view_cache = t->view_cache;
+    c->split_streams = t->split_streams;
     return SPT_OK;
 }
 
@@ -2018,7 +2249,7 @@ int spt_comm_init(spt_ctx* c, const uint8_t id[SPT_COMM_ID_BYTES], int n_ranks, 
     if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(c, SPT_ERR_INVALID, "spt_comm_init: rank out of range");
     if (!rccl().ok) return fail(c, SPT_ERR_NO_DEVICE, rccl().err);
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     free_comm(c);
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
@@ -2031,7 +2262,7 @@ int spt_comm_init(spt_ctx* c, const uint8_t id[SPT_COMM_ID_BYTES], int n_ranks, 
 int spt_comm_destroy(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     free_comm(c);
     return SPT_OK;
 }
@@ -2054,12 +2285,12 @@ int gather_check(spt_ctx* c, void* root_image, const char* what, uint32_t& rows_
 // gather_buf of `need` floats, its padding rows zeroed once (every copy into it writes the same rows)
 int gather_buffer(spt_ctx* c, size_t need) {
     if (c->gather_elems == need) return SPT_OK;
-    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->gather_done, 0));
-    SPT_HIP(c, hipStreamSynchronize(c->stream));  // (an earlier gather may still read the old buffer)
+    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(on_stream(c), c->gather_done, 0));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (an earlier gather may still read the old buffer)
     free_dev(c->gather_buf);
     if (need) {
         SPT_HIP(c, hipMalloc(&c->gather_buf, sizeof(float) * need));
-        SPT_HIP(c, hipMemsetAsync(c->gather_buf, 0, sizeof(float) * need, c->stream));
+        SPT_HIP(c, hipMemsetAsync(c->gather_buf, 0, sizeof(float) * need, on_stream(c)));
     }
     c->gather_elems = need;
     return SPT_OK;
@@ -2078,19 +2309,19 @@ int spt_gather_image(spt_ctx* c, void* root_image) {
     const bool padded = c->rows < rows_max;
     st = gather_buffer(c, root ? shard_elems * c->cfg.shard_count : (padded ? shard_elems : 0));
     if (st != SPT_OK) return st;
-    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->gather_done, 0));  // gather_buf is free
+    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(on_stream(c), c->gather_done, 0));  // gather_buf is free
     const float4* send = c->accum;
     if (padded && !root) {
         if (c->pixels)
-            SPT_HIP(c, hipMemcpyAsync(c->gather_buf, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, c->stream));
+            SPT_HIP(c, hipMemcpyAsync(c->gather_buf, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, on_stream(c)));
         send = c->gather_buf;
     }
     // one ncclGather for any world size (a 1-rank communicator copies: the single-GPU test runs the
     // same collective call the N-GPU run does)
-    SPT_NCCL(c, rccl().gather(send, root ? c->gather_buf : nullptr, shard_elems, ncclFloat32, 0, c->comm, c->stream));
+    SPT_NCCL(c, rccl().gather(send, root ? c->gather_buf : nullptr, shard_elems, ncclFloat32, 0, c->comm, on_stream(c)));
     if (root) {
         launch_assemble_rows(c->gather_buf, (float4*)root_image, c->cfg.width, c->cfg.height, c->cfg.shard_count,
-                             rows_max, c->stream);
+                             rows_max, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     }
     return SPT_OK;
@@ -2113,10 +2344,10 @@ int spt_gather_image_overlapped(spt_ctx* c, void* root_image) {
     // the snapshot, on the ctx stream after the frames rendered so far: rank 0's own shard goes to its
     // slot of the receive buffer (an in-place gather), the others' to their send buffer. The previous
     // overlapped gather must have finished reading that buffer first.
-    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->gather_done, 0));
+    if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(on_stream(c), c->gather_done, 0));
     if (c->pixels)
-        SPT_HIP(c, hipMemcpyAsync(c->gather_buf, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, c->stream));
-    SPT_HIP(c, hipEventRecord(c->snap_ready, c->stream));
+        SPT_HIP(c, hipMemcpyAsync(c->gather_buf, c->accum, sizeof(float4) * c->pixels, hipMemcpyDeviceToDevice, on_stream(c)));
+    SPT_HIP(c, hipEventRecord(c->snap_ready, on_stream(c)));
     // the collective and the assembly on the comm stream: the ctx stream renders on meanwhile
     SPT_HIP(c, hipStreamWaitEvent(c->comm_stream, c->snap_ready, 0));
     SPT_NCCL(c, rccl().gather(c->gather_buf, root ? c->gather_buf : nullptr, shard_elems, ncclFloat32, 0, c->comm,
@@ -2135,7 +2366,7 @@ int spt_gather_wait(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     if (!c->gather_pending) return SPT_OK;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipStreamWaitEvent(c->stream, c->gather_done, 0));
+    SPT_HIP(c, hipStreamWaitEvent(on_stream(c), c->gather_done, 0));
     c->gather_pending = false;
     return SPT_OK;
 }

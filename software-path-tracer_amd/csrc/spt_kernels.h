@@ -341,8 +341,11 @@ void launch_accumulate(const PassParams& p, hipStream_t s);
 // flat scenes, persistent schedule: every frame of the call in one launch, accumulated in frame
 // order in registers (no queues, no radiance buffer); `stats` tallies segments per bounce
 // (true: the flat scene's specialized kernel ran, spt_jit.hip; false: the generic one)
-// view: the view's compacted lists (n_sweep is set by the launch), or nullptr: the pixel plan
-bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view = nullptr);
+// view: the view's compacted lists (n_sweep is set by the launch), or nullptr: the pixel plan;
+// view_half: 0 the whole view, 1 / 2 half A / B of a split view (spt_launch_plan.h make_view_split: `view`
+// then holds that half's part of the lists, p.work / p.chunk_* the half's own buffers, s its own stream)
+bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view = nullptr,
+                  uint32_t view_half = 0u);
 // the scenes and configurations whose k_paths keeps a per-pixel bounce 0 that a view's lists can hold
 inline bool view_lists_scene(const PassParams& p) {
     return p.nodes == nullptr && p.n_prims != 0u && !cam_per_path(p.cam_mode) && p.bsdf == 0u;

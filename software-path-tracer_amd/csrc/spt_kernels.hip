@@ -3298,7 +3298,7 @@ bool launch_persistent(hipFunction_t fn, const void* kernel, uint32_t grid, size
 }
 }  // namespace
 
-bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view_lists) {
+bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view_lists, uint32_t view_half) {
     ShadeParams sp = shade_params(p, 0u);
     CameraParams cam = camera_params(p);
     const bool bvh = p.nodes != nullptr;
@@ -3331,7 +3331,7 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
     // The key names the plan; a scene or configuration change clears it (spt_capi.hip). The order
     // changes which wave traces a chunk, never a result.
     bool record = false;
-    const uint64_t order_key = view.live ? view_order_key(plan, view.n_live) : chunk_order_key(plan, p.shard_pixels);
+    const uint64_t order_key = view.live ? view_order_key(plan, view.n_live, view_half) : chunk_order_key(plan, p.shard_pixels);
     if (!p.px_shift && p.chunk_cost && p.chunk_order && plan.n[0] > 1u) {
         if (*p.chunk_order_key == order_key) {
             plan.order = p.chunk_order;

@@ -147,11 +147,16 @@ inline uint64_t chunk_order_key(const ChunkPlan& plan, uint32_t P) {
 // (the pixel plan's tail tiers cover the image's last pixels whatever they hold: on Cornell 1080p its
 // 8-pixel tier holds no live pixel at all).
 // (measurement builds: -DSPT_VIEW_TIER8=0 leaves the smallest tier to the remainder, the one A/B of the
-// view plan's tiers, profiles/view_cache_rates.txt)
+// view plan's tiers, profiles/view_cache_rates.txt; -DSPT_VIEW_TIER16=0 leaves the middle tier out as well, for
+// the A/B under split launches, profiles/split_streams_rates.txt)
 #ifndef SPT_VIEW_TIER8
 #define SPT_VIEW_TIER8 1
 #endif
+#ifndef SPT_VIEW_TIER16
+#define SPT_VIEW_TIER16 1
+#endif
 constexpr bool kViewTier8 = SPT_VIEW_TIER8 != 0;
+constexpr bool kViewTier16 = SPT_VIEW_TIER16 != 0;
 struct ViewChunkPlan {
     ChunkPlan plan;
     uint32_t n_sweep;
@@ -173,7 +178,7 @@ inline ViewChunkPlan make_view_plan(uint32_t shard_pixels, uint32_t live, uint32
     // chunks per small tier
     const uint64_t tail = shard_pixels ? (uint64_t)chunks_per_wave * resident_waves * live / shard_pixels : 0u;
     const uint32_t c_px = kViewTier8 ? (uint32_t)std::min<uint64_t>(live, tail << s2) : 0u;
-    const uint32_t b_px = (uint32_t)std::min<uint64_t>(live - c_px, tail << s1) & ~((1u << s1) - 1u);
+    const uint32_t b_px = kViewTier16 ? (uint32_t)std::min<uint64_t>(live - c_px, tail << s1) & ~((1u << s1) - 1u) : 0u;
     const uint32_t a_px = (live - c_px - b_px) & ~((1u << s0) - 1u);
     plan.n[0] = a_px >> s0;
     plan.n[1] = b_px >> s1;
@@ -182,9 +187,48 @@ inline ViewChunkPlan make_view_plan(uint32_t shard_pixels, uint32_t live, uint32
     plan.n[2] = (live - a_px - b_px + (1u << s2) - 1u) >> s2;
     return vp;
 }
-// names the view plan a recorded first-tier order belongs to (never a pixel plan's key: the top bit)
-inline uint64_t view_order_key(const ChunkPlan& plan, uint32_t live) {
-    return chunk_order_key(plan, live) | (1ull << 63);
+// names the view plan a recorded first-tier order belongs to (never a pixel plan's key: the top bit);
+// half: 0 the whole view's plan, 1 / 2 the plan of half A / B of a split view (make_view_split): bits 61-62,
+// which chunk_order_key leaves free for any first tier of < 2^24 chunks
+inline uint64_t view_order_key(const ChunkPlan& plan, uint32_t live, uint32_t half = 0u) {
+    return (chunk_order_key(plan, live) & ~(3ull << 61)) | ((uint64_t)(half & 3u) << 61) | (1ull << 63);
+}
+
+// A view's lists cut into two halves, A and B, that two k_paths launches on two streams run over at the
+// same time (spt_capi.hip): the launches touch disjoint pixels, so nothing orders one against the other,
+// and each launch's blocks move in as the other's waves run out of chunks. Half h covers live records
+// [live_at[h], live_at[h + 1]) and constant pixels [const_at[h], const_at[h + 1]). The live list is cut at
+// the multiple of the first tier's chunk size (first_tier_px, the whole shard's: make_view_plan) nearest
+// its middle, the constant list at the multiple of kViewSweep nearest its middle, so no chunk and no
+// sweep unit straddles the cut. A list shorter than half a unit goes to B whole: a half may be empty (and
+// is then not launched).
+struct ViewSplit {
+    uint32_t live_at[3];
+    uint32_t const_at[3];
+};
+inline uint32_t split_cut(uint32_t n, uint32_t unit) {
+    unit = std::max(unit, 1u);
+    const uint64_t cut = ((uint64_t)n / 2u + unit / 2u) / unit * unit;
+    return (uint32_t)std::min<uint64_t>(cut, n);
+}
+inline ViewSplit make_view_split(uint32_t n_live, uint32_t n_const, uint32_t first_tier_px) {
+    return ViewSplit{{0u, split_cut(n_live, first_tier_px), n_live}, {0u, split_cut(n_const, kViewSweep), n_const}};
+}
+// Whether the launches of one spt_render call over a cached view are split (spt_tuning.split_streams: knob).
+// Decided ONCE per call, from the call's largest launch (a call of more than max_launch_frames frames runs
+// several launches, the last one the remainder): were it decided per launch, a short remainder would run
+// whole on the ctx stream while the halves of the launch before it are still in flight over the same pixels.
+// Automatic (knob 0): launches of at least 2^24 live-pixel frames. The second launch and its ordering cost a
+// call 13-18 us whatever its size, the overlap gains about 5 % of its time: measured +4.6 %
+// at Cornell 1080p x 64 frames (51.6 M), +3.4 % on its 1/8 row shard x 512 frames (51.6 M), +6.5 % at 720p x
+// 64 (22.9 M); -4.5 % at 480x270 x 64 (3.2 M), -25 % at 96x64 x 64 (0.15 M).
+constexpr uint64_t kSplitMinLiveFrames = 1ull << 24;
+inline bool split_call_wanted(int32_t knob, uint32_t n_live, uint32_t call_frames, uint32_t max_launch_frames) {
+    if (knob) return knob > 0;
+    return (uint64_t)n_live * std::min(call_frames, max_launch_frames) >= kSplitMinLiveFrames;
+}
+inline bool view_half_empty(const ViewSplit& s, uint32_t h) {
+    return s.live_at[h + 1] == s.live_at[h] && s.const_at[h + 1] == s.const_at[h];
 }
 
 constexpr uint32_t kBlockWaves = kBlock / 64u;
