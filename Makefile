@@ -2,7 +2,8 @@
 #
 #   make            libspt_hip.so (C-ABI + gfx950 kernels) and libspt_render.so (C++ render::PathTracer backend)
 #   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so), its restatement with
-#                   material models (tests/cpp/libref_materials.so) and the lens's device check (tests/cpp/test_device_lens)
+#                   material models (tests/cpp/libref_materials.so), the lens's device check (tests/cpp/test_device_lens)
+#                   and the sphere pass's (tests/cpp/test_sphere_cull)
 #   make cpp-tests  the C++ interface test driver (tests/cpp)
 #
 # Every float operation on the hot path is compiled with -ffp-contract=off, on the device and on the
@@ -59,7 +60,8 @@ $(RLIB): $(RENDER_SRCS) $(LIB) $(wildcard include/render/*.h) $(CSRC)/HIPPathTra
 
 REFMAT := tests/cpp/libref_materials.so
 DEVLENS := tests/cpp/test_device_lens
-oracle: $(REFMAT) $(DEVLENS)
+SPHCULL := tests/cpp/test_sphere_cull
+oracle: $(REFMAT) $(DEVLENS) $(SPHCULL)
 
 oracle/build/libcpu_ref.so: oracle/cpu_ref.c oracle/cpu_ref.h include/spt.h oracle/Makefile
 	$(MAKE) -C oracle
@@ -77,11 +79,16 @@ $(REFMAT): tests/cpp/ref_materials.c oracle/cpu_ref.h include/spt.h oracle/build
 $(DEVLENS): tests/cpp/test_device_lens.hip $(CSRC)/spt_device.h
 	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
 
+# GPU program (run by tests/test_gpu_sphere_cull.py; --host, run by tests/test_sphere_cull_host.py: its inputs'
+# coverage, no GPU): spt_device.h's flat_sphere_pass against the loop over isect_sphere_fast; test infrastructure
+$(SPHCULL): tests/cpp/test_sphere_cull.hip $(CSRC)/spt_device.h
+	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
+
 cpp-tests: $(RLIB) oracle
 	$(MAKE) -C tests/cpp
 
 clean:
 	rm -rf $(OBJ) $(LIB) $(RLIB)
 	$(MAKE) -C oracle clean
-	rm -f $(REFMAT) $(DEVLENS)
+	rm -f $(REFMAT) $(DEVLENS) $(SPHCULL)
 	-$(MAKE) -C tests/cpp clean

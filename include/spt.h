@@ -196,6 +196,10 @@ typedef struct spt_stats {
     uint64_t view_split;                      /* 1: the last k_paths launch ran as two launches over the
                                                  two halves of the cached view, on two streams
                                                  (spt_tuning.split_streams; same results)          */
+    uint64_t flat_sphere_second_passes;       /* wave-level second passes of the one-pass sphere test of
+                                                 a shape with two to four spheres (some lane's ray has
+                                                 two or more candidate spheres: a second root stage);
+                                                 counted by k_paths' counting forms only           */
 } spt_stats;
 
 typedef struct spt_ctx spt_ctx;

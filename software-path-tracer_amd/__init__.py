@@ -157,6 +157,7 @@ class SptStats(ctypes.Structure):
         ("flat_pairs", ctypes.c_uint64),
         ("flat_pair_second_passes", ctypes.c_uint64),
         ("view_split", ctypes.c_uint64),
+        ("flat_sphere_second_passes", ctypes.c_uint64),
     ]
 
     def as_dict(self) -> dict:

@@ -2129,6 +2129,7 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     out->view_live_pixels = c->view_valid ? c->view_n[0] : 0u;
     out->flat_pairs = c->last_specialized ? c->last_pairs : 0u;
     out->flat_pair_second_passes = tot[kTotPairSecond];
+    out->flat_sphere_second_passes = tot[kTotSphereSecond];
     out->view_split = c->last_view_split ? 1u : 0u;
     if (tot[kTotStalled])
         return fail(c, SPT_ERR_HIP, "k_paths: " + std::to_string(tot[kTotStalled]) +

@@ -487,6 +487,111 @@ __device__ __forceinline__ float isect_sphere_fast(float4 s, float rr, F3 o, F3 
     return kInf;
 }
 
+// kNS >= 2 spheres (kp: their records, two words of float4 read per sphere: a = (center, radius), b = (r^2, -, -,
+// original index)) against one ray, with ONE root stage per ray where that is enough; `best` is the running
+// (t bits, original index) key. The result is the minimum over isect_sphere_fast of every sphere, bit for bit.
+// Stage 1, every sphere: isect_sphere_fast's b, c, disc, `redo` and validity, the same operations in the same
+// order. A sphere is a candidate for a lane if its disc is valid and not (b > 0 && c > 0). Such a culled sphere
+// returns kInf from isect_sphere_fast: t1's numerator -b - sq is negative, and disc = fl(fl(b b) - fl(4 a c)) <=
+// fl(b b) (a > 0, c > 0), whose correctly rounded root is |b| (radix 2; no underflow: a valid disc is 0 or >=
+// 2^-96), so sq <= b and t2's numerator -b + sq is <= 0; div_ref keeps the sign, and both roots fail t >= tmin.
+// Stage 2, once per ray: the lane's first candidate (b, disc and index selected lane-wise) runs the root stage
+// of isect_sphere_fast on the same operands: the same t. The far root runs only in a wave where some lane's
+// near root fell below tmin (a ray that starts inside or on its sphere).
+// Second pass: a wave with a lane of two or more candidates runs the root stage again, on each lane's second
+// candidate; with three or more spheres, a wave with a lane of three or more candidates then runs
+// isect_sphere_fast over every sphere (a sphere tested twice changes nothing: the key minimum is idempotent).
+// `second`: the counting kernels' counts in LDS (second[1] counts the second passes, one per wave), or null.
+template <uint32_t kNS>
+__device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, F3 o, F3 d, float a, RcpRef r2a, float tmin,
+                                                 bool& redo, uint64_t& best, uint32_t* second) {
+    // One root stage on per-lane operands; `on`: the lane holds a candidate (another lane's operands are those of
+    // some sphere that is none of its candidates, its roots are not read: no exec-mask region). A candidate's
+    // near root is kept if t >= tmin, else the far root replaces it (the wave then runs the far root) and is kept
+    // if t >= tmin: isect_sphere_fast's result. lanes: the wave's lanes that are `on` (a mask in scalar registers).
+    auto roots = [&](float sb, float sdisc, uint32_t sidx, bool on, uint64_t lanes) {
+        const float sq = sqrt_unit(sdisc);
+        float t = div_ref(-sb - sq, r2a);
+        const bool low = !(t >= tmin);
+        if ((__builtin_amdgcn_ballot_w64(low) & lanes) != 0ull) {
+            asm volatile("" ::: "memory");  // (kept a branch: the compiler would otherwise run the far root in every wave)
+            t = low ? div_ref(-sb + sq, r2a) : t;
+        }
+        t = (on & (t >= tmin)) ? t : kInf;
+        const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | sidx;
+        best = key < best ? key : best;
+    };
+    float bk[kNS], dk[kNS];
+    uint32_t ik[kNS];
+    bool cand[kNS];
+    uint64_t any = 0ull, many = 0ull, more = 0ull;  // lane masks (scalar registers): a candidate, two or more, three or more
+#pragma unroll
+    for (uint32_t k = 0; k < kNS; ++k) {
+        const float4 s = kp[4 * k + 0], pb = kp[4 * k + 1];
+        const float lx = o.x - s.x, ly = o.y - s.y, lz = o.z - s.z;
+        const float b = 2.0f * ((lx * d.x + ly * d.y) + lz * d.z);
+        const float c = ((lx * lx + ly * ly) + lz * lz) - pb.x;
+        const float disc = b * b - 4.0f * a * c;
+        redo = redo | ((disc > 0.0f) & (disc < 0x1p-96f));
+        cand[k] = ((disc >= 0x1p-96f) | (disc == 0.0f)) & (!(b > 0.0f) | !(c > 0.0f));
+        bk[k] = b;
+        dk[k] = disc;
+        ik[k] = __float_as_uint(pb.w);
+        // (the same predicate from the compares' own lane masks: scalar instructions only)
+        const uint64_t cm = (__builtin_amdgcn_ballot_w64(disc >= 0x1p-96f) | __builtin_amdgcn_ballot_w64(disc == 0.0f)) &
+                            (__builtin_amdgcn_ballot_w64(!(b > 0.0f)) | __builtin_amdgcn_ballot_w64(!(c > 0.0f)));
+        more |= cm & many;
+        many |= cm & any;
+        any |= cm;
+    }
+    // the lane's first candidate: the last sphere's operands unless an earlier sphere is a candidate
+    float sb = bk[kNS - 1u], sdisc = dk[kNS - 1u];
+    uint32_t sidx = ik[kNS - 1u];
+    bool seen = cand[kNS - 1u];
+#pragma unroll
+    for (uint32_t k = kNS - 1u; k-- > 0u;) {
+        sb = cand[k] ? bk[k] : sb;
+        sdisc = cand[k] ? dk[k] : sdisc;
+        sidx = cand[k] ? ik[k] : sidx;
+        seen = seen | cand[k];
+    }
+    roots(sb, sdisc, sidx, seen, any);
+    if (many != 0ull) {
+        // the lane's second candidate: the last sphere's operands unless an earlier sphere is the second one
+        bool one = cand[0], two = false;  // the lane's candidates up to sphere k: one or more, two or more
+        bool next[kNS];
+        next[0] = false;
+#pragma unroll
+        for (uint32_t k = 1; k < kNS; ++k) {
+            next[k] = cand[k] & one & !two;
+            two = two | (cand[k] & one);
+            one = one | cand[k];
+        }
+        float sb2 = bk[kNS - 1u], sdisc2 = dk[kNS - 1u];
+        uint32_t sidx2 = ik[kNS - 1u];
+#pragma unroll
+        for (uint32_t k = kNS - 1u; k-- > 1u;) {
+            sb2 = next[k] ? bk[k] : sb2;
+            sdisc2 = next[k] ? dk[k] : sdisc2;
+            sidx2 = next[k] ? ik[k] : sidx2;
+        }
+        roots(sb2, sdisc2, sidx2, two, many);
+        // (one count per wave: the first active lane's, in LDS)
+        if (second && __lane_id() == (uint32_t)__ffsll((long long)__ballot(true)) - 1u) atomicAdd(second + 1, 1u);
+        if constexpr (kNS >= 3u) {
+            if (more != 0ull) {
+#pragma unroll
+                for (uint32_t k = 0; k < kNS; ++k) {
+                    const float4 s = kp[4 * k + 0], pb = kp[4 * k + 1];
+                    const float tk = isect_sphere_fast(s, pb.x, o, d, a, r2a, tmin, redo);
+                    const uint64_t kk = ((uint64_t)__float_as_uint(tk) << 32) | __float_as_uint(pb.w);
+                    best = kk < best ? kk : best;
+                }
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ float comp(float4 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 __device__ __forceinline__ float comp(F3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 

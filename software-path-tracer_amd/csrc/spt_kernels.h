@@ -16,7 +16,8 @@ constexpr uint32_t kMaxBounces = 32;
 constexpr uint32_t kFlagFastDiv = 1u << 30;  // internal ShadeParams flag: the scene passed fast_division_ok (scene.cpp)
 // statistics counters (u64): segments per bounce | radiance updates per bounce | k_paths lane slots
 // of its tracing steps | lanes that traced in them | BVH interior nodes visited | primitives tested |
-// NEE shadow rays traced | waves stopped by the step bound | second passes of the paired wall test
+// NEE shadow rays traced | waves stopped by the step bound | second passes of the paired wall test |
+// second passes of the one-pass sphere test
 constexpr uint32_t kTotShadow = 2 * kMaxBounces + 4;
 // k_paths waves that left their step loop at its safety bound with frames not yet accumulated (a logic
 // error: every path ends within max_bounces steps); always counted, reported by spt_get_stats
@@ -24,7 +25,12 @@ constexpr uint32_t kTotStalled = 2 * kMaxBounces + 5;
 // wave-level second passes of the paired wall test (closest_flat: some lane's origin outside a pair's
 // slab), counted by the counting forms of the specialized flat k_paths
 constexpr uint32_t kTotPairSecond = 2 * kMaxBounces + 6;
-constexpr uint32_t kTotals = 2 * kMaxBounces + 7;
+// wave-level second passes of the one-pass sphere test (spt_device.h flat_sphere_pass: some lane with two or
+// more candidate spheres), counted by the same kernels
+constexpr uint32_t kTotSphereSecond = 2 * kMaxBounces + 7;
+// the most spheres of a shape key whose k_paths kernels run the one-pass sphere test
+constexpr uint32_t kOnePassMax = 4;
+constexpr uint32_t kTotals = 2 * kMaxBounces + 8;
 
 // Next-event estimation (SPT_FLAG_NEE): the emitter records (scene.h DevEmitter, spt_device.h
 // light_sample). Passed as every integrator kernel's LAST argument, so the kernels without NEE keep
@@ -175,7 +181,8 @@ __host__ __device__ constexpr uint32_t flat_shape_pairs(uint64_t key) {
     return flat_shape_pairs(key, 0u) + flat_shape_pairs(key, 1u) + flat_shape_pairs(key, 2u);
 }
 // A k_paths with wall pairs reads their LDS table (spt_kernels.hip make_pair_table), 2 entries of 2 float4
-// per pair, behind the launch-sized shading records, and its counting form keeps one count behind that
+// per pair, behind the launch-sized shading records, and its counting form keeps its counts behind that (16 B:
+// the pairs' second passes, then the sphere test's)
 __host__ __device__ constexpr uint32_t flat_pair_table_bytes(uint64_t key) {
     return flat_shape_pairs(key) ? 64u * flat_shape_pairs(key) + 16u : 0u;
 }

@@ -76,7 +76,12 @@ __device__ __forceinline__ void closest_flat_exact(const float4* __restrict__ pr
 // wall of the pair that its direction faces (|d[AX]| >= 2^-20 here, never zero), its five words read
 // from a small LDS table by `up`; if any lane of the wave starts outside the slab, the whole wave
 // tests the other wall too — both are exact tests of real quads, so that is always right.
-
+//
+// Spheres (kOnePass: k_paths' kernels of a shape key with two to four spheres): every sphere's discriminant, then
+// ONE root stage per ray on the lane's first candidate sphere, and a second one in a wave where some lane has two
+// candidates (spt_device.h flat_sphere_pass, which states why the result is the per-sphere loop's, bit for bit).
+// C2: 3.5 % fewer vector instructions per launch, +2.5 % (profiles/sphere_pass_rates.txt).
+//
 // The table: per pair two entries of two float4, lower plane first:
 // (a[AX], a[U], a[V], c[U]), (d[V], original index bits, 0, 0); the x pairs, then y, then z.
 template <uint64_t kShape>
@@ -156,11 +161,16 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
 #define SPT_FLAT_GROUPS(UNROLL, PIN, HEAD)                                                      \
     {                                                                                           \
         uint32_t k = 0;                                                                         \
-        UNROLL for (const uint32_t e = flat_ends & 63u; k < e; ++k) { /* spheres */             \
-            const float4 pa = kp[4 * k + 0], pb = kp[4 * k + 1];                                \
-            PIN(pa);                                                                            \
-            PIN(pb);                                                                            \
-            take(isect_sphere_fast(pa, pb.x, o, d, a, r2a, kTNear, redo), pb);                  \
+        if constexpr (kOnePass) { /* two or more spheres: one root stage per ray (flat_sphere_pass) */ \
+            flat_sphere_pass<(uint32_t)(kShape & 63u)>(kp, o, d, a, r2a, kTNear, redo, best, second); \
+            k = (uint32_t)(kShape & 63u);                                                       \
+        } else {                                                                                \
+            UNROLL for (const uint32_t e = flat_ends & 63u; k < e; ++k) { /* spheres */         \
+                const float4 pa = kp[4 * k + 0], pb = kp[4 * k + 1];                            \
+                PIN(pa);                                                                        \
+                PIN(pb);                                                                        \
+                take(isect_sphere_fast(pa, pb.x, o, d, a, r2a, kTNear, redo), pb);              \
+            }                                                                                   \
         }                                                                                       \
         HEAD(0, rdx)                                                                            \
         SPT_FLAT_GROUP(UNROLL, PIN, 6, (isect_quad_axis_fast<0, ((kRectBits >> 0) & 1u) != 0u>(pa, pc, pd, o, d, rdx, kTNear))) \
@@ -196,6 +206,9 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
     const float in_t = best_t;
     const uint32_t in_k = best_k;
     constexpr uint32_t kRectBits = (uint32_t)(kShape >> 53) & 7u;  // flat_shape_key
+    // k_paths' kernels of a shape with two to kOnePassMax spheres test them in one root pass (flat_sphere_pass
+    // keeps every sphere's b and disc in registers: a shape with more spheres keeps the loop)
+    [[maybe_unused]] constexpr bool kOnePass = kShape != 0 && kPaired && (kShape & 63u) >= 2u && (kShape & 63u) <= kOnePassMax;
     if (fast_scene) {
         const float a = (d.x * d.x + d.y * d.y) + d.z * d.z;  // isect_sphere's a
         const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
@@ -1646,14 +1659,17 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     __shared__ uint32_t s_shadow[kStats && kNee ? 1u : 1u];  // NEE shadow rays traced (statistics)
     if (kStats && kNee && threadIdx.x == 0u) s_shadow[0] = 0u;
     if (!kBvh) make_shade_recs(prims, mats, sp.n_prims, s_scene);
-    // a shape with wall pairs: their table behind the shading records, then the counting forms' count of
+    // a shape with wall pairs: their table behind the shading records, then the counting forms' counts of
     // second passes (launch_paths sizes the LDS: flat_pair_table_bytes)
     constexpr uint32_t kPairs = kBvh ? 0u : flat_shape_pairs(kShape);
     [[maybe_unused]] float4* const pair_tab = s_scene + 3u * ((uint32_t)(kShape >> 30) & 63u);
     [[maybe_unused]] uint32_t* const pair_second = kStats ? (uint32_t*)(pair_tab + 4u * kPairs) : nullptr;
+    // (the second word of that count: the second passes of the one-pass sphere test, flat_sphere_pass)
+    constexpr bool kCountSpheres = kStats && kPairs != 0u && (kShape & 63u) >= 2u && (kShape & 63u) <= kOnePassMax;
     if constexpr (kPairs != 0u) {
         make_pair_table<kShape>(prims, pair_tab);
         if (kStats && threadIdx.x == 0u) *pair_second = 0u;
+        if (kCountSpheres && threadIdx.x == 0u) pair_second[1] = 0u;
     }
     // the next launch's work heads (stream order: the previous user of that set has finished)
     if (blockIdx.x == 0u && threadIdx.x < kWorkHeads) work_next[threadIdx.x * kWorkStride] = 0u;
@@ -2384,6 +2400,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         if (kNee && threadIdx.x == 0u && s_shadow[0]) atomicAdd(&totals[kTotShadow], (unsigned long long)s_shadow[0]);
         if constexpr (kPairs != 0u)
             if (threadIdx.x == 0u && *pair_second) atomicAdd(&totals[kTotPairSecond], (unsigned long long)*pair_second);
+        if constexpr (kCountSpheres)
+            if (threadIdx.x == 0u && pair_second[1]) atomicAdd(&totals[kTotSphereSecond], (unsigned long long)pair_second[1]);
     }
 }
 
