@@ -524,6 +524,10 @@ enum spt_profile {
 int spt_set_profiling(spt_ctx* ctx, int mode);  /* mode: OR of spt_profile, 0 = off */
 int spt_get_stats(spt_ctx* ctx, spt_stats* out);   /* synchronizes the ctx stream */
 int spt_stats_clear(spt_ctx* ctx);
+/* *view_wide = 1 when the last k_paths launch ran the wide form, 64-pixel chunks over the cached view's live
+ * list (spt_tuning.wide_chunks; same results), else 0. A query of its own beside spt_stats.view_cached and
+ * view_split: spt_stats keeps its size. */
+int spt_get_view_wide(spt_ctx* ctx, uint64_t* view_wide);
 
 /* ---- multi-GPU: row shards gathered over RCCL ------------------------------
  * One process and one ctx per GPU; ctx r is configured with shard_rank = r, shard_count = N. The
@@ -593,6 +597,13 @@ typedef struct spt_tuning {
                                   render's writes, as without the split). Decided once per spt_render call.
                                   0: automatic (launches of at least 2^24 live-pixel frames); 1: whenever a view is
                                   cached; -1: never                                                     */
+    int32_t wide_chunks;       /* flat scenes, k_paths over a cached view: a first tier of 64-pixel chunks, every
+                                  lane of a wave holding a pixel (the wide kernel; launches of at most 512
+                                  frames, so a longer call runs more of them). Eligible: no NEE, no forced
+                                  px_shift, a whole image (world size 1). Decided once per spt_render call.
+                                  0: automatic (launches of at least 3.15 M live-pixel frames of an image
+                                  whose plan already starts with 32-pixel chunks: Cornell 1080p from 4
+                                  frames per call); 1: every eligible launch over a cached view; -1: never */
 } spt_tuning;
 /* Applies to later calls; subqueues re-sizes at the next spt_configure. */
 int spt_set_tuning(spt_ctx* ctx, const spt_tuning* tuning);

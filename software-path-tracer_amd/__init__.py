@@ -159,12 +159,16 @@ class SptStats(ctypes.Structure):
         ("view_split", ctypes.c_uint64),
         ("flat_sphere_second_passes", ctypes.c_uint64),
     ]
+    # spt_get_view_wide's answer, set by Context.stats(): 1 when the last k_paths launch ran the wide form
+    # (a query of its own: spt_stats keeps its size)
+    view_wide = 0
 
     def as_dict(self) -> dict:
         d = {}
         for k, _ in self._fields_:
             v = getattr(self, k)
             d[k] = list(v) if isinstance(v, ctypes.Array) else v
+        d["view_wide"] = self.view_wide
         return d
 
 
@@ -174,7 +178,7 @@ EXPORTED_SYMBOLS = (
     "spt_set_scene", "spt_configure", "spt_reset", "spt_get_frame_count", "spt_render", "spt_synchronize",
     "spt_shard_pixels", "spt_read_accum", "spt_accum_device_ptr", "spt_copy_accum_device", "spt_resolve_rgba8",
     "spt_resolve_rgba8_exposure", "spt_register_host_output", "spt_render_resolve_rgba8", "spt_assemble_rows",
-    "spt_set_profiling", "spt_get_stats", "spt_stats_clear", "spt_build_scene",
+    "spt_set_profiling", "spt_get_stats", "spt_get_view_wide", "spt_stats_clear", "spt_build_scene",
     "spt_set_env_map", "spt_env_octa_from_equirect",
     "spt_comm_available", "spt_comm_unique_id", "spt_comm_init", "spt_gather_image", "spt_gather_image_overlapped", "spt_gather_wait",
     "spt_comm_destroy", "spt_set_tuning",
@@ -204,6 +208,7 @@ class SptTuning(ctypes.Structure):
         ("specialize", ctypes.c_int32),
         ("view_cache", ctypes.c_int32),
         ("split_streams", ctypes.c_int32),
+        ("wide_chunks", ctypes.c_int32),
     ]
 
     def __init__(self, **kw):
@@ -279,6 +284,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_set_env_map": ([P, P, U32, U32], I),
         "spt_env_octa_from_equirect": ([P, U32, U32, P, U32, U32], I),
         "spt_get_stats": ([P, ctypes.POINTER(SptStats)], I),
+        "spt_get_view_wide": ([P, ctypes.POINTER(ctypes.c_uint64)], I),
         "spt_stats_clear": ([P], I),
         "spt_build_scene": ([U32, P, ctypes.POINTER(U32), P, ctypes.POINTER(U32), ctypes.POINTER(SptEnv)], I),
         "spt_comm_available": ([], I),
@@ -810,6 +816,9 @@ class Context:
     def stats(self) -> SptStats:
         s = SptStats()
         self._check(self.lib.spt_get_stats(self.h, ctypes.byref(s)), "spt_get_stats")
+        wide = ctypes.c_uint64(0)
+        self._check(self.lib.spt_get_view_wide(self.h, ctypes.byref(wide)), "spt_get_view_wide")
+        s.view_wide = int(wide.value)
         return s
 
     def clear_stats(self) -> None:

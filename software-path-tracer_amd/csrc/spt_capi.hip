@@ -99,6 +99,8 @@ struct spt_ctx {
     bool stream_dirty = true;
     int32_t split_streams = 0;      // spt_tuning: -1 never, 0 automatic, 1 always when a view is valid
     bool last_view_split = false;   // the last persistent launch was split
+    bool last_view_wide = false;    // ... ran the wide kernel (64-pixel chunks)
+    int32_t wide_chunks = 0;        // spt_tuning: 0 = automatic, 1 = every eligible launch over a view, -1 = never
     // spt_accum_device_ptr handed the sums' address out (until the next spt_configure frees it): the caller may
     // read them with work of its own on its stream that no ctx call sees, so every split launch forks, as if
     // the stream were always dirty (it then waits for that work; the overlap across calls is given up)
@@ -617,12 +619,17 @@ static int write_camera_record(spt_ctx* c) {
     return SPT_OK;
 }
 
+// the ctx may run wide launches (spt_launch_plan.h wide_possible): their kernel is compiled with the others
+static bool wide_possible_ctx(const spt_ctx* c) {
+    return c->view_cache >= 0 && c->px_shift == 0u && wide_possible(c->wide_chunks, c->pixels, c->cfg.shard_count, c->cu_count);
+}
+
 // Start compiling a configured flat scene's specialized kernels in the background (a new shape or a new
 // configuration): frames rendered before they are ready run the generic kernels.
 static void prefetch_flat(const spt_ctx* c) {
     if (!(c->has_scene && c->configured && c->n_prims && c->n_nodes == 0 && c->specialize == 0)) return;
     const uint64_t key = flat_jit_key(c);
-    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0);
+    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
     for (int i = 0; i < kinds.n; ++i) jit_prefetch(kinds.k[i].kind, kinds.k[i].env, key);
 }
 
@@ -1235,8 +1242,8 @@ static bool half_buffers(spt_ctx* c) {
 
 // One persistent launch as two: `whole` is the view's lists, p the launch's parameters (its work heads and
 // chunk buffers are replaced by each half's own). launched[h]: half h got a launch (an empty half gets none).
-static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, bool launched[2]) {
-    const ViewSplit sp = make_view_split(whole.n_live, whole.n_const, 1u << kMaxChunkShift);
+static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, bool launched[2], int wide) {
+    const ViewSplit sp = make_view_split(whole.n_live, whole.n_const, wide ? kWidePx : 1u << kMaxChunkShift);
     EventPair span_ev;
     if (c->profiling && c->span && begin_persistent(c, span_ev) != SPT_OK) return SPT_ERR_HIP;  // (the span's begin: ctx stream)
     if (c->stream_dirty || c->accum_shared) {  // fork
@@ -1269,7 +1276,7 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
             ++n_ev;
             if (hipEventRecord(ev[n_ev - 1].a, vh.stream) != hipSuccess) rc = fail(c, SPT_ERR_HIP, "k_paths (split): hipEventRecord");
         }
-        c->last_specialized = launch_paths(p, c->counters, vh.stream, &view, h + 1u);
+        c->last_specialized = launch_paths(p, c->counters, vh.stream, &view, h + 1u, wide, &c->last_view_wide);
         launched[h] = true;
         // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
         const hipError_t le = hipGetLastError();
@@ -1317,7 +1324,11 @@ static int join_halves(spt_ctx* c, bool launched[2]) {
 static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, uint32_t n_frames, bool launched[2]) {
     uint32_t done = 0;
     while (done < n_frames) {
-        const uint32_t f = std::min(kPersistentMaxFrames, n_frames - done);
+        // (a call whose launches over the view may be wide takes at most kWideMaxFrames frames per such launch:
+        // the ring's lap byte; decided for the call, as the split is)
+        const bool view_now = c->view_cache >= 0 && c->view_valid && view_lists_scene(p);
+        const int wide = view_now ? wide_call(c->wide_chunks, wide_eligible(p), wide_first_tier(c->pixels, c->cu_count), c->view_n[0], n_frames) : 0;
+        const uint32_t f = std::min(wide ? kWideMaxFrames : kPersistentMaxFrames, n_frames - done);
         p.first_frame = first_frame + done;
         p.n_frames = f;
         p.n_paths = f * c->pixels;
@@ -1330,7 +1341,7 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
         // launch of the call once the lists exist.
         if (view_on && split_call_wanted(c->split_streams, c->view_n[0], n_frames, kPersistentMaxFrames) && half_buffers(c)) {
             c->last_view_cached = c->last_view_split = true;
-            const int rc = launch_paths_split(c, p, view, launched);
+            const int rc = launch_paths_split(c, p, view, launched, wide);
             if (rc != SPT_OK) return rc;
             done += f;
             c->passes++;
@@ -1345,7 +1356,7 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
         p.chunk_cost = c->chunk_cost;
         p.chunk_order = c->chunk_order;
         p.chunk_order_key = &c->chunk_order_key;
-        c->last_specialized = launch_paths(p, c->counters, on_stream(c), view_on ? &view : nullptr);
+        c->last_specialized = launch_paths(p, c->counters, on_stream(c), view_on ? &view : nullptr, 0u, wide, &c->last_view_wide);
         c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
         c->last_view_cached = view_on;
         // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
@@ -2137,6 +2148,12 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     return SPT_OK;
 }
 
+int spt_get_view_wide(spt_ctx* c, uint64_t* view_wide) {
+    if (!c || !view_wide) return SPT_ERR_INVALID;
+    *view_wide = c->last_view_wide ? 1u : 0u;
+    return SPT_OK;
+}
+
 int spt_stats_clear(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
@@ -2160,7 +2177,7 @@ int spt_specialize_scene(spt_ctx* c) {
     SPT_HIP(c, hipSetDevice(c->device));
     const uint64_t key = flat_jit_key(c);  // (before spt_configure: the shape alone)
     std::string err;
-    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0);
+    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
     for (int i = 0; i < kinds.n; ++i)
         if (!jit_function(kinds.k[i].kind, kinds.k[i].env, key, &err))
             return fail(c, SPT_ERR_HIP, ("specialized kernels unavailable (the generic ones run): " + err).c_str());
@@ -2201,7 +2218,7 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     if (t->chunks_per_wave > 1024 || t->subqueues > 65536 || t->tail_bounce > kMaxBounces ||
         t->bvh_max_leaf > kBvhMaxLeaf || (t->bvh_bins && (t->bvh_bins < 2 || t->bvh_bins > 64)) ||
         t->specialize < -1 || t->specialize > 1 || t->view_cache < -1 || t->view_cache > 0 || t->split_streams < -1 ||
-        t->split_streams > 1)
+        t->split_streams > 1 || t->wide_chunks < -1 || t->wide_chunks > 1)
         return fail(c, SPT_ERR_INVALID, "spt_tuning: value out of range");
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
@@ -2230,6 +2247,7 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     c->specialize = t->specialize;
     c->view_cache = t->view_cache;
     c->split_streams = t->split_streams;
+    c->wide_chunks = t->wide_chunks;
     return SPT_OK;
 }
 

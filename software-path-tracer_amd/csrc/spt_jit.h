@@ -12,7 +12,7 @@ namespace spt {
 // The kernels compiled per flat scene shape: every one is <kStats, kBvh = false, env, shape, tail>, kStats
 // false but for the two counting k_paths of a shape with wall pairs (spt_launch_plan.h jit_kind).
 enum : int { kJitPaths, kJitFrame, kJitPathsChan, kJitPathsNee, kJitFrameNee, kJitFrameRgba, kJitFrameNeeRgba,
-             kJitPathsStats, kJitPathsNeeStats, kJitKinds };
+             kJitPathsStats, kJitPathsNeeStats, kJitPathsWide, kJitPathsWideStats, kJitKinds };
 constexpr int kJitCallersEnv = -1;
 struct JitKindRow {
     const char* kernel;
@@ -30,6 +30,8 @@ constexpr JitKindRow kJitKindTable[kJitKinds] = {
     {"k_frame", ", false, 1, true", 2},              // kNee = kNeeAll, kRgba
     {"k_paths", "", kJitCallersEnv, true},           // kStats
     {"k_paths", ", 0, false, 1", 2, true},           // kStats, kNee = kNeeAll
+    {"k_paths", ", 0, false, 0, false, false, true", kJitCallersEnv},        // kWide (64-pixel chunks of a view)
+    {"k_paths", ", 0, false, 0, false, false, true", kJitCallersEnv, true},  // kStats, kWide
 };
 // the name expression hiprtc instantiates for (kind, env, shape)
 inline std::string jit_name_expr(int kind, int env, uint64_t shape) {

@@ -289,6 +289,14 @@ constexpr uint32_t kMaxChunkShift = 5;  // k_paths chunks of at most 32 pixels (
 // ends with 2- and 1-pixel ones — a chunk runs all frames of a launch (N x 64), so its length, not its
 // pixel count, sets the launch's tail
 constexpr uint32_t kMinChunkShift = 0;
+// The wide form of the flat pixel-lane k_paths (kWide; only over a view's lists, where every pixel of a
+// chunk is live): a first tier of 64-pixel chunks, every lane holding a pixel's accumulator. A chunk runs
+// n_frames x 64 slots through the 256-entry ring, whose done byte holds the slot's lap (slot / 256 + 1): a
+// wide launch therefore takes at most 512 frames (lap <= 128, as 1024 frames of 32 pixels), and a call of
+// more frames runs several such launches (spt_capi.hip render_persistent).
+constexpr uint32_t kWideShift = 6;
+constexpr uint32_t kWidePx = 1u << kWideShift;
+constexpr uint32_t kWideMaxFrames = 512;
 
 // k_paths work plan: n[i] chunks of 1 << shift[i] pixels starting at pixel start[i] (start[0] = 0).
 // Flat scenes: the first tier's chunks are handed out in `order` (chunk indices, longest first) once a
@@ -351,8 +359,9 @@ void launch_accumulate(const PassParams& p, hipStream_t s);
 // view: the view's compacted lists (n_sweep is set by the launch), or nullptr: the pixel plan;
 // view_half: 0 the whole view, 1 / 2 half A / B of a split view (spt_launch_plan.h make_view_split: `view`
 // then holds that half's part of the lists, p.work / p.chunk_* the half's own buffers, s its own stream)
+// wide_call: spt_launch_plan.h wide_call of the call (0: the narrow plan); ran_wide: whether the wide kernel ran
 bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view = nullptr,
-                  uint32_t view_half = 0u);
+                  uint32_t view_half = 0u, int wide_call = 0, bool* ran_wide = nullptr);
 // the scenes and configurations whose k_paths keeps a per-pixel bounce 0 that a view's lists can hold
 inline bool view_lists_scene(const PassParams& p) {
     return p.nodes == nullptr && p.n_prims != 0u && !cam_per_path(p.cam_mode) && p.bsdf == 0u;

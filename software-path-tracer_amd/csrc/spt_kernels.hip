@@ -1626,7 +1626,7 @@ __device__ __forceinline__ void advance_rays(const float4* __restrict__ nodes, c
 // jittered — is read at run time: camera_ray_xy) and shades with shade_hit's kBsdf and scatter_specular;
 // `spec`, the path's one bit of material state, is a lane register. Generic kernels only, kEnv = 2.
 template <bool kStats, bool kBvh, int kEnv, uint64_t kShape = 0, int kSimdWaves = 0, bool kChan = false, int kNee = 0,
-          bool kJitter = false, bool kBsdf = false>
+          bool kJitter = false, bool kBsdf = false, bool kWide = false>
 __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWavesBvh : ((kNee || kBsdf) ? kPathsWaves : kPathsWavesFlat))) void k_paths(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                                   const float4* __restrict__ nodes, uint32_t n_prims,
                                                   float4* __restrict__ accum,
@@ -1638,16 +1638,19 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     constexpr bool kStart0 = kJitter || kBsdf;  // every path starts at bounce 0: no per-pixel primary state
     // the instantiations that can run over a view's compacted lists (ViewPlan); the others never read `view`
     constexpr bool kView = !kBvh && !kStart0;
+    static_assert(!kWide || (kView && !kChan && !kNee), "the wide form: the flat pixel-lane kernel over a view's lists");
     bake_config<kShape>(sp);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
     extern __shared__ float4 s_scene[];
     constexpr uint32_t kPxRecs = kBvh ? 3u : kFlatPxRecs;  // PrimaryState records kept per pixel
-    __shared__ float4 s_px[kWaves][kPxRecs][1u << kMaxChunkShift];  // per-pixel primary state (PrimaryState)
+    // (kWide: r0 and r1 of up to 64 live pixels; r2 stays in the view's live list)
+    constexpr uint32_t kR2 = kWide ? 0u : 2u;  // where the kernels that stage r2 keep it (kWide: never read)
+    __shared__ float4 s_px[kWaves][kWide ? 2u : kPxRecs][kWide ? kWidePx : 1u << kMaxChunkShift];  // per-pixel primary state (PrimaryState)
     __shared__ float s_L[kWaves][3][kRingSlots];  // radiance of finished paths, ring of path slots
     // a done byte per ring entry (the slot's lap), read four at a time by the completion check
     __shared__ __attribute__((aligned(16))) uint32_t s_cnt[kWaves][64];
-    __shared__ uint8_t s_pix[kWaves][1u << kMaxChunkShift];  // per pixel: live rank | kConstPx + entry of its Lc
+    __shared__ uint8_t s_pix[kWaves][kWide ? 1u : 1u << kMaxChunkShift];  // per pixel: live rank | kConstPx + entry of its Lc
     // BVH scenes: the tree's top nodes (breadth-first: the root and the levels below it), read from
     // LDS instead of L2 by every traversal — the LDS left over at this kernel's occupancy
     constexpr uint32_t kTop = kBvh ? (kSimdWaves == 8 ? kBvhTopNodes8 : kBvhTopNodes) : 0u;
@@ -1695,9 +1698,9 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     uint32_t lane_slots = 0, lane_busy = 0;  // statistics: lane utilization of the tracing steps
     BvhCounters bvh_ctr;                     // statistics: BVH work of this lane's traced segments
     uint32_t n_chunks = plan.n[0] + plan.n[1] + plan.n[2];
-    bool view_on = false;  // (wave-uniform) the launch runs over a view's compacted lists
+    bool view_on = kWide;  // (wave-uniform) the launch runs over a view's compacted lists (kWide: always)
     if constexpr (kView) {
-        view_on = view.live != nullptr;
+        if (!kWide) view_on = view.live != nullptr;
         if (view_on) n_chunks += view.n_sweep;
     }
     const uint32_t xcc = xcc_id();
@@ -1759,7 +1762,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             pxs = plan.shift[2];
             pix0 = plan.start[2] + ((chunk - plan.n[0] - plan.n[1]) << pxs);
         }
-        const uint32_t px = 1u << pxs;  // pixels of this chunk (1 to 32)
+        const uint32_t px = 1u << pxs;  // pixels of this chunk (1 to 32; kWide: to 64)
         // (a view's tiers are laid over its live list: pix0 is then a live-list index)
         const uint32_t npx = min(px, ((kView && view_on) ? view.n_live : cam.shard_pixels) - pix0);
         // Bounce 0 of every pixel, once per chunk. A pixel whose camera ray ends its path without an
@@ -1841,14 +1844,15 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         }
         // bounce 0: one segment per path (kJitter: the step counts the camera segments it traces)
         if (kStats && !kStart0 && lane == 0u) atomicAdd(&s_seg[0], n_frames * npx);
-        const uint32_t live_mask = (uint32_t)__ballot(live_px);  // bit j: pixel j is live (px <= 32)
-        const uint32_t n_live = (uint32_t)__popc(live_mask);
+        // (kWide: every pixel of the chunk is live, so pixel j's live rank is j and no mask is needed)
+        const uint32_t live_mask = kWide ? 0u : (uint32_t)__ballot(live_px);  // bit j: pixel j is live (px <= 32)
+        const uint32_t n_live = kWide ? npx : (uint32_t)__popc(live_mask);
 #ifdef SPT_TIMELINE
         tl_pxs = pxs;
         tl_live = n_live;
 #endif
         if (kOrdered && plan.cost && n_live == 0u && chunk < plan.n[0] && lane == 0u) plan.cost[chunk] = 0u;
-        if (n_live == 0u) {  // a chunk of constant pixels (sky): every frame adds Lc, in order
+        if (!kWide && n_live == 0u) {  // a chunk of constant pixels (sky): every frame adds Lc, in order
             // (the channel lanes fetch their pixel's Lc from its pixel lane)
             const float lx = __shfl(lc.x, (int)cp, 64), ly = __shfl(lc.y, (int)cp, 64), lz = __shfl(lc.z, (int)cp, 64);
             const float v0 = c0 == 0u ? lx : (c0 == 1u ? ly : lz);
@@ -1869,22 +1873,33 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         // a constant pixel's Lc at record 0, entry n_live + (its rank among the constant pixels);
         // s_pix[j]: pixel j's live rank, or kConstPx | the entry of its Lc (read by accumulate)
         const uint32_t li = __builtin_amdgcn_mbcnt_lo(live_mask, 0u);  // live pixels below this lane
+        // kWide: the chunk's part of the live list; r2 (the tangent, the shard pixel) is read from it
+        [[maybe_unused]] const float4* const wrec = kWide ? view.live + 3u * (size_t)pix0 : nullptr;
+        if constexpr (kWide) {
+            if (lane < npx) {
+                s_px[wave][0][lane] = ps.r0;
+                s_px[wave][1][lane] = ps.r1;
+            }
+        } else {
         if (live_px) {
             s_px[wave][0][li] = ps.r0;
             s_px[wave][1][li] = ps.r1;
-            s_px[wave][2][li] = ps.r2;
+            s_px[wave][kR2][li] = ps.r2;
         } else if (lane < npx) {
             s_px[wave][0][n_live + lane - li] = make_float4(lc.x, lc.y, lc.z, 0.f);
         }
         if (lane < px) s_pix[wave][lane] = (uint8_t)(live_px ? li : (kConstPx | (n_live + lane - li)));
+        }
         // Ring of kRingSlots path slots (slot s = frame * n_live + live rank; entry s mod kRingSlots):
         // the radiance of finished paths and a done byte per entry holding the slot's lap (s / kRingSlots
-        // + 1, <= 128 for <= 1024 frames of <= 32 pixels), so entries are never cleared: a byte left by
-        // the previous lap reads as not done.
+        // + 1, <= 128 for <= 1024 frames of <= 32 pixels, or <= kWideMaxFrames = 512 frames of <= 64), so
+        // entries are never cleared: a byte left by the previous lap reads as not done.
         s_cnt[wave][lane] = 0;
         uint8_t* const ring_flg = reinterpret_cast<uint8_t*>(&s_cnt[wave][0]);
-        // floor(s / n_live) for s < 2^15 as a high multiply by m = ceil(2^31 / n_live) (an SGPR):
+        // floor(s / n_live) for s <= 2^15 as a high multiply by m = ceil(2^31 / n_live) (an SGPR):
         // (2s * m) >> 32 = floor(s / n_live + s * e / (n_live * 2^31)) with e < n_live, exact
+        // (exact while s * e < 2^31: n_live <= 64 and s <= 2^16 give s * e < 2^22, so kWide's s <= 2^15 too;
+        // tests/cpp/test_wide_plan.cpp checks every n_live <= 64 and s <= 2^16)
         const uint32_t m_live = __builtin_amdgcn_readfirstlane((0x80000000u + n_live - 1u) / n_live);
         auto div_live = [&](uint32_t s) { return __umulhi(s << 1, m_live); };
         // kChan (small chunks, <= 16 live pixels): the ring's radiance entries are laid out per pixel —
@@ -1963,6 +1978,30 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 run += (uint32_t)__builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)miss, (int)dz)) >> 3;
             const uint32_t k = min(div_live(n_slots - oldest_s), div_live(run - (oldest_s & 3u)));  // complete frames
             if (k == 0u) return;
+            if constexpr (kWide) {
+                // every lane below npx holds a live pixel's accumulator: frames in pairs, all four channels
+                if (lane < npx) {
+                    uint32_t e = oldest_s + lane;
+                    uint32_t f = 0;
+                    for (; f + 2u <= k; f += 2u) {
+                        const uint32_t e0 = e & (kRingSlots - 1u), e1 = (e + n_live) & (kRingSlots - 1u);
+                        e += 2u * n_live;
+                        const float x0 = s_L[wave][0][e0], y0 = s_L[wave][1][e0], z0 = s_L[wave][2][e0];
+                        const float x1 = s_L[wave][0][e1], y1 = s_L[wave][1][e1], z1 = s_L[wave][2][e1];
+                        acc.x = (acc.x + x0) + x1;
+                        acc.y = (acc.y + y0) + y1;
+                        acc.z = (acc.z + z0) + z1;
+                        acc.w = (acc.w + 1.0f) + 1.0f;
+                    }
+                    if (f < k) {
+                        const uint32_t e0 = e & (kRingSlots - 1u);
+                        acc.x = acc.x + s_L[wave][0][e0];
+                        acc.y = acc.y + s_L[wave][1][e0];
+                        acc.z = acc.z + s_L[wave][2][e0];
+                        acc.w = acc.w + 1.0f;
+                    }
+                }
+            } else
             if (ch_on) {
                 // channel lanes: frames in pairs (both ring reads in flight at once), the adds in frame
                 // order; a constant pixel adds its Lc (from LDS) where a live one reads its ring entry
@@ -2260,6 +2299,10 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     }
                 } else {
                 const float4 p1 = s_px[wave][1][r];
+                // kWide: r2 from the live list (L1/L2: the wave re-reads a record once per frame), issued
+                // here so that the draws below cover its latency
+                float4 p2w = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (kWide) p2w = wrec[3u * r + 2u];
                 bool alive = true;  // a live pixel: a hit, and bounce_count 1 < max_bounces
                 if (!kBvh) {  // ... from the hit primitive's LDS shading record (make_shade_recs)
                     const uint32_t k = __float_as_uint(p1.w) & ~kHitBit;
@@ -2283,7 +2326,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     have = true;
                     nee_hit(F3{p0.x, p0.y, p0.z}, fin0);
                     if (pend) {
-                        const float4 p2 = s_px[wave][2][r];
+                        const float4 p2 = s_px[wave][kR2][r];
                         dt = F3{p2.x, p2.y, p2.z};
                     }
                     alive = false;  // (the direction follows at the sampling site)
@@ -2294,7 +2337,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     else T = rr_divide(T, cp);
                 }
                 if (alive) {
-                    const float4 p2 = s_px[wave][2][r];
+                    const float4 p2 = kWide ? p2w : s_px[wave][kR2][r];
                     dn = F3{p0.x, p0.y, p0.z};
                     dt = F3{p2.x, p2.y, p2.z};
                     pend = true;
@@ -2360,7 +2403,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         if (ch_on) {
             uint32_t ap = pix0 + cp;
             if constexpr (kView) {
-                if (view_on) ap = __float_as_uint(s_px[wave][2][cp].w);  // (a view: the record's pixel)
+                if (view_on) ap = __float_as_uint(s_px[wave][kR2][cp].w);  // (a view: the record's pixel)
             }
             float* af = reinterpret_cast<float*>(accum) + 4u * (size_t)ap + c0;
             af[0] = acc.x;
@@ -2368,7 +2411,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         } else if (!chmode && lane < npx) {
             uint32_t ap = pix0 + lane;
             if constexpr (kView) {
-                if (view_on) ap = __float_as_uint(s_px[wave][2][lane].w);
+                if (view_on) ap = __float_as_uint(kWide ? wrec[3u * lane + 2u].w : s_px[wave][kR2][lane].w);
             }
             accum[ap] = acc;
         }
@@ -3245,6 +3288,11 @@ const void* paths_kernel(const PathsVariant& v) {
         return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres>);
     }
     if (v.env > 1) return nullptr;
+    if (v.wide) {  // flat scenes over a view's lists: 64-pixel chunks, pixel lanes
+        if (v.bvh || v.simd_waves || v.chan) return nullptr;
+        if (v.stats) return env ? kp(k_paths<true, false, 1, 0, 0, false, 0, false, false, true>) : kp(k_paths<true, false, 0, 0, 0, false, 0, false, false, true>);
+        return env ? kp(k_paths<false, false, 1, 0, 0, false, 0, false, false, true>) : kp(k_paths<false, false, 0, 0, 0, false, 0, false, false, true>);
+    }
     if (v.simd_waves) {  // small BVH scenes: 8 waves per SIMD
         if (v.simd_waves != kBvhSmallWaves || !v.bvh || v.stats || v.chan) return nullptr;
         return env ? kp(k_paths<false, true, 1, 0, kBvhSmallWaves>) : kp(k_paths<false, true, 0, 0, kBvhSmallWaves>);
@@ -3316,7 +3364,8 @@ bool launch_persistent(hipFunction_t fn, const void* kernel, uint32_t grid, size
 }
 }  // namespace
 
-bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view_lists, uint32_t view_half) {
+bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan* view_lists, uint32_t view_half,
+                  int wide_call, bool* ran_wide) {
     ShadeParams sp = shade_params(p, 0u);
     CameraParams cam = camera_params(p);
     const bool bvh = p.nodes != nullptr;
@@ -3334,9 +3383,17 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
     ViewPlan view{};
     if (view_lists && view_lists->live && view_lists_scene(p)) view = *view_lists;
     ChunkPlan plan;
+    bool wide = false;
     if (view.live) {
-        const ViewChunkPlan vp = make_view_plan(p.shard_pixels, view.n_live, view.n_const, resident_waves(per_cu, p.cu_count),
-                                                p.chunks_per_wave, p.px_shift);
+        // The wide plan and kernel (64-pixel chunks), where the call asked for them and the launch is eligible.
+        // The plan is sized with the narrow kernel's occupancy asked above (both run at 7 waves per SIMD); the
+        // grid with the wide kernel's own.
+        const uint32_t waves = resident_waves(per_cu, p.cu_count);
+        wide = view.n_live != 0u && p.n_frames <= kWideMaxFrames && wide_eligible(p) &&
+               wide_launch(wide_call, make_chunk_plan(p.shard_pixels, waves, p.chunks_per_wave, p.px_shift).shift[0]);
+        // (a half of a split view comes with chunks_per_wave 0, no small tiers: a wide half gets short ones back)
+        const uint32_t cpw = wide && view_half && !p.chunks_per_wave ? kWideSplitChunksPerWave : p.chunks_per_wave;
+        const ViewChunkPlan vp = make_view_plan(p.shard_pixels, view.n_live, view.n_const, waves, cpw, p.px_shift, wide);
         plan = vp.plan;
         view.n_sweep = vp.n_sweep;
     } else {
@@ -3358,9 +3415,10 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
             record = true;
         }
     }
-    v = paths_variant(p, stats, plan.shift[0]);
-    if (v.chan) fn = jit_kernel(jit_kind(v, p.jit_shape), p);
-    const uint32_t grid = paths_grid(plan, bvh, per_cu, p.cu_count, view.n_sweep);
+    v = paths_variant(p, stats, plan.shift[0], wide);
+    if (v.chan || v.wide) fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    if (ran_wide) *ran_wide = v.wide;
+    const uint32_t grid = paths_grid(plan, bvh, v.wide ? blocks_per_cu(fn, paths_kernel(v), lds_scene) : per_cu, p.cu_count, view.n_sweep);
     void* args[] = {(void*)&p.prims, (void*)&p.mats, (void*)&p.nodes, (void*)&p.n_prims, (void*)&p.accum, (void*)&p.totals,
                     (void*)&p.work, (void*)&p.work_next, &sp, &cam, (void*)&p.n_frames, &plan, (void*)&p.nee, &view};
     const bool specialized = launch_persistent(fn, paths_kernel(v), grid, lds_scene, args, s);

@@ -23,6 +23,7 @@ struct PathsVariant {
                           // traces its camera segment; env 2 only
     bool bsdf = false;    // the kBsdf form (a scene with material models): starts every path at bounce 0 too and reads
                           // the camera's kind at run time, so `jitter` stays false; env 2, nee 0 or kNeeAll
+    bool wide = false;    // the kWide form (64-pixel chunks over a view's lists): flat, pixel lanes, no NEE; env 0 or 1
 };
 struct FrameVariant {
     bool stats, bvh;
@@ -38,8 +39,9 @@ inline int nee_variant(const PassParams& p) {
     if (p.nee.n_emit == 0u) return 0;
     return p.nodes != nullptr && p.nee.spheres == 0u ? kNeeNoSpheres : kNeeAll;
 }
-// first_shift: the chunk plan's shift[0]
-inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t first_shift) {
+// first_shift: the chunk plan's shift[0]; wide: the launch runs a view's wide plan (wide_launch: flat, no NEE,
+// a per-pixel camera ray, no material models)
+inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t first_shift, bool wide = false) {
     const bool bvh = p.nodes != nullptr;
     const int nee = nee_variant(p);
     PathsVariant v{stats, bvh, nee ? 2 : (p.env ? 1 : 0), 0, false, nee};
@@ -56,6 +58,8 @@ inline PathsVariant paths_variant(const PassParams& p, bool stats, uint32_t firs
     }
     if (bvh && !stats && !nee && p.n_prims <= kBvhSmall) v.simd_waves = kBvhSmallWaves;
     v.chan = !bvh && !stats && !nee && first_shift < kMaxChunkShift;
+    v.wide = wide && !bvh && !nee;
+    if (v.wide) v.chan = false;  // (its small tiers run in the wide kernel's pixel lanes)
     return v;
 }
 inline FrameVariant frame_variant(const PassParams& p, bool stats) {
@@ -84,6 +88,10 @@ struct JitKind {
 constexpr JitKind kJitNone{-1, 0};
 inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
     if (!shape || v.bvh || v.jitter || v.bsdf) return kJitNone;
+    if (v.wide) {
+        if (v.stats) return flat_shape_pairs(shape) ? JitKind{kJitPathsWideStats, v.env} : kJitNone;
+        return JitKind{kJitPathsWide, v.env};
+    }
     if (v.stats) return flat_shape_pairs(shape) ? JitKind{v.nee ? kJitPathsNeeStats : kJitPathsStats, v.env} : kJitNone;
     return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
 }
@@ -94,12 +102,14 @@ inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
 // The kinds a flat scene's renders may ask for: compiled ahead by spt_set_scene, waited for by
 // spt_specialize_scene. (The two kRgba kinds are not in the list: a fused resolve compiles its kernel
 // on first use. Adding them here is the whole change, but it changes what a scene change compiles.)
+// wide: the ctx may run wide launches (wide_possible), so the wide k_paths is compiled ahead too
 struct JitKindList {
     int n;
-    JitKind k[3];
+    JitKind k[4];
 };
-inline JitKindList jit_kinds_of_scene(bool nee, int env) {
+inline JitKindList jit_kinds_of_scene(bool nee, int env, bool wide = false) {
     if (nee) return {2, {{kJitPathsNee, 2}, {kJitFrameNee, 2}}};
+    if (wide) return {4, {{kJitPaths, env}, {kJitFrame, env}, {kJitPathsChan, env}, {kJitPathsWide, env}}};
     return {3, {{kJitPaths, env}, {kJitFrame, env}, {kJitPathsChan, env}}};
 }
 
@@ -161,13 +171,17 @@ struct ViewChunkPlan {
     ChunkPlan plan;
     uint32_t n_sweep;
 };
+// wide (the kWide kernel; never with px_shift): a first tier of kWidePx-pixel chunks whatever the pixel plan's
+// is, over tiers of 32 and 16 pixels sized by the same rule; the tiers below the first stay <= 32 pixels.
 inline ViewChunkPlan make_view_plan(uint32_t shard_pixels, uint32_t live, uint32_t constant, uint32_t resident_waves,
-                                    uint32_t chunks_per_wave, uint32_t px_shift) {
+                                    uint32_t chunks_per_wave, uint32_t px_shift, bool wide = false) {
     ViewChunkPlan vp{};
     ChunkPlan& plan = vp.plan;
     vp.n_sweep = (constant + kViewSweep - 1u) / kViewSweep;
     const ChunkPlan pixel_plan = make_chunk_plan(shard_pixels, resident_waves, chunks_per_wave, px_shift);
-    const uint32_t s0 = pixel_plan.shift[0], s1 = pixel_plan.shift[1], s2 = pixel_plan.shift[2];
+    wide = wide && !px_shift;
+    const uint32_t s0 = wide ? kWideShift : pixel_plan.shift[0], s1 = wide ? kWideShift - 1u : pixel_plan.shift[1],
+                   s2 = wide ? kWideShift - 2u : pixel_plan.shift[2];
     plan.shift[0] = s0;
     plan.shift[1] = s1;
     plan.shift[2] = s2;
@@ -177,8 +191,12 @@ inline ViewChunkPlan make_view_plan(uint32_t shard_pixels, uint32_t live, uint32
     }
     // chunks per small tier
     const uint64_t tail = shard_pixels ? (uint64_t)chunks_per_wave * resident_waves * live / shard_pixels : 0u;
-    const uint32_t c_px = kViewTier8 ? (uint32_t)std::min<uint64_t>(live, tail << s2) : 0u;
-    const uint32_t b_px = kViewTier16 ? (uint32_t)std::min<uint64_t>(live - c_px, tail << s1) & ~((1u << s1) - 1u) : 0u;
+    // (a wide plan's small tiers take a quarter of the live list each at most, so its first tier exists: the cap
+    // binds only where wide chunks are forced on an image below the automatic rule's — there the pixel plan's
+    // first tier is 32 pixels, P >= 256 x the resident waves, so tail << s1 <= chunks_per_wave x live / 8)
+    const uint64_t cap = wide ? live / 4u : live;
+    const uint32_t c_px = kViewTier8 ? (uint32_t)std::min<uint64_t>(cap, tail << s2) : 0u;
+    const uint32_t b_px = kViewTier16 ? (uint32_t)std::min<uint64_t>(std::min<uint64_t>(cap, live - c_px), tail << s1) & ~((1u << s1) - 1u) : 0u;
     const uint32_t a_px = (live - c_px - b_px) & ~((1u << s0) - 1u);
     plan.n[0] = a_px >> s0;
     plan.n[1] = b_px >> s1;
@@ -211,7 +229,9 @@ inline uint32_t split_cut(uint32_t n, uint32_t unit) {
     const uint64_t cut = ((uint64_t)n / 2u + unit / 2u) / unit * unit;
     return (uint32_t)std::min<uint64_t>(cut, n);
 }
-inline ViewSplit make_view_split(uint32_t n_live, uint32_t n_const, uint32_t first_tier_px) {
+// (first_tier_px: 1 << kMaxChunkShift, or kWidePx for a call whose launches may be wide — a multiple of every
+// smaller chunk size, so the cut suits a launch of the call that runs the narrow plan after all)
+inline ViewSplit make_view_split(uint32_t n_live, uint32_t n_const, uint32_t first_tier_px = 1u << kMaxChunkShift) {
     return ViewSplit{{0u, split_cut(n_live, first_tier_px), n_live}, {0u, split_cut(n_const, kViewSweep), n_const}};
 }
 // Whether the launches of one spt_render call over a cached view are split (spt_tuning.split_streams: knob).
@@ -226,6 +246,44 @@ constexpr uint64_t kSplitMinLiveFrames = 1ull << 24;
 inline bool split_call_wanted(int32_t knob, uint32_t n_live, uint32_t call_frames, uint32_t max_launch_frames) {
     if (knob) return knob > 0;
     return (uint64_t)n_live * std::min(call_frames, max_launch_frames) >= kSplitMinLiveFrames;
+}
+// Wide launches (spt_tuning.wide_chunks: knob; the kWide k_paths, 64-pixel chunks over a view's lists).
+// Eligible: a flat scene with a per-pixel camera ray and no material models (the view's lists exist), no NEE,
+// no forced chunk size, and a whole image: a row shard's launches hold world x the frames over 1 / world of the
+// pixels and need their small chunks (make_chunk_plan), so they keep them (not measured otherwise).
+// wide_call: decided once per call, as the split is (the cut of the live list and the frames per launch follow
+// it): 0 no, 1 automatic (each launch then checks that the pixel plan's first tier is 32 pixels with the
+// occupancy it asked: wide_launch), 2 forced on. Automatic: an image whose pixel plan starts with 32-pixel
+// chunks (wide_first_tier: with the flat kernels' 7 blocks per CU) and launches of at least kWideMinLiveFrames
+// live-pixel frames. Forced on against forced off at Cornell 1080p: 4 frames per call (3.2 M, the
+// persistent schedule's shortest call) +21.8 %, 8 (6.4 M) +14.5 %, 16 (12.9 M) +5.7 %, 32 (25.8 M) +5.3 %, 64 (51.6 M) +1.9 to +2.6 %, 128 (103 M) +0.4 %; 4K x 16 (51.6 M)
+// +13.7 %; 720p x 64, whose plan starts with 16-pixel chunks, -15 %. The threshold sits just below the smallest
+// launch measured; nothing was measured below it.
+constexpr uint64_t kWideMinLiveFrames = 3ull << 20;  // 3.15 M
+constexpr int kWideBlocksPerCu = 7;  // the flat k_paths' blocks per CU (7 waves/SIMD), for the per-call estimate
+inline bool wide_first_tier(uint32_t shard_pixels, uint32_t cu_count) {
+    return make_chunk_plan(shard_pixels, (uint32_t)kWideBlocksPerCu * cu_count * (kBlock / 64u), 0u, 0u).shift[0] == kMaxChunkShift;
+}
+// The halves of a split view run without small tiers (spt_capi.hip launch_paths_split). A wide half has half as
+// many first-tier chunks — Cornell 1080p: 6,296 for 7,168 resident waves — so its end is coarser, and one
+// chunk per wave and small tier (32 and 16 pixels) pays: C2 +0.6 % over none, 2 chunks the same as none
+// (profiles/wide_chunks_rates.txt).
+constexpr uint32_t kWideSplitChunksPerWave = 1;
+inline bool wide_eligible(const PassParams& p) {
+    return view_lists_scene(p) && nee_variant(p) == 0 && p.shard_count <= 1u && p.px_shift == 0u;
+}
+inline int wide_call(int32_t knob, bool eligible, bool first_tier_32, uint32_t n_live, uint32_t call_frames) {
+    if (knob < 0 || !eligible) return 0;
+    if (knob > 0) return 2;
+    return first_tier_32 && (uint64_t)n_live * std::min(call_frames, kWideMaxFrames) >= kWideMinLiveFrames ? 1 : 0;
+}
+inline bool wide_launch(int wide_call, uint32_t pixel_first_shift) {
+    return wide_call == 2 || (wide_call == 1 && pixel_first_shift == kMaxChunkShift);
+}
+// whether a ctx of this many shard pixels can run a wide launch at all (its kernel is then compiled ahead)
+inline bool wide_possible(int32_t knob, uint32_t shard_pixels, uint32_t shard_count, uint32_t cu_count) {
+    if (knob < 0 || shard_count > 1u) return false;
+    return knob > 0 || (wide_first_tier(shard_pixels, cu_count) && (uint64_t)shard_pixels * kWideMaxFrames >= kWideMinLiveFrames);
 }
 inline bool view_half_empty(const ViewSplit& s, uint32_t h) {
     return s.live_at[h + 1] == s.live_at[h] && s.const_at[h + 1] == s.const_at[h];
