@@ -629,8 +629,8 @@ static bool wide_possible_ctx(const spt_ctx* c) {
 static void prefetch_flat(const spt_ctx* c) {
     if (!(c->has_scene && c->configured && c->n_prims && c->n_nodes == 0 && c->specialize == 0)) return;
     const uint64_t key = flat_jit_key(c);
-    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
-    for (int i = 0; i < kinds.n; ++i) jit_prefetch(kinds.k[i].kind, kinds.k[i].env, key);
+    const JitFormList forms = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
+    for (int i = 0; i < forms.n; ++i) jit_prefetch(forms.f[i], key);
 }
 
 PassParams base_params(spt_ctx* c) {
@@ -2177,9 +2177,9 @@ int spt_specialize_scene(spt_ctx* c) {
     SPT_HIP(c, hipSetDevice(c->device));
     const uint64_t key = flat_jit_key(c);  // (before spt_configure: the shape alone)
     std::string err;
-    const JitKindList kinds = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
-    for (int i = 0; i < kinds.n; ++i)
-        if (!jit_function(kinds.k[i].kind, kinds.k[i].env, key, &err))
+    const JitFormList forms = jit_kinds_of_scene(nee_active(c), c->d_env ? 1 : 0, wide_possible_ctx(c));
+    for (int i = 0; i < forms.n; ++i)
+        if (!jit_function(forms.f[i], key, &err))
             return fail(c, SPT_ERR_HIP, ("specialized kernels unavailable (the generic ones run): " + err).c_str());
     return SPT_OK;
 }
@@ -2198,10 +2198,10 @@ int spt_compile_flat_kernels(const spt_prim* prims, uint32_t n_prims, int env_ma
     const uint32_t flat_rect = flat_rect_bits(sorted, ends);
     const uint64_t key = flat_shape_key(flat_ends, n_prims, flat_rect, flat_wall_pairs(sorted, ends, flat_rect));
     std::string out;
-    const JitKindList kinds = jit_kinds_of_scene(false, env_map ? 1 : 0);  // (no emitters known here: the kinds without NEE)
+    const JitFormList forms = jit_kinds_of_scene(false, env_map ? 1 : 0);  // (no emitters known here: the forms without NEE)
     int built = 0;
-    while (built < kinds.n && jit_compile(kinds.k[built].kind, kinds.k[built].env, key, &out)) ++built;
-    if (built == kinds.n) return SPT_OK;
+    while (built < forms.n && jit_compile(forms.f[built], key, &out)) ++built;
+    if (built == forms.n) return SPT_OK;
     if (log && log_bytes) {
         std::strncpy(log, out.c_str(), log_bytes - 1);
         log[log_bytes - 1] = 0;

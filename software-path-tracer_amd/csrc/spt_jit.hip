@@ -38,8 +38,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "spt_jit.h"
-#include "spt_jit_src.inc"  // kJitSources: {file name, text} of spt_kernels.hip and its headers
+#include "spt_launch_plan.h"  // spt_jit.h, jit_name_expr
+#include "spt_jit_src.inc"  // kKernelSources: {file name, text} of spt_kernels.hip and its headers
 
 namespace spt {
 namespace {
@@ -117,7 +117,7 @@ struct Program {
 #define SPT_DEFAULT_ARCH "gfx950"  // Makefile ARCH: the offline build's target, used without a device
 #endif
 
-using CodeKey = std::tuple<std::string, int, int, uint64_t>;  // (arch, kernel, env, shape)
+using CodeKey = std::tuple<std::string, bool, int, uint64_t>;  // (arch, k_frame, variant code, shape): JitForm
 
 // Process-lifetime state, never destroyed: the compile worker may still run while static destructors
 // would otherwise tear it down (it is stopped and joined at exit, see stop_worker).
@@ -125,7 +125,7 @@ struct JitState {
     std::mutex mu;
     std::condition_variable cv;
     std::map<CodeKey, Program> code;
-    std::map<std::tuple<int, int, int, uint64_t>, hipFunction_t> fns;  // (device, kernel, env, shape)
+    std::map<std::tuple<int, bool, int, uint64_t>, hipFunction_t> fns;  // (device, k_frame, variant code, shape)
     std::deque<CodeKey> queue;  // compiles waiting for the worker
     std::thread worker;
     bool started = false, stop = false, rtc_known = false;
@@ -163,7 +163,7 @@ void at_fork_child() {
     g_rtc = nullptr;
 }
 
-Program compile_now(const std::string& arch, int kernel, int env, uint64_t shape);
+Program compile_now(const std::string& arch, JitForm form, uint64_t shape);
 
 // The one thread that loads hiprtc and runs every compile, in queue order.
 void worker_main() {
@@ -184,7 +184,7 @@ void worker_main() {
             key = st().queue.front();
             st().queue.pop_front();
         }
-        Program p = compile_now(std::get<0>(key), std::get<1>(key), std::get<2>(key), std::get<3>(key));
+        Program p = compile_now(std::get<0>(key), JitForm{std::get<1>(key), std::get<2>(key)}, std::get<3>(key));
         std::lock_guard<std::mutex> lock(st().mu);
         p.state = 2;
         st().code[key] = std::move(p);
@@ -233,13 +233,13 @@ std::string device_arch(int device) {
 }
 
 // One hiprtc compile (no lock held).
-Program compile_now(const std::string& arch, int kernel, int env, uint64_t shape) {
+Program compile_now(const std::string& arch, JitForm form, uint64_t shape) {
     Program out;
-    const std::string expr = jit_name_expr(kernel, env, shape);
+    const std::string expr = jit_name_expr(form, shape);
     std::vector<const char*> hdr_src, hdr_name;
-    for (size_t i = 1; i < kJitSourceCount; ++i) {
-        hdr_name.push_back(kJitSources[i].name);
-        hdr_src.push_back(kJitSources[i].text);
+    for (size_t i = 1; i < kKernelSourceCount; ++i) {
+        hdr_name.push_back(kKernelSources[i].name);
+        hdr_src.push_back(kKernelSources[i].text);
     }
     const Rtc& rt = rtc();
     if (!rt.ok) {
@@ -247,7 +247,7 @@ Program compile_now(const std::string& arch, int kernel, int env, uint64_t shape
         return out;
     }
     hiprtcProgram prog;
-    if (rt.create(&prog, kJitSources[0].text, kJitSources[0].name, (int)hdr_src.size(), hdr_src.data(),
+    if (rt.create(&prog, kKernelSources[0].text, kKernelSources[0].name, (int)hdr_src.size(), hdr_src.data(),
                   hdr_name.data()) != HIPRTC_SUCCESS) {
         out.log = "hiprtcCreateProgram failed";
         return out;
@@ -327,33 +327,33 @@ std::string jit_compiler() {
     return st().compiler;
 }
 
-bool jit_compile(int kernel, int env, uint64_t shape, std::string* log, std::vector<char>* code) {
+bool jit_compile(JitForm form, uint64_t shape, std::string* log, std::vector<char>* code) {
     std::unique_lock<std::mutex> lock(st().mu);
-    const Program* p = get_program(lock, CodeKey{SPT_DEFAULT_ARCH, kernel, env, shape}, true);
+    const Program* p = get_program(lock, CodeKey{SPT_DEFAULT_ARCH, form.frame, form.code, shape}, true);
     if (log) *log = p->log;
     if (code) *code = p->code;
     return !p->code.empty();
 }
 
-void jit_prefetch(int kernel, int env, uint64_t shape) {
+void jit_prefetch(JitForm form, uint64_t shape) {
     int device = 0;
     const std::string arch = hipGetDevice(&device) == hipSuccess ? device_arch(device) : std::string(SPT_DEFAULT_ARCH);
     std::unique_lock<std::mutex> lock(st().mu);
-    (void)get_program(lock, CodeKey{arch, kernel, env, shape}, false);
+    (void)get_program(lock, CodeKey{arch, form.frame, form.code, shape}, false);
 }
 
-bool jit_ready(int kernel, int env, uint64_t shape) {
+bool jit_ready(JitForm form, uint64_t shape) {
     int device = 0;
     const std::string arch = hipGetDevice(&device) == hipSuccess ? device_arch(device) : std::string(SPT_DEFAULT_ARCH);
     std::lock_guard<std::mutex> lock(st().mu);
-    auto it = st().code.find(CodeKey{arch, kernel, env, shape});
+    auto it = st().code.find(CodeKey{arch, form.frame, form.code, shape});
     return it != st().code.end() && it->second.state == 2;
 }
 
-hipFunction_t jit_function(int kernel, int env, uint64_t shape, std::string* err, bool wait) {
+hipFunction_t jit_function(JitForm form, uint64_t shape, std::string* err, bool wait) {
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    const auto fkey = std::make_tuple(device, kernel, env, shape);
+    const auto fkey = std::make_tuple(device, form.frame, form.code, shape);
     {
         std::lock_guard<std::mutex> lock(st().mu);
         auto it = st().fns.find(fkey);
@@ -363,7 +363,7 @@ hipFunction_t jit_function(int kernel, int env, uint64_t shape, std::string* err
     std::unique_lock<std::mutex> lock(st().mu);
     auto it = st().fns.find(fkey);
     if (it != st().fns.end()) return it->second;
-    const Program* p = get_program(lock, CodeKey{arch, kernel, env, shape}, wait);
+    const Program* p = get_program(lock, CodeKey{arch, form.frame, form.code, shape}, wait);
     if (!p) return nullptr;  // still compiling in the background: the caller runs its generic kernel
     hipFunction_t fn = nullptr;
     if (!p->code.empty()) {

@@ -3121,8 +3121,10 @@ __global__ __launch_bounds__(kBlock) void k_view_lists(const float4* __restrict_
 // host launchers
 #ifndef __HIPCC_RTC__
 }  // namespace spt
+#include <array>
 #include <cassert>
 #include <type_traits>
+#include <utility>
 
 #include "spt_denoise.h"
 #include "spt_launch_plan.h"
@@ -3258,94 +3260,31 @@ const void* kp(K* kernel) {
     return (const void*)kernel;
 }
 
-// The offline-compiled k_paths of a variant: every instantiation the library holds is named here, once.
-// nullptr: no such kernel (paths_variant never asks for one).
-const void* paths_kernel(const PathsVariant& v) {
-    const bool env = v.env == 1;
-    if (v.bsdf) {  // the kBsdf forms (they read the camera's kind at run time): as the kJitter ones, and every emitter kind
-        if (v.env != 2 || v.simd_waves || v.chan || v.jitter || v.nee == kNeeNoSpheres) return nullptr;
-        if (!v.bvh) {
-            if (v.nee) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll, false, true>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll, false, true>);
-            return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, 0, false, true>) : kp(k_paths<false, false, 2, 0, 0, false, 0, false, true>);
-        }
-        if (v.nee) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll, false, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll, false, true>);
-        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, 0, false, true>) : kp(k_paths<false, true, 2, 0, 0, false, 0, false, true>);
-    }
-    if (v.jitter) {  // the kJitter forms: the sky's kind at run time, no 8-wave and no channel-lane kernel
-        if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee == kNeeNoSpheres)) return nullptr;
-        if (!v.bvh) {
-            if (v.nee) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll, true>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll, true>);
-            return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, 0, true>) : kp(k_paths<false, false, 2, 0, 0, false, 0, true>);
-        }
-        if (v.nee == kNeeAll) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll, true>);
-        if (v.nee) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres, true>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres, true>);
-        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, 0, true>) : kp(k_paths<false, true, 2, 0, 0, false, 0, true>);
-    }
-    if (v.nee) {  // the sky's kind decided at run time (kEnv 2); BVH: the sphere sample compiled in only when needed
-        if (v.env != 2 || v.simd_waves || v.chan || (!v.bvh && v.nee != kNeeAll)) return nullptr;
-        if (!v.bvh) return v.stats ? kp(k_paths<true, false, 2, 0, 0, false, kNeeAll>) : kp(k_paths<false, false, 2, 0, 0, false, kNeeAll>);
-        if (v.nee == kNeeAll) return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeAll>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeAll>);
-        return v.stats ? kp(k_paths<true, true, 2, 0, 0, false, kNeeNoSpheres>) : kp(k_paths<false, true, 2, 0, 0, false, kNeeNoSpheres>);
-    }
-    if (v.env > 1) return nullptr;
-    if (v.wide) {  // flat scenes over a view's lists: 64-pixel chunks, pixel lanes
-        if (v.bvh || v.simd_waves || v.chan) return nullptr;
-        if (v.stats) return env ? kp(k_paths<true, false, 1, 0, 0, false, 0, false, false, true>) : kp(k_paths<true, false, 0, 0, 0, false, 0, false, false, true>);
-        return env ? kp(k_paths<false, false, 1, 0, 0, false, 0, false, false, true>) : kp(k_paths<false, false, 0, 0, 0, false, 0, false, false, true>);
-    }
-    if (v.simd_waves) {  // small BVH scenes: 8 waves per SIMD
-        if (v.simd_waves != kBvhSmallWaves || !v.bvh || v.stats || v.chan) return nullptr;
-        return env ? kp(k_paths<false, true, 1, 0, kBvhSmallWaves>) : kp(k_paths<false, true, 0, 0, kBvhSmallWaves>);
-    }
-    if (v.chan) {  // flat scenes, chunks of <= 16 pixels: the channel-lane kernel
-        if (v.bvh || v.stats) return nullptr;
-        return env ? kp(k_paths<false, false, 1, 0, 0, true>) : kp(k_paths<false, false, 0, 0, 0, true>);
-    }
-    if (v.stats) return v.bvh ? (env ? kp(k_paths<true, true, 1>) : kp(k_paths<true, true, 0>))
-                              : (env ? kp(k_paths<true, false, 1>) : kp(k_paths<true, false, 0>));
-    return v.bvh ? (env ? kp(k_paths<false, true, 1>) : kp(k_paths<false, true, 0>))
-                 : (env ? kp(k_paths<false, false, 1>) : kp(k_paths<false, false, 0>));
+// The offline-compiled k_paths / k_frame of a variant. The library holds the instantiation of every variant that
+// paths_built / frame_built accept (spt_launch_plan.h) and of no other: one table per kernel, indexed by the
+// variant's code, made once when the library is loaded. nullptr: no such kernel (paths_variant /
+// frame_variant never ask for one).
+template <class F, size_t... kCode>
+std::array<const void*, sizeof...(kCode)> kernel_table(F instance, std::index_sequence<kCode...>) {
+    return {instance(std::integral_constant<int, (int)kCode>{})...};
 }
-
-// ... and k_frame's: 16 without the fused resolve, 9 with it (kRgba has no stats form)
-const void* frame_kernel(const FrameVariant& v) {
-    const bool env = v.env == 1;
-    if (v.bsdf) {  // the kBsdf forms: kEnv 2, never the LDS-held form, every emitter kind; 8 and 4 with the fused resolve
-        if (v.env != 2 || v.small || v.nee == kNeeNoSpheres || (v.rgba && v.stats)) return nullptr;
-        if (v.rgba) {
-            if (v.nee) return v.bvh ? kp(k_frame<false, true, 2, 0, false, kNeeAll, true, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, true, true>);
-            return v.bvh ? kp(k_frame<false, true, 2, 0, false, 0, true, true>) : kp(k_frame<false, false, 2, 0, false, 0, true, true>);
-        }
-        if (v.nee) {
-            if (v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeAll, false, true>) : kp(k_frame<false, true, 2, 0, false, kNeeAll, false, true>);
-            return v.stats ? kp(k_frame<true, false, 2, 0, false, kNeeAll, false, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, false, true>);
-        }
-        if (v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, 0, false, true>) : kp(k_frame<false, true, 2, 0, false, 0, false, true>);
-        return v.stats ? kp(k_frame<true, false, 2, 0, false, 0, false, true>) : kp(k_frame<false, false, 2, 0, false, 0, false, true>);
-    }
-    if (v.nee ? (v.env != 2 || v.small || (!v.bvh && v.nee != kNeeAll)) : v.env > 1) return nullptr;
-    if (v.small && (!v.bvh || v.stats)) return nullptr;
-    if (v.rgba) {
-        if (v.stats) return nullptr;
-        if (v.nee == kNeeNoSpheres) return kp(k_frame<false, true, 2, 0, false, kNeeNoSpheres, true>);
-        if (v.nee) return v.bvh ? kp(k_frame<false, true, 2, 0, false, kNeeAll, true>) : kp(k_frame<false, false, 2, 0, false, kNeeAll, true>);
-        if (v.small) return env ? kp(k_frame<false, true, 1, 0, true, 0, true>) : kp(k_frame<false, true, 0, 0, true, 0, true>);
-        return v.bvh ? (env ? kp(k_frame<false, true, 1, 0, false, 0, true>) : kp(k_frame<false, true, 0, 0, false, 0, true>))
-                     : (env ? kp(k_frame<false, false, 1, 0, false, 0, true>) : kp(k_frame<false, false, 0, 0, false, 0, true>));
-    }
-    if (v.nee == kNeeNoSpheres) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeNoSpheres>) : kp(k_frame<false, true, 2, 0, false, kNeeNoSpheres>);
-    if (v.nee && v.bvh) return v.stats ? kp(k_frame<true, true, 2, 0, false, kNeeAll>) : kp(k_frame<false, true, 2, 0, false, kNeeAll>);
-    if (v.nee) return v.stats ? kp(k_frame<true, false, 2, 0, false, kNeeAll>) : kp(k_frame<false, false, 2, 0, false, kNeeAll>);
-    if (v.small) return env ? kp(k_frame<false, true, 1, 0, true>) : kp(k_frame<false, true, 0, 0, true>);
-    if (v.stats) return v.bvh ? (env ? kp(k_frame<true, true, 1>) : kp(k_frame<true, true, 0>))
-                              : (env ? kp(k_frame<true, false, 1>) : kp(k_frame<true, false, 0>));
-    return v.bvh ? (env ? kp(k_frame<false, true, 1>) : kp(k_frame<false, true, 0>))
-                 : (env ? kp(k_frame<false, false, 1>) : kp(k_frame<false, false, 0>));
-}
+const auto kPathsKernels = kernel_table([](auto code) -> const void* {
+    constexpr PathsVariant v = paths_of_code(decltype(code)::value);
+    if constexpr (paths_built(v)) return kp(k_paths<v.stats, v.bvh, v.env, 0, v.simd_waves, v.chan, v.nee, v.jitter, v.bsdf, v.wide>);
+    else return nullptr;
+}, std::make_index_sequence<kPathsCodes>{});
+const auto kFrameKernels = kernel_table([](auto code) -> const void* {  // (v.jitter is no template argument: both values name the same kernel)
+    constexpr FrameVariant v = frame_of_code(decltype(code)::value);
+    if constexpr (frame_built(v)) return kp(k_frame<v.stats, v.bvh, v.env, 0, v.small, v.nee, v.rgba, v.bsdf>);
+    else return nullptr;
+}, std::make_index_sequence<kFrameCodes>{});
+static_assert(paths_built_count() == 40 && frame_built_count() == 37, "a form was added or lost: say so here and in DESIGN.md");
+const void* paths_kernel(const PathsVariant& v) { return kPathsKernels[(size_t)paths_code(v)]; }
+const void* frame_kernel(const FrameVariant& v) { return kFrameKernels[(size_t)frame_code(v)]; }
 
 // the specialized kernel of a variant on the current device, or nullptr: none, not compiled yet, or not buildable
-hipFunction_t jit_kernel(JitKind k, const PassParams& p) {
-    return k.kind < 0 ? nullptr : jit_function(k.kind, k.env, p.jit_shape, nullptr, p.jit_wait != 0u);
+hipFunction_t jit_kernel(JitForm f, const PassParams& p) {
+    return f ? jit_function(f, p.jit_shape, nullptr, p.jit_wait != 0u) : nullptr;
 }
 // blocks resident per CU of the specialized kernel if there is one, else of `kernel`
 int blocks_per_cu(hipFunction_t fn, const void* kernel, size_t lds) {
@@ -3376,7 +3315,7 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
     // without kChan (first_shift = kMaxChunkShift), also when the kChan kernel then runs. Whether asking
     // the launched kernel for the grid would be better is not measured.
     PathsVariant v = paths_variant(p, stats, kMaxChunkShift);
-    hipFunction_t fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    hipFunction_t fn = jit_kernel(jit_form(v, p.jit_shape), p);
     const int per_cu = blocks_per_cu(fn, paths_kernel(v), lds_scene);
     // A view's lists (flat scenes, ViewPlan): the plan over the live list and the sweep units. Its first
     // tier has the pixel plan's chunk size, so the kernel chosen below is the pixel plan's too.
@@ -3416,7 +3355,7 @@ bool launch_paths(const PassParams& p, bool stats, hipStream_t s, const ViewPlan
         }
     }
     v = paths_variant(p, stats, plan.shift[0], wide);
-    if (v.chan || v.wide) fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    if (v.chan || v.wide) fn = jit_kernel(jit_form(v, p.jit_shape), p);
     if (ran_wide) *ran_wide = v.wide;
     const uint32_t grid = paths_grid(plan, bvh, v.wide ? blocks_per_cu(fn, paths_kernel(v), lds_scene) : per_cu, p.cu_count, view.n_sweep);
     void* args[] = {(void*)&p.prims, (void*)&p.mats, (void*)&p.nodes, (void*)&p.n_prims, (void*)&p.accum, (void*)&p.totals,
@@ -3436,7 +3375,7 @@ bool launch_frame(const PassParams& p, bool stats, hipStream_t s) {
     const FrameVariant v = frame_variant(p, stats);
     const size_t lds_scene = v.bvh ? (v.small ? sizeof(uint2) * kBlock * std::max(1u, p.stack_need) : 0)
                                    : sizeof(float4) * 3u * p.n_prims;  // LDS stacks / make_shade_recs
-    const hipFunction_t fn = jit_kernel(jit_kind(v, p.jit_shape), p);
+    const hipFunction_t fn = jit_kernel(jit_form(v, p.jit_shape), p);
     // Without a specialized kernel the occupancy asked is that of the variant WITHOUT the fused resolve
     // (kRgba), also when the kRgba kernel then runs: its grid is sized as the plain frame's. Whether
     // asking the launched kernel would be better is not measured.

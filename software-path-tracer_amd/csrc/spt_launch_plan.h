@@ -1,18 +1,21 @@
 // spt_launch_plan.h — what launch_paths / launch_frame decide before they launch: which instantiation
-// of k_paths / k_frame runs, its run-time compiled form (spt_jit.h), the chunk plan and the grids.
+// of k_paths / k_frame runs, which the library holds, its run-time compiled form (spt_jit.h), the chunk plan and the grids.
 // Pure host functions, no HIP runtime calls: tests/cpp/test_launch_plan.cpp checks them without a
 // GPU. Every variant computes the same image bits, so a wrong choice here shows only as lost speed.
 // Not part of the kernel source compiled at run time. Internal.
 #pragma once
 
 #include <algorithm>
+#include <string>
 
 #include "spt_jit.h"
 #include "spt_kernels.h"
 
 namespace spt {
 
-// k_paths<stats, bvh, env, shape, simd_waves, chan, nee, jitter> / k_frame<stats, bvh, env, shape, small, nee, rgba>
+// A form of the persistent kernels is described by one of these values and nothing else (shape: 0 in the
+// library's own kernels, a flat scene's in the ones compiled at run time; k_frame's jitter is no argument):
+// k_paths<stats, bvh, env, shape, simd_waves, chan, nee, jitter, bsdf, wide> / k_frame<stats, bvh, env, shape, small, nee, rgba, bsdf>
 struct PathsVariant {
     bool stats, bvh;
     int env;         // 0 gradient sky, 1 environment map, 2 decided at run time (the NEE kernels)
@@ -34,6 +37,69 @@ struct FrameVariant {
     bool jitter = false;  // a per-path camera ray (cam_per_path): the same kernels on hit_mode 0 (no camera-hit cache, no lists)
     bool bsdf = false;    // the kBsdf kernels (a scene with material models): hit_mode 0, env 2, never `small`
 };
+constexpr bool operator==(const PathsVariant& a, const PathsVariant& b) {
+    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.simd_waves == b.simd_waves && a.chan == b.chan &&
+           a.nee == b.nee && a.jitter == b.jitter && a.bsdf == b.bsdf && a.wide == b.wide;
+}
+constexpr bool operator==(const FrameVariant& a, const FrameVariant& b) {
+    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.small == b.small && a.nee == b.nee &&
+           a.rgba == b.rgba && a.jitter == b.jitter && a.bsdf == b.bsdf;
+}
+
+// A variant's code: its fields as the digits of a mixed-radix number, the first field the most significant
+// (env and nee: 0, 1, 2; simd_waves: 0 or kBvhSmallWaves). paths_of_code / frame_of_code are the inverses:
+// each field is the code over the product of the radices behind it, modulo its own.
+constexpr int kPathsCodes = 2 * 2 * 3 * 2 * 2 * 3 * 2 * 2 * 2;
+constexpr int kFrameCodes = 2 * 2 * 3 * 2 * 3 * 2 * 2 * 2;
+constexpr int paths_code(const PathsVariant& v) {
+    return (((((((v.stats * 2 + v.bvh) * 3 + v.env) * 2 + (v.simd_waves != 0)) * 2 + v.chan) * 3 + v.nee) * 2 + v.jitter) * 2 + v.bsdf) * 2 + v.wide;
+}
+constexpr PathsVariant paths_of_code(int c) {
+    return PathsVariant{c / 576 % 2 != 0, c / 288 % 2 != 0, c / 96 % 3, c / 48 % 2 ? kBvhSmallWaves : 0, c / 24 % 2 != 0, c / 8 % 3,
+                        c / 4 % 2 != 0, c / 2 % 2 != 0, c % 2 != 0};
+}
+constexpr int frame_code(const FrameVariant& v) {
+    return ((((((v.stats * 2 + v.bvh) * 3 + v.env) * 2 + v.small) * 3 + v.nee) * 2 + v.rgba) * 2 + v.jitter) * 2 + v.bsdf;
+}
+constexpr FrameVariant frame_of_code(int c) {
+    return FrameVariant{c / 288 % 2 != 0, c / 144 % 2 != 0, c / 48 % 3, c / 24 % 2 != 0, c / 8 % 3, c / 4 % 2 != 0, c / 2 % 2 != 0, c % 2 != 0};
+}
+
+// Whether the library holds a k_paths / k_frame of the variant (compiled offline, shape 0): the rules by which
+// spt_kernels.hip instantiates its kernel table. paths_variant / frame_variant ask for these only.
+constexpr bool paths_built(const PathsVariant& v) {
+    if (v.bsdf || v.jitter || v.nee) {
+        // the sky's kind read at run time (env 2); pixel lanes at the kernel's own occupancy, 32-pixel chunks at most
+        if (v.env != 2 || v.simd_waves || v.chan || v.wide) return false;
+        // kBsdf reads the camera's kind at run time (no kJitter of its own) and samples every emitter kind
+        if (v.bsdf) return !v.jitter && v.nee != kNeeNoSpheres;
+        return v.bvh || v.nee != kNeeNoSpheres;  // (the sphere sample is left out of BVH kernels only)
+    }
+    if (v.env == 2) return false;
+    if (v.wide) return !v.bvh && !v.simd_waves && !v.chan;       // flat scenes over a view's lists, pixel lanes
+    if (v.simd_waves) return v.bvh && !v.stats && !v.chan;       // small BVH scenes: 8 waves per SIMD
+    if (v.chan) return !v.bvh && !v.stats;                       // flat scenes, chunks of <= 16 pixels
+    return true;
+}
+// (`jitter` selects no kernel of its own: both values name the same instantiation)
+constexpr bool frame_built(const FrameVariant& v) {
+    if (v.rgba && v.stats) return false;  // the fused resolve has no stats form
+    if (v.bsdf) return v.env == 2 && !v.small && v.nee != kNeeNoSpheres;
+    if (v.nee) return v.env == 2 && !v.small && (v.bvh || v.nee == kNeeAll);
+    if (v.env == 2) return false;
+    return !v.small || (v.bvh && !v.stats);
+}
+// how many kernels that makes: 40 k_paths and 37 k_frame (a k_frame per built code without `jitter`)
+constexpr int paths_built_count() {
+    int n = 0;
+    for (int c = 0; c < kPathsCodes; ++c) n += paths_built(paths_of_code(c));
+    return n;
+}
+constexpr int frame_built_count() {
+    int n = 0;
+    for (int c = 0; c < kFrameCodes; ++c) n += !frame_of_code(c).jitter && frame_built(frame_of_code(c));
+    return n;
+}
 
 inline int nee_variant(const PassParams& p) {
     if (p.nee.n_emit == 0u) return 0;
@@ -78,39 +144,55 @@ inline uint32_t frame_hit_mode(const PassParams& p, bool cache_valid, bool lists
     return !cache_valid ? 1u : (lists ? 3u : 2u);
 }
 
-// The variant's kernel compiled for a flat scene's shape (spt_jit.h), and the env to ask for it with;
-// kind < 0: there is none (a BVH scene, statistics, or no shape), the offline-compiled kernel runs.
-// The counting k_paths of a shape with wall pairs (flat_shape_pairs) is compiled for the shape too, on first
-// use: it then runs the paired wall test the timed kernel runs, and counts its second passes.
-struct JitKind {
-    int kind, env;
-};
-constexpr JitKind kJitNone{-1, 0};
-inline JitKind jit_kind(const PathsVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.jitter || v.bsdf) return kJitNone;
-    if (v.wide) {
-        if (v.stats) return flat_shape_pairs(shape) ? JitKind{kJitPathsWideStats, v.env} : kJitNone;
-        return JitKind{kJitPathsWide, v.env};
+// The variant's kernel compiled for a flat scene's shape (spt_jit.h): the flat variant it instantiates, with the
+// fields that select nothing in it cleared, so that launches which run the same kernel ask for the same one.
+// kNoJitForm: there is none (a BVH scene, a per-path camera ray, material models, or no shape), the
+// offline-compiled kernel runs. k_frame's counting form has none. The counting k_paths of a shape with wall
+// pairs (flat_shape_pairs) is compiled for the shape, on first use: it then runs the paired wall test the timed
+// kernel runs, and counts its second passes.
+constexpr JitForm kNoJitForm{false, -1};
+constexpr JitForm jit_form_of(const PathsVariant& v) { return JitForm{false, paths_code(v)}; }
+constexpr JitForm jit_form_of(const FrameVariant& v) { return JitForm{true, frame_code(v)}; }
+inline JitForm jit_form(const PathsVariant& v, uint64_t shape) {
+    if (!shape || v.bvh || v.jitter || v.bsdf || (v.stats && !flat_shape_pairs(shape))) return kNoJitForm;
+    const bool nee = v.nee && !v.wide;  // (a flat scene's NEE kernel samples every emitter kind; its sky kind is read at run time)
+    return jit_form_of(PathsVariant{v.stats, false, nee ? 2 : v.env, 0, v.chan && !v.stats && !v.wide && !nee, nee ? kNeeAll : 0, false, false, v.wide});
+}
+inline JitForm jit_form(const FrameVariant& v, uint64_t shape) {
+    if (!shape || v.bvh || v.stats || v.bsdf) return kNoJitForm;
+    return jit_form_of(FrameVariant{false, false, v.nee ? 2 : v.env, false, v.nee ? kNeeAll : 0, v.rgba});
+}
+// the name expression hiprtc instantiates for (form, shape): every template argument, from the variant
+inline std::string jit_name_expr(JitForm form, uint64_t shape) {
+    const auto b = [](bool x) { return std::string(x ? "true" : "false"); };
+    const auto i = [](int x) { return std::to_string(x); };
+    const auto name = [](const char* kernel, std::initializer_list<std::string> args) {
+        std::string s;
+        for (const std::string& a : args) s += (s.empty() ? std::string("spt::") + kernel + "<" : ", ") + a;
+        return s + ">";
+    };
+    const std::string sh = std::to_string((unsigned long long)shape) + "ull";
+    if (form.frame) {
+        const FrameVariant v = frame_of_code(form.code);
+        return name("k_frame", {b(v.stats), b(v.bvh), i(v.env), sh, b(v.small), i(v.nee), b(v.rgba), b(v.bsdf)});
     }
-    if (v.stats) return flat_shape_pairs(shape) ? JitKind{v.nee ? kJitPathsNeeStats : kJitPathsStats, v.env} : kJitNone;
-    return JitKind{v.nee ? kJitPathsNee : v.chan ? kJitPathsChan : kJitPaths, v.env};
+    const PathsVariant v = paths_of_code(form.code);
+    return name("k_paths", {b(v.stats), b(v.bvh), i(v.env), sh, i(v.simd_waves), b(v.chan), i(v.nee), b(v.jitter), b(v.bsdf), b(v.wide)});
 }
-inline JitKind jit_kind(const FrameVariant& v, uint64_t shape) {
-    if (!shape || v.bvh || v.stats || v.bsdf) return kJitNone;
-    return JitKind{v.rgba ? (v.nee ? kJitFrameNeeRgba : kJitFrameRgba) : (v.nee ? kJitFrameNee : kJitFrame), v.env};
-}
-// The kinds a flat scene's renders may ask for: compiled ahead by spt_set_scene, waited for by
-// spt_specialize_scene. (The two kRgba kinds are not in the list: a fused resolve compiles its kernel
+// The forms a flat scene's renders may ask for: compiled ahead by spt_set_scene, waited for by
+// spt_specialize_scene. (The two kRgba forms are not in the list: a fused resolve compiles its kernel
 // on first use. Adding them here is the whole change, but it changes what a scene change compiles.)
 // wide: the ctx may run wide launches (wide_possible), so the wide k_paths is compiled ahead too
-struct JitKindList {
+struct JitFormList {
     int n;
-    JitKind k[4];
+    JitForm f[4];
 };
-inline JitKindList jit_kinds_of_scene(bool nee, int env, bool wide = false) {
-    if (nee) return {2, {{kJitPathsNee, 2}, {kJitFrameNee, 2}}};
-    if (wide) return {4, {{kJitPaths, env}, {kJitFrame, env}, {kJitPathsChan, env}, {kJitPathsWide, env}}};
-    return {3, {{kJitPaths, env}, {kJitFrame, env}, {kJitPathsChan, env}}};
+inline JitFormList jit_kinds_of_scene(bool nee, int env, bool wide = false) {
+    if (nee) return {2, {jit_form_of(PathsVariant{false, false, 2, 0, false, kNeeAll}), jit_form_of(FrameVariant{false, false, 2, false, kNeeAll, false})}};
+    const PathsVariant paths{false, false, env, 0, false, 0}, chan{false, false, env, 0, true, 0};
+    JitFormList l{3, {jit_form_of(paths), jit_form_of(FrameVariant{false, false, env, false, 0, false}), jit_form_of(chan)}};
+    if (wide) l.f[l.n++] = jit_form_of(PathsVariant{false, false, env, 0, false, 0, false, false, true});
+    return l;
 }
 
 // k_paths chunk plan (order and cost unset): the largest chunks (32/16/8 ... pixels) that still give

@@ -31,10 +31,6 @@ static PathsVariant paths_before(const PassParams& p, bool stats, uint32_t first
     v.chan = !bvh && !stats && !nee && first_shift < kMaxChunkShift;
     return v;
 }
-static bool same(const PathsVariant& a, const PathsVariant& b) {
-    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.simd_waves == b.simd_waves && a.chan == b.chan &&
-           a.nee == b.nee && a.jitter == b.jitter && a.bsdf == b.bsdf;
-}
 int main() {
     const uint64_t shape = jit_config_key(flat_shape_key(0x2082082u, 8u), 8u, 2u, 1u, 0u);
     for (int stats = 0; stats < 2; ++stats)
@@ -50,19 +46,21 @@ int main() {
                                 r.rgba = rgba ? &out : nullptr;
                                 // ---- without models: the plan of before, field for field
                                 const PathsVariant a = paths_variant(r, stats, shift);
-                                CHECK(same(a, paths_before(r, stats, shift)) && !a.bsdf);
-                                const JitKind ka = jit_kind(a, bvh ? 0ull : shape);
+                                CHECK(a == paths_before(r, stats, shift) && !a.bsdf);
+                                const JitForm ka = jit_form(a, bvh ? 0ull : shape);
                                 const bool generic = bvh || stats || cam == kCamJitter;
-                                CHECK((ka.kind == kJitNone.kind) == generic);
-                                if (!generic) CHECK(ka.kind == (emit ? kJitPathsNee : a.chan ? kJitPathsChan : kJitPaths) && ka.env == a.env);
+                                CHECK((ka == kNoJitForm) == generic);
+                                // the NEE, the channel-lane or the plain form, with the variant's sky kind
+                                if (!generic) CHECK(ka == jit_form_of(PathsVariant{false, false, a.env, 0, !emit && a.chan, emit ? kNeeAll : 0}));
                                 const FrameVariant f = frame_variant(r, stats);
                                 const bool fstats = stats && !rgba;
                                 const int nee = emit == 0u ? 0 : (bvh && emit == 1u ? kNeeNoSpheres : kNeeAll);
                                 CHECK(!f.bsdf && f.stats == fstats && f.bvh == (bvh != 0) && f.env == (nee ? 2 : env) &&
                                       f.small == frame_small_scene(r, fstats) && f.nee == nee && f.rgba == (rgba != 0) &&
                                       f.jitter == (cam == kCamJitter));
-                                const JitKind kf = jit_kind(f, bvh ? 0ull : shape);
-                                CHECK((kf.kind == kJitNone.kind) == (bvh || fstats));
+                                const JitForm kf = jit_form(f, bvh ? 0ull : shape);
+                                CHECK((kf == kNoJitForm) == (bvh || fstats));
+                                if (kf) CHECK(kf == jit_form_of(FrameVariant{false, false, f.env, false, f.nee, f.rgba}));
                                 if (cam != kCamJitter)
                                     CHECK(frame_hit_mode(r, false, false) == 1u && frame_hit_mode(r, true, false) == 2u &&
                                           frame_hit_mode(r, true, true) == 3u);
@@ -73,11 +71,11 @@ int main() {
                                 CHECK(b.bsdf && !b.jitter && b.env == 2 && b.simd_waves == 0 && !b.chan);  // one generic form ...
                                 CHECK(b.stats == (stats != 0) && b.bvh == (bvh != 0));
                                 CHECK(b.nee == (emit ? kNeeAll : 0));  // ... that samples every emitter kind
-                                CHECK(jit_kind(b, bvh ? 0ull : shape).kind == kJitNone.kind);  // no shape-specialized kernel
+                                CHECK(jit_form(b, bvh ? 0ull : shape) == kNoJitForm);  // no shape-specialized kernel
                                 const FrameVariant g = frame_variant(m, stats);
                                 CHECK(g.bsdf && g.env == 2 && !g.small && g.nee == (emit ? kNeeAll : 0) && g.stats == fstats &&
                                       g.bvh == (bvh != 0) && g.rgba == (rgba != 0));
-                                CHECK(jit_kind(g, bvh ? 0ull : shape).kind == kJitNone.kind);
+                                CHECK(jit_form(g, bvh ? 0ull : shape) == kNoJitForm);
                                 // hit_mode 0: every camera segment is traced, whatever the ctx holds
                                 CHECK(frame_hit_mode(m, false, false) == 0u && frame_hit_mode(m, true, false) == 0u &&
                                       frame_hit_mode(m, true, true) == 0u);

@@ -28,7 +28,7 @@ int main() {
                         CHECK(v.env == 2 && v.simd_waves == 0 && !v.chan);  // ... generic: no 8-wave, no channel-lane kernel
                         CHECK(v.stats == (stats != 0) && v.bvh == (bvh != 0));
                         CHECK(v.nee == (emit == 0u ? 0 : (bvh && emit == 1u ? kNeeNoSpheres : kNeeAll)));
-                        CHECK(jit_kind(v, bvh ? 0ull : shape).kind == kJitNone.kind);  // no shape-specialized kernel
+                        CHECK(jit_form(v, bvh ? 0ull : shape) == kNoJitForm);  // no shape-specialized kernel
                         const FrameVariant f = frame_variant(j, stats);
                         CHECK(f.jitter);
                         // the hit cache and the lists are ignored, whatever the ctx holds
@@ -39,9 +39,8 @@ int main() {
                         PassParams q = r;
                         q.cam_mode = kCamPosed;
                         const PathsVariant a = paths_variant(r, stats, shift), b = paths_variant(q, stats, shift);
-                        CHECK(!a.jitter && !b.jitter && a.stats == b.stats && a.bvh == b.bvh && a.env == b.env &&
-                              a.simd_waves == b.simd_waves && a.chan == b.chan && a.nee == b.nee);
-                        CHECK(jit_kind(a, bvh ? 0ull : shape).kind == jit_kind(b, bvh ? 0ull : shape).kind);
+                        CHECK(!a.jitter && !b.jitter && a == b);
+                        CHECK(jit_form(a, bvh ? 0ull : shape) == jit_form(b, bvh ? 0ull : shape));
                         CHECK(!frame_variant(q, stats).jitter);
                         CHECK(frame_hit_mode(q, false, false) == 1u && frame_hit_mode(q, true, false) == 2u &&
                               frame_hit_mode(q, true, true) == 3u);
@@ -49,7 +48,7 @@ int main() {
     // the small-BVH and channel-lane forms exist for the other cameras (so the checks above are not vacuous)
     CHECK(paths_variant(scene(1000u, true, 0u, 0u, false, kCamPosed), false, 5u).simd_waves == kBvhSmallWaves);
     CHECK(paths_variant(scene(8u, false, 0u, 0u, false, kCamPosed), false, 3u).chan);
-    CHECK(jit_kind(paths_variant(scene(8u, false, 0u, 0u, false, kCamPosed), false, 5u), shape).kind == kJitPaths);
+    CHECK(jit_form(paths_variant(scene(8u, false, 0u, 0u, false, kCamPosed), false, 5u), shape) == jit_form_of(PathsVariant{false, false, 0, 0, false, 0}));
     if (g_fail == 0) std::puts("ok");
     return g_fail ? 1 : 0;
 }

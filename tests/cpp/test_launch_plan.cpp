@@ -1,6 +1,6 @@
 // Host check of the persistent kernels' launch planning (spt_launch_plan.h): the chunk plan of k_paths,
-// which instantiation of k_paths / k_frame a scene runs and its run-time compiled kind, k_frame's grid,
-// and the name expressions of the run-time compiled kinds (spt_jit.h). Every variant computes the same
+// which instantiation of k_paths / k_frame a scene runs, that the library holds it, its run-time compiled
+// form and that form's name expression (jit_name_expr), and k_frame's grid. Every variant computes the same
 // image, so only a check like this one sees a wrong choice.
 #include <cstdio>
 #include <cstring>
@@ -93,13 +93,20 @@ static PassParams scene(uint32_t bvh_prims, uint32_t n_emit = 0, uint32_t sphere
     p.jit_shape = bvh_prims ? 0 : flat_shape_key(0, 20);
     return p;
 }
-static bool same(const PathsVariant& a, const PathsVariant& b) {
-    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.simd_waves == b.simd_waves && a.chan == b.chan && a.nee == b.nee;
+// (operator== compares every field: jitter, bsdf and wide too)
+template <class V>
+static bool same(const V& a, const V& b) {
+    return a == b;
 }
-static bool same(const FrameVariant& a, const FrameVariant& b) {
-    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.small == b.small && a.nee == b.nee && a.rgba == b.rgba;
+// the run-time compiled form of `v` is the variant `want`
+static bool jit_is(const PathsVariant& v, uint64_t shape, const PathsVariant& want) {
+    const JitForm f = jit_form(v, shape);
+    return f && !f.frame && paths_of_code(f.code) == want;
 }
-static bool same(JitKind a, JitKind b) { return a.kind == b.kind && (a.kind < 0 || a.env == b.env); }
+static bool jit_is(const FrameVariant& v, uint64_t shape, const FrameVariant& want) {
+    const JitForm f = jit_form(v, shape);
+    return f && f.frame && frame_of_code(f.code) == want;
+}
 
 static void selectors() {
     const uint64_t shape = flat_shape_key(0, 20);
@@ -167,24 +174,122 @@ static void selectors() {
     CHECK(!frame_variant(r, false).small);
     CHECK(!frame_variant(scene(0), false).small);
 
-    // the run-time compiled kind of each variant; none for BVH, statistics and no shape
-    CHECK(same(jit_kind(PathsVariant{false, false, 1, 0, false, 0}, shape), JitKind{kJitPaths, 1}));
-    CHECK(same(jit_kind(PathsVariant{false, false, 0, 0, true, 0}, shape), JitKind{kJitPathsChan, 0}));
-    CHECK(same(jit_kind(PathsVariant{false, false, 2, 0, false, kNeeAll}, shape), JitKind{kJitPathsNee, 2}));
-    CHECK(same(jit_kind(PathsVariant{false, true, 0, kBvhSmallWaves, false, 0}, shape), kJitNone));
-    CHECK(same(jit_kind(PathsVariant{true, false, 0, 0, false, 0}, shape), kJitNone));
-    CHECK(same(jit_kind(PathsVariant{false, false, 0, 0, false, 0}, 0), kJitNone));
-    CHECK(same(jit_kind(FrameVariant{false, false, 0, false, 0, false}, shape), JitKind{kJitFrame, 0}));
-    CHECK(same(jit_kind(FrameVariant{false, false, 2, false, kNeeAll, false}, shape), JitKind{kJitFrameNee, 2}));
-    CHECK(same(jit_kind(FrameVariant{false, false, 1, false, 0, true}, shape), JitKind{kJitFrameRgba, 1}));
-    CHECK(same(jit_kind(FrameVariant{false, false, 2, false, kNeeAll, true}, shape), JitKind{kJitFrameNeeRgba, 2}));
-    CHECK(same(jit_kind(FrameVariant{false, true, 0, true, 0, false}, shape), kJitNone));
-    CHECK(same(jit_kind(FrameVariant{true, false, 0, false, 0, false}, shape), kJitNone));
-    CHECK(same(jit_kind(FrameVariant{false, false, 0, false, 0, true}, 0), kJitNone));
-    JitKindList l = jit_kinds_of_scene(true, 1);
-    CHECK(l.n == 2 && same(l.k[0], JitKind{kJitPathsNee, 2}) && same(l.k[1], JitKind{kJitFrameNee, 2}));
+    // the run-time compiled form of each variant; none for BVH, statistics (a shape without wall pairs) and no shape
+    const uint64_t pairs = flat_shape_key(0, 20, 0, 1);  // (a shape with a wall pair: its counting k_paths is compiled too)
+    CHECK(flat_shape_pairs(pairs) != 0 && flat_shape_pairs(shape) == 0);
+    const PathsVariant plain{false, false, 1, 0, false, 0}, chan{false, false, 0, 0, true, 0}, nee{false, false, 2, 0, false, kNeeAll};
+    const PathsVariant wide{false, false, 1, 0, false, 0, false, false, true}, wide_stats{true, false, 0, 0, false, 0, false, false, true};
+    const PathsVariant stats{true, false, 0, 0, false, 0}, nee_stats{true, false, 2, 0, false, kNeeAll};
+    CHECK(jit_is(plain, shape, plain));
+    CHECK(jit_is(chan, shape, chan));
+    CHECK(jit_is(nee, shape, nee));
+    CHECK(jit_is(wide, shape, wide));
+    CHECK(jit_is(stats, pairs, stats));
+    CHECK(jit_is(nee_stats, pairs, nee_stats));
+    CHECK(jit_is(wide_stats, pairs, wide_stats));
+    CHECK(jit_form(PathsVariant{false, true, 0, kBvhSmallWaves, false, 0}, shape) == kNoJitForm);
+    CHECK(jit_form(stats, shape) == kNoJitForm);
+    CHECK(jit_form(nee_stats, shape) == kNoJitForm);
+    CHECK(jit_form(wide_stats, shape) == kNoJitForm);
+    CHECK(jit_form(PathsVariant{false, false, 0, 0, false, 0}, 0) == kNoJitForm);
+    CHECK(jit_form(PathsVariant{false, false, 2, 0, false, 0, true}, shape) == kNoJitForm);         // jitter
+    CHECK(jit_form(PathsVariant{false, false, 2, 0, false, 0, false, true}, shape) == kNoJitForm);  // bsdf
+    const FrameVariant frame{false, false, 0, false, 0, false}, frame_nee{false, false, 2, false, kNeeAll, false};
+    const FrameVariant frame_rgba{false, false, 1, false, 0, true}, frame_nee_rgba{false, false, 2, false, kNeeAll, true};
+    CHECK(jit_is(frame, shape, frame));
+    CHECK(jit_is(frame_nee, shape, frame_nee));
+    CHECK(jit_is(frame_rgba, shape, frame_rgba));
+    CHECK(jit_is(frame_nee_rgba, shape, frame_nee_rgba));
+    CHECK(jit_is(FrameVariant{false, false, 0, false, 0, false, true}, shape, frame));  // jitter: the same kernel
+    CHECK(jit_form(FrameVariant{false, true, 0, true, 0, false}, shape) == kNoJitForm);
+    CHECK(jit_form(FrameVariant{true, false, 0, false, 0, false}, shape) == kNoJitForm);
+    CHECK(jit_form(FrameVariant{true, false, 0, false, 0, false}, pairs) == kNoJitForm);  // k_frame's counting form: never
+    CHECK(jit_form(FrameVariant{false, false, 0, false, 0, true}, 0) == kNoJitForm);
+    CHECK(jit_form(FrameVariant{false, false, 2, false, 0, false, false, true}, shape) == kNoJitForm);  // bsdf
+    JitFormList l = jit_kinds_of_scene(true, 1);
+    CHECK(l.n == 2 && l.f[0] == jit_form_of(nee) && l.f[1] == jit_form_of(frame_nee));
     l = jit_kinds_of_scene(false, 1);
-    CHECK(l.n == 3 && same(l.k[0], JitKind{kJitPaths, 1}) && same(l.k[1], JitKind{kJitFrame, 1}) && same(l.k[2], JitKind{kJitPathsChan, 1}));
+    CHECK(l.n == 3 && l.f[0] == jit_form_of(plain) && l.f[1] == jit_form_of(FrameVariant{false, false, 1, false, 0, false}) &&
+          l.f[2] == jit_form_of(PathsVariant{false, false, 1, 0, true, 0}));
+    l = jit_kinds_of_scene(false, 0, true);
+    CHECK(l.n == 4 && l.f[0] == jit_form_of(PathsVariant{false, false, 0, 0, false, 0}) && l.f[1] == jit_form_of(frame) &&
+          l.f[2] == jit_form_of(chan) && l.f[3] == jit_form_of(PathsVariant{false, false, 0, 0, false, 0, false, false, true}));
+    l = jit_kinds_of_scene(true, 0, true);
+    CHECK(l.n == 2 && l.f[0] == jit_form_of(nee) && l.f[1] == jit_form_of(frame_nee));
+}
+
+// The code of a variant and the forms the library holds: the pack / unpack pair over the whole code space, the
+// counts, and every PassParams combination the selectors distinguish — each gets a built form, and its
+// run-time compiled form, when there is one, is a built flat form.
+static void forms_exhaustive() {
+    static_assert(paths_built_count() == 40 && frame_built_count() == 37, "the forms the library holds");
+    int n_paths = 0, n_frame = 0;
+    for (int c = 0; c < kPathsCodes; ++c) {
+        const PathsVariant v = paths_of_code(c);
+        CHECK(paths_code(v) == c && same(paths_of_code(paths_code(v)), v));
+        CHECK(v.env >= 0 && v.env <= 2 && v.nee >= 0 && v.nee <= 2 && (v.simd_waves == 0 || v.simd_waves == kBvhSmallWaves));
+        n_paths += paths_built(v);
+        if (v.wide && (v.bsdf || v.jitter || v.nee)) CHECK(!paths_built(v));
+    }
+    for (int c = 0; c < kFrameCodes; ++c) {
+        const FrameVariant v = frame_of_code(c);
+        CHECK(frame_code(v) == c && same(frame_of_code(frame_code(v)), v));
+        CHECK(v.env >= 0 && v.env <= 2 && v.nee >= 0 && v.nee <= 2);
+        FrameVariant j = v;
+        j.jitter = !v.jitter;
+        CHECK(frame_built(j) == frame_built(v));  // jitter selects no kernel of its own
+        n_frame += !v.jitter && frame_built(v);
+    }
+    CHECK(n_paths == 40 && n_frame == 37);
+    CHECK(paths_code(PathsVariant{true, true, 2, kBvhSmallWaves, true, 2, true, true, true}) == kPathsCodes - 1);
+    CHECK(frame_code(FrameVariant{true, true, 2, true, 2, true, true, true}) == kFrameCodes - 1);
+
+    const uint64_t shapes[] = {flat_shape_key(0, 20), flat_shape_key(0, 20, 0, 1)};  // without and with a wall pair
+    static float4 pose[4];
+    int combos = 0;
+    for (int sc = 0; sc < 4; ++sc)  // flat / small BVH / large BVH / a BVH scene k_frame holds in LDS
+        for (bool env : {false, true})
+            for (int em = 0; em < 3; ++em)  // emitters: none / with spheres / without spheres
+                for (uint32_t cam : {kCamReference, kCamPosed, kCamJitter, kCamPosed | kCamLens, kCamJitter | kCamLens})
+                    for (bool bsdf : {false, true})
+                        for (bool stats : {false, true})
+                            for (bool rgba : {false, true})
+                                for (uint32_t shift : {5u, 4u, 0u})
+                                    for (bool wide : {false, true})
+                                        for (uint64_t shape : shapes) {
+                                            PassParams p = scene(sc == 0 ? 0 : sc == 1 ? kBvhSmall : sc == 2 ? 1000 : kFrameTopPrims,
+                                                                 em ? 3 : 0, em == 1 ? 1 : 0, env);
+                                            if (sc == 3) {
+                                                p.n_dev_nodes = kFrameTopNodes;
+                                                p.n_mats = 0;
+                                                p.stack_need = kFrameLdsStackMax;
+                                            }
+                                            if (sc != 0) shape = 0;
+                                            p.jit_shape = shape;
+                                            p.cam_mode = cam;
+                                            p.cam_pose = cam == kCamReference ? nullptr : pose;
+                                            p.bsdf = bsdf ? 1u : 0u;
+                                            p.rgba = rgba ? g_rgba : nullptr;
+                                            ++combos;
+                                            const PathsVariant v = paths_variant(p, stats, shift, wide);
+                                            CHECK(paths_built(v));
+                                            CHECK(v.stats == stats && v.bvh == (sc != 0));
+                                            const JitForm jp = jit_form(v, shape);
+                                            if (jp) {
+                                                const PathsVariant f = paths_of_code(jp.code);
+                                                CHECK(!jp.frame && !f.bvh && paths_built(f) && f.stats == v.stats && f.wide == v.wide);
+                                            }
+                                            const FrameVariant fv = frame_variant(p, stats);
+                                            CHECK(frame_built(fv));
+                                            CHECK(fv.bvh == (sc != 0) && fv.rgba == rgba);
+                                            if (sc == 3 && !em && !bsdf && !(stats && !rgba)) CHECK(fv.small);
+                                            const JitForm jf = jit_form(fv, shape);
+                                            if (jf) {
+                                                const FrameVariant f = frame_of_code(jf.code);
+                                                CHECK(jf.frame && !f.bvh && !f.stats && !f.jitter && frame_built(f) && f.rgba == fv.rgba);
+                                            }
+                                        }
+    CHECK(combos == 4 * 2 * 3 * 5 * 2 * 2 * 2 * 3 * 2 * 2);
 }
 
 static void frame_grids() {
@@ -222,15 +327,30 @@ static void frame_grids() {
 static void jit_names() {
     const uint64_t shape = flat_shape_key(0x1234, 20);
     const std::string sh = std::to_string((unsigned long long)shape) + "ull";
-    CHECK(jit_name_expr(kJitPaths, 1, shape) == "spt::k_paths<false, false, 1, " + sh + ">");
-    CHECK(jit_name_expr(kJitFrame, 1, shape) == "spt::k_frame<false, false, 1, " + sh + ">");
-    CHECK(jit_name_expr(kJitPathsChan, 1, shape) == "spt::k_paths<false, false, 1, " + sh + ", 0, true>");
-    CHECK(jit_name_expr(kJitPathsNee, 1, shape) == "spt::k_paths<false, false, 2, " + sh + ", 0, false, 1>");
-    CHECK(jit_name_expr(kJitFrameNee, 1, shape) == "spt::k_frame<false, false, 2, " + sh + ", false, 1>");
-    CHECK(jit_name_expr(kJitFrameRgba, 1, shape) == "spt::k_frame<false, false, 1, " + sh + ", false, 0, true>");
-    CHECK(jit_name_expr(kJitFrameNeeRgba, 1, shape) == "spt::k_frame<false, false, 2, " + sh + ", false, 1, true>");
-    CHECK(jit_name_expr(kJitPaths, 0, 68719476756ull) == "spt::k_paths<false, false, 0, 68719476756ull>");
-    static_assert(kNeeAll == 1, "the kNee argument the NEE kinds' names spell");
+    // (every template argument is spelled, the defaulted ones too: the same specializations as without them)
+    const auto paths_name = [&](const PathsVariant& v, uint64_t s = 0) { return jit_name_expr(jit_form(v, s ? s : shape), s ? s : shape); };
+    const auto frame_name = [&](const FrameVariant& v) { return jit_name_expr(jit_form(v, shape), shape); };
+    CHECK(paths_name(PathsVariant{false, false, 1, 0, false, 0}) == "spt::k_paths<false, false, 1, " + sh + ", 0, false, 0, false, false, false>");
+    CHECK(frame_name(FrameVariant{false, false, 1, false, 0, false}) == "spt::k_frame<false, false, 1, " + sh + ", false, 0, false, false>");
+    CHECK(paths_name(PathsVariant{false, false, 1, 0, true, 0}) == "spt::k_paths<false, false, 1, " + sh + ", 0, true, 0, false, false, false>");
+    CHECK(paths_name(PathsVariant{false, false, 2, 0, false, kNeeAll}) == "spt::k_paths<false, false, 2, " + sh + ", 0, false, 1, false, false, false>");
+    CHECK(frame_name(FrameVariant{false, false, 2, false, kNeeAll, false}) == "spt::k_frame<false, false, 2, " + sh + ", false, 1, false, false>");
+    CHECK(frame_name(FrameVariant{false, false, 1, false, 0, true}) == "spt::k_frame<false, false, 1, " + sh + ", false, 0, true, false>");
+    CHECK(frame_name(FrameVariant{false, false, 2, false, kNeeAll, true}) == "spt::k_frame<false, false, 2, " + sh + ", false, 1, true, false>");
+    CHECK(paths_name(PathsVariant{false, false, 0, 0, false, 0}, 68719476756ull) ==
+          "spt::k_paths<false, false, 0, 68719476756ull, 0, false, 0, false, false, false>");
+    // wide; and the counting forms of a shape with a wall pair: plain, NEE, wide
+    CHECK(paths_name(PathsVariant{false, false, 1, 0, false, 0, false, false, true}) == "spt::k_paths<false, false, 1, " + sh + ", 0, false, 0, false, false, true>");
+    const uint64_t pairs = flat_shape_key(0x1234, 20, 0, 1);
+    const std::string ps = std::to_string((unsigned long long)pairs) + "ull";
+    CHECK(paths_name(PathsVariant{true, false, 1, 0, false, 0}, pairs) == "spt::k_paths<true, false, 1, " + ps + ", 0, false, 0, false, false, false>");
+    CHECK(paths_name(PathsVariant{true, false, 2, 0, false, kNeeAll}, pairs) == "spt::k_paths<true, false, 2, " + ps + ", 0, false, 1, false, false, false>");
+    CHECK(paths_name(PathsVariant{true, false, 0, 0, false, 0, false, false, true}, pairs) == "spt::k_paths<true, false, 0, " + ps + ", 0, false, 0, false, false, true>");
+    // a name spells whatever the code holds (the offline-only fields too)
+    CHECK(jit_name_expr(jit_form_of(PathsVariant{false, true, 0, kBvhSmallWaves, false, kNeeNoSpheres, true, true, false}), 5ull) ==
+          "spt::k_paths<false, true, 0, 5ull, " + std::to_string(kBvhSmallWaves) + ", false, 2, true, true, false>");
+    CHECK(jit_name_expr(jit_form_of(FrameVariant{true, true, 0, true, 0, false}), 5ull) == "spt::k_frame<true, true, 0, 5ull, true, 0, false, false>");
+    static_assert(kNeeAll == 1 && kNeeNoSpheres == 2, "the kNee argument the NEE forms' names spell");
 }
 
 int main() {
@@ -239,6 +359,7 @@ int main() {
     selectors();
     frame_grids();
     jit_names();
+    forms_exhaustive();
     std::printf(g_failed ? "FAIL (%d checks)\n" : "PASS\n", g_failed);
     return g_failed ? 1 : 0;
 }

@@ -18,14 +18,6 @@ static PassParams scene(uint32_t n_prims, bool bvh, uint32_t n_emit, uint32_t sp
     p.rgba = nullptr;
     return p;
 }
-static bool same(const PathsVariant& a, const PathsVariant& b) {
-    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.simd_waves == b.simd_waves && a.chan == b.chan &&
-           a.nee == b.nee && a.jitter == b.jitter && a.bsdf == b.bsdf;
-}
-static bool same(const FrameVariant& a, const FrameVariant& b) {
-    return a.stats == b.stats && a.bvh == b.bvh && a.env == b.env && a.small == b.small && a.nee == b.nee &&
-           a.rgba == b.rgba && a.jitter == b.jitter && a.bsdf == b.bsdf;
-}
 int main() {
     // the modes' values are part of the device record
     static_assert(kCamReference == 0u && kCamPosed == 1u && kCamJitter == 2u && kCamLens == 4u, "camera modes");
@@ -51,13 +43,13 @@ int main() {
                                     l.cam_mode = mode;
                                     const PathsVariant v = paths_variant(l, stats, shift);
                                     const FrameVariant f = frame_variant(l, stats);
-                                    CHECK(same(v, vj) && same(f, fj));
+                                    CHECK(v == vj && f == fj);
                                     CHECK(v.bsdf == (bsdf != 0u) && f.bsdf == (bsdf != 0u));  // with bsdf: the bsdf form
                                     CHECK(bsdf ? !v.jitter : v.jitter);
                                     CHECK(f.jitter);
                                     CHECK(v.env == 2 && v.simd_waves == 0 && !v.chan);
-                                    CHECK(jit_kind(v, bvh ? 0ull : shape).kind == kJitNone.kind);
-                                    CHECK(jit_kind(f, bvh ? 0ull : shape).kind == jit_kind(fj, bvh ? 0ull : shape).kind);
+                                    CHECK(jit_form(v, bvh ? 0ull : shape) == kNoJitForm);
+                                    CHECK(jit_form(f, bvh ? 0ull : shape) == jit_form(fj, bvh ? 0ull : shape));
                                     for (int cv = 0; cv < 2; ++cv)
                                         for (int li = 0; li <= cv; ++li) {
                                             CHECK(frame_hit_mode(l, cv, li) == 0u);

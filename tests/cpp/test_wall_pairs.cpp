@@ -140,14 +140,19 @@ int main() {
         CHECK((cfg >> 63) == 0);
         // the counting k_paths of a shape with pairs is compiled for the shape (it counts the second passes of
         // the test the timed kernel runs); without pairs the offline counting kernels run, as before
-        const JitKind ks = jit_kind(PathsVariant{true, false, 0, 0, false, 0}, key);
-        const JitKind kn = jit_kind(PathsVariant{true, false, 2, 0, false, kNeeAll}, key);
-        CHECK(ks.kind == kJitPathsStats && ks.env == 0 && kn.kind == kJitPathsNeeStats && kn.env == 2);
-        CHECK(jit_kind(PathsVariant{true, false, 0, 0, false, 0}, flat_shape_key(fe, n, s.rect)).kind < 0);
-        CHECK(jit_kind(PathsVariant{false, false, 0, 0, false, 0}, key).kind == kJitPaths);
-        CHECK(jit_name_expr(kJitPathsStats, 1, 5ull) == "spt::k_paths<true, false, 1, 5ull>");
-        CHECK(jit_name_expr(kJitPathsNeeStats, 0, 5ull) == "spt::k_paths<true, false, 2, 5ull, 0, false, 1>");
-        CHECK(jit_name_expr(kJitPaths, 1, 5ull) == "spt::k_paths<false, false, 1, 5ull>");
+        const PathsVariant counting{true, false, 0, 0, false, 0}, counting_nee{true, false, 2, 0, false, kNeeAll};
+        const PathsVariant timed{false, false, 0, 0, false, 0};
+        CHECK(jit_form(counting, key) == jit_form_of(counting) && jit_form(counting_nee, key) == jit_form_of(counting_nee));
+        CHECK(jit_form(counting, flat_shape_key(fe, n, s.rect)) == kNoJitForm);
+        CHECK(jit_form(counting_nee, flat_shape_key(fe, n, s.rect)) == kNoJitForm);
+        CHECK(jit_form(timed, key) == jit_form_of(timed));
+        CHECK(jit_name_expr(jit_form(PathsVariant{true, false, 1, 0, false, 0}, key), 5ull) ==
+              "spt::k_paths<true, false, 1, 5ull, 0, false, 0, false, false, false>");
+        // (the NEE form's sky kind is 2 whatever the variant says)
+        CHECK(jit_name_expr(jit_form(PathsVariant{true, false, 0, 0, false, kNeeAll}, key), 5ull) ==
+              "spt::k_paths<true, false, 2, 5ull, 0, false, 1, false, false, false>");
+        CHECK(jit_name_expr(jit_form(PathsVariant{false, false, 1, 0, false, 0}, key), 5ull) ==
+              "spt::k_paths<false, false, 1, 5ull, 0, false, 0, false, false, false>");
         for (uint32_t pb = 0; pb < 64; ++pb) {
             const uint64_t k2 = flat_shape_key(fe, n, s.rect, pb);
             CHECK(flat_shape_pairs(k2, 0) == (pb & 3u) && flat_shape_pairs(k2, 1) == ((pb >> 2) & 3u) &&

@@ -81,7 +81,7 @@ def test_stack_entry_code_is_a_lower_bound(exe):
 def test_launch_plan_picks_the_kernels_and_grids(exe):
     """spt_launch_plan.h on the host: k_paths' chunk plan (tiling invariants over a sweep, exact tiers of
     the benchmark shapes), the k_paths / k_frame variant and run-time compiled kind each kind of scene
-    runs, k_frame's grid rule, and the run-time compiled kinds' name expressions (spt_jit.h). Every
+    runs, k_frame's grid rule, and the run-time compiled forms' name expressions (jit_name_expr). Every
     variant gives the same image, so no parity test sees a wrong choice."""
     r = subprocess.run([os.path.join(ROOT, "tests", "cpp", "test_launch_plan")], capture_output=True, text=True,
                        timeout=300)

@@ -164,6 +164,33 @@ def test_render_resolve_fused(spt, scene, w, h, bounces, flags):
             fused.render_resolve_rgba8(frame + 1, 1, 0, out=buf)  # frame_count 0: "No frames rendered yet"
 
 
+@pytest.mark.parametrize("nee,fused", [(True, False), (False, True), (True, True)], ids=["nee", "rgba", "nee-rgba"])
+def test_specialized_k_frame_forms(spt, nee, fused):
+    """k_frame's shape-specialized forms with light sampling, with the fused resolve and with both: each runs
+    (spt_stats.specialized) and gives the generic kernel's bits. Cornell 64x48, 8 one-frame calls."""
+    w, h, frames = 64, 48, 8
+    got = {}
+    for specialize in (1, -1):
+        with spt.Context(0) as ctx:
+            ctx.set_tuning(specialize=specialize)
+            ctx.set_scene(*spt.build_scene("cornell"))
+            ctx.configure(w, h, 8, 2, spt.FLAG_NEE if nee else 0)
+            buf = np.zeros(ctx.shard_pixels, dtype=np.uint32)
+            if fused:
+                ctx.register_host_output(buf)
+            for k in range(frames):
+                if fused:
+                    ctx.render_resolve_rgba8(k, 1, k + 1, out=buf)
+                else:
+                    ctx.render(k, 1)
+                st = ctx.stats()
+                assert st.schedule == spt.SCHEDULE_FRAME
+                assert int(st.specialized) == (1 if specialize == 1 else 0), (k, specialize)
+            got[specialize] = (ctx.read_accum().copy(), buf.copy())
+    assert np.array_equal(got[1][0].view(np.uint32), got[-1][0].view(np.uint32))
+    assert np.array_equal(got[1][1], got[-1][1])
+
+
 def test_render_resolve_fused_golden(spt, golden):
     """The App's scene at 64x64, 16 one-frame calls through spt_render_resolve_rgba8 into the registered
     buffer: the committed oracle fixture's RGBA8."""

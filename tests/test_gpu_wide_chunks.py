@@ -61,6 +61,20 @@ def test_wide_counters(spt, ref):
     assert list(stats[-1].radiance_updates) == list(pstats[-1].radiance_updates)
 
 
+def test_wide_counters_specialized(spt):
+    """The counting wide form compiled for the shape (Cornell has wall pairs): it runs, with the generic one's bits.
+    Cornell 64x48, 8 frames in two calls (the second runs over the view's lists)."""
+    w, h, calls = 64, 48, (4, 4)
+    acc, stats = render_calls(spt, calls=calls, w=w, h=h, tuning=dict(WIDE, specialize=1), counters=True)
+    assert_wide(stats)
+    assert stats[-1].specialized == 1
+    gen, gstats = render_calls(spt, calls=calls, w=w, h=h, tuning=dict(WIDE, specialize=-1), counters=True)
+    assert_wide(gstats)
+    assert gstats[-1].specialized == 0
+    assert_same(acc, gen, "wide counters: specialized vs generic")
+    assert list(stats[-1].segments) == list(gstats[-1].segments)
+
+
 def test_wide_fewer_than_64_live(spt, ref):
     """A view whose whole live list is shorter than one wide chunk: the wide kernel runs its small tiers only."""
     w, h = 11, 7
