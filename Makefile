@@ -25,7 +25,8 @@ FPFLAGS  := -ffp-contract=off -fno-fast-math
 HIPFLAGS := -O3 -fno-slp-vectorize $(FPFLAGS) -fPIC -std=c++17 --offload-arch=$(ARCH) -fno-gpu-rdc -Wall -Iinclude -I$(CSRC)
 CXXFLAGS := -O2 $(FPFLAGS) -fPIC -std=c++17 -Wall -Wextra -Iinclude -I$(CSRC)
 
-HIP_SRCS := $(CSRC)/spt_kernels.hip $(CSRC)/spt_capi.hip $(CSRC)/spt_jit.hip $(CSRC)/spt_denoise.hip
+HIP_SRCS := $(CSRC)/spt_kernels.hip $(CSRC)/spt_capi.hip $(CSRC)/spt_jit.hip $(CSRC)/spt_denoise.hip \
+            $(CSRC)/spt_reproject.hip
 CPP_SRCS := $(CSRC)/scene.cpp $(CSRC)/scenes.cpp
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS))
 CPP_OBJS := $(patsubst $(CSRC)/%.cpp,$(OBJ)/%.o,$(CPP_SRCS))

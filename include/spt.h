@@ -497,6 +497,114 @@ int spt_resolve_denoised_rgba8(spt_ctx* ctx, float exposure, uint32_t* host_out)
 int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
                     const spt_denoise_params* params, float* out);
 
+/* ---- temporal reprojection (superset: the reference restarts at 1 spp whenever anything changes) -------
+ * After a camera move the image the old view accumulated is reused: nearly every surface is Lambertian, its
+ * outgoing radiance does not depend on the eye, so what the old view gathered at a world point is an estimate
+ * for the pixel that sees that point now. All arithmetic below is fp32 without contraction, '/' correctly
+ * rounded; the operations are + - * /, floorf, fabsf, fminf, comparisons and one float -> int conversion of a
+ * range-checked value; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *
+ * A captured view is an image hc (rgb: a mean radiance; a: its length n in frames, >= 1), that view's feat_a
+ * and feat_b (ha, hb) and its camera. From the camera's float fields the ctx derives, in double and rounded
+ * once to float, the dual basis of (u, v, w):
+ *   cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);  c = cross(v,w);
+ *   det = (u.x*c.x + u.y*c.y) + u.z*c.z;  ru = cross(v,w)/det;  rv = cross(w,u)/det;  rw = cross(u,v)/det
+ * (all three rows zero if det is 0 or not finite: nothing is reused then), o' = its origin, and j' = 0.5f if it
+ * had SPT_CAMERA_JITTER, else 0 (where its features' rays went). No camera: the reference's, identity rows,
+ * origin 0, j' = 0.
+ *
+ * Reprojection of the captured view into the current one, per pixel p with the current feat_a = (P, mat),
+ * feat_b = (N, t); Wf = (float)W, Hf = (float)H, aspect = Wf / Hf; "none" is out = (0, 0, 0, 0):
+ *   1. mat is the miss value: none.
+ *   2. mat's model is METAL or DIELECTRIC (their radiance depends on the eye): none.
+ *   3. e = P - o';  a = dot(ru,e);  b = dot(rv,e);  c = dot(rw,e);  unless c > 0: none.
+ *   4. sx = a / c;  sy = b / c;
+ *      fx = ((sx / aspect + 1.0f) * 0.5f) * Wf - j';   fy = (1.0f - (sy + 1.0f) * 0.5f) * Hf - j';
+ *      unless fx > -1.0f && fx < Wf && fy > -1.0f && fy < Hf: none (NaN and inf fall out here).
+ *   5. x0f = floorf(fx);  ax = fx - x0f;  x0 = (int)x0f;  the same for y. Four taps q = (x0 + i, y0 + j),
+ *      j = 0, 1 outer and i = 0, 1 inner, k = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay). A tap is valid iff
+ *      q is inside the image, ha_q's material bits equal mat, dot(N, hb_q.xyz) >= normal_min and
+ *      fabsf(dot(N, ha_q.xyz - P)) <= plane_tolerance * t. A valid tap adds
+ *      sum.c += k * hc_q.c (c = r, g, b: multiply, then add);  sum_n += k * hc_q.a;  sum_w += k
+ *      and any other tap nothing (its hc is not read).
+ *   6. unless sum_w >= min_weight: none. Otherwise out.rgb = sum.rgb / sum_w,
+ *      out.a = fminf(sum_n / sum_w, max_history).
+ * The material alone does not tell surfaces apart (Cornell's floor, ceiling, back wall and spheres share one):
+ * the normal and plane tests do. The primitive index is not used: it would reject every neighbouring triangle
+ * of a mesh.
+ *
+ * Blend of the reprojected history h with the frames accumulated since: f = (float)frame_count,
+ * m = accum / f on all four channels (the denoiser's mean);
+ *   out.rgb = h.a > 0 ? (h.rgb * h.a + m.rgb * f) / (h.a + f) : m.rgb   (exactly those operations);  out.a = m.a
+ * and out = m without an active history. A capture stores the same rgb with a = h.a + f (f without a
+ * history), so lengths chain across moves and max_history caps them at the next reprojection: a camera that
+ * moves every frame shows an exponential average.
+ *
+ * With a lens the features stay the chief ray's, as for the denoiser: reuse is then approximate (a defocused
+ * pixel gathers radiance from around its chief ray's hit), not refused. Not covered: moving geometry
+ * (spt_update_prims drops the history), reuse on or through metal and glass, row shards. */
+typedef struct spt_reproject_params {   /* 32 bytes */
+    float    max_history;      /* finite, >= 1; default 32.0f: the most frames a history counts for  */
+    float    normal_min;       /* finite; default 0.9f: the least cosine between the two normals     */
+    float    plane_tolerance;  /* finite, >= 0; default 0.01f: distance from the pixel's tangent
+                                  plane, as a share of the pixel's hit distance t                    */
+    float    min_weight;       /* finite, > 0; default 0.01f: the least sum of valid taps' weights   */
+    uint32_t reserved[4];      /* must be 0                                                           */
+} spt_reproject_params;
+/* Host only: the defaults above. SPT_ERR_INVALID for NULL. */
+int spt_reproject_params_default(spt_reproject_params* out);
+/* Store what is shown now — the blend of the active history (if any) with the frame_count frames accumulated
+ * (frame_count: the divisor) — as the ctx's captured view, with its length, the feature images (rendered first
+ * if they are stale) and the camera. Replaces an earlier capture; the active history stays. Asynchronous on
+ * the ctx stream; the buffers are allocated by the first call. SPT_ERR_NO_SCENE / SPT_ERR_NOT_CONFIGURED as
+ * spt_denoise; SPT_ERR_INVALID for frame_count == 0 or a ctx that renders a row shard (shard_count != 1). */
+int spt_history_capture(spt_ctx* ctx, uint32_t frame_count);
+/* Map the captured view into the current one with the current camera's features (rendered first if they are
+ * stale); the result becomes the ctx's active history. params = NULL: the defaults. Asynchronous on the ctx
+ * stream. SPT_ERR_INVALID without a capture, for a parameter out of range or a non-zero reserved word. */
+int spt_reproject(spt_ctx* ctx, const spt_reproject_params* params);
+/* Drop the capture and the active history (their memory stays with the ctx until spt_configure). */
+int spt_history_clear(spt_ctx* ctx);
+/* The active history, rgb + length per pixel (zeros where nothing was reused): copied to the host (n_pixels * 4
+ * floats; waits for the stream), or its device pointer and byte size (valid until the next spt_reproject or
+ * spt_configure). SPT_ERR_INVALID without an active history. */
+int spt_read_history(spt_ctx* ctx, float* host_rgba);
+int spt_history_device_ptr(spt_ctx* ctx, void** dptr, size_t* bytes);
+/* Write the blend of the active history with the frame_count frames accumulated (the mean alone without an
+ * active history) into the ctx's blended image. Asynchronous on the ctx stream; errors as spt_history_capture. */
+int spt_history_blend(spt_ctx* ctx, uint32_t frame_count);
+/* The last spt_history_blend's image, as spt_read_denoised / spt_denoised_device_ptr /
+ * spt_resolve_denoised_rgba8 give the denoised one (it is a mean: divisor 1; the registered host buffer is
+ * written directly). SPT_ERR_INVALID before any spt_history_blend since the last spt_configure. */
+int spt_read_blended(spt_ctx* ctx, float* host_rgba);
+int spt_blended_device_ptr(spt_ctx* ctx, void** dptr, size_t* bytes);
+int spt_resolve_blended_rgba8(spt_ctx* ctx, float exposure, uint32_t* host_out);
+/* spt_denoise over the blended image instead of accum / frame_count, into the ctx's denoised image (read it with
+ * spt_read_denoised / spt_resolve_denoised_rgba8). SPT_ERR_INVALID before any spt_history_blend. */
+int spt_denoise_blended(spt_ctx* ctx, const spt_denoise_params* params);
+/* Measurement and tests (the images never depend on it): the memory layout later spt_history_capture calls
+ * store the view in: 0 three float4 images, 1 one 48-byte record per pixel (feat_a, feat_b, image), -1 (the
+ * default) the one that measured faster. SPT_ERR_INVALID otherwise. */
+int spt_set_history_layout(spt_ctx* ctx, int layout);
+/* What drops them: spt_set_scene, spt_update_prims, spt_configure, spt_set_material_models and spt_set_env_map
+ * drop the capture and the active history (the radiance changed); spt_set_camera and spt_set_camera_lens drop
+ * the active history alone (the capture survives them: that is its purpose). spt_reset, spt_render, the
+ * accumulation, the frame count and the stats are untouched by all of the above, and a ctx that never calls
+ * them allocates nothing for them. */
+/* Host only, no device needed: the captured camera as the gather reads it: rows = (ru, rv, rw), origin = o',
+ * *j = j'. camera = NULL: the reference's. SPT_ERR_INVALID for a null output or an invalid camera. */
+int spt_reproject_basis(const spt_camera* camera, float rows[9], float origin[3], float* j);
+/* Host only, no device needed: the reprojection above on the caller's arrays by the function the kernels
+ * compile (csrc/spt_reproject.h reproject_pixel): the same bits as spt_reproject. prev_camera: the captured
+ * view's (NULL: the reference's); cur_a / cur_b: the current features; hist_rgba / hist_a / hist_b: the captured
+ * image and features; out: the history; width * height * 4 floats each. material_reusable: one word per
+ * material, 0 for a METAL or DIELECTRIC one (a material index >= n_materials counts as 0); NULL: all reusable.
+ * params = NULL: the defaults. SPT_ERR_INVALID for a null array, a zero size, an invalid parameter or camera. */
+int spt_reproject_host(const spt_reproject_params* params, const spt_camera* prev_camera, uint32_t width,
+                       uint32_t height, const float* cur_a, const float* cur_b, const float* hist_rgba,
+                       const float* hist_a, const float* hist_b, const uint32_t* material_reusable,
+                       uint32_t n_materials, float* out);
+
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */
 /* Miss radiance from an octahedral environment map instead of sample_sky's gradient (only while

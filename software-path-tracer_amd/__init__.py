@@ -189,6 +189,10 @@ EXPORTED_SYMBOLS = (
     "spt_render_features", "spt_read_features", "spt_features_device_ptr",
     "spt_denoise_params_default", "spt_denoise", "spt_set_denoise_form", "spt_read_denoised", "spt_denoised_device_ptr",
     "spt_resolve_denoised_rgba8", "spt_atrous_host",
+    "spt_reproject_params_default", "spt_history_capture", "spt_reproject", "spt_history_clear", "spt_read_history",
+    "spt_history_device_ptr", "spt_history_blend", "spt_read_blended", "spt_blended_device_ptr",
+    "spt_resolve_blended_rgba8", "spt_denoise_blended", "spt_set_history_layout", "spt_reproject_basis",
+    "spt_reproject_host",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -239,6 +243,30 @@ class DenoiseParams(ctypes.Structure):
         for k, v in kw.items():
             if k not in dict(self._fields_):
                 raise TypeError(f"unknown spt_denoise_params field {k}")
+            setattr(self, k, v)
+
+
+class ReprojectParams(ctypes.Structure):
+    """spt_reproject_params (32 bytes): the most frames a reprojected history counts for (>= 1), the least
+    cosine between the two views' normals, the plane distance allowed as a share of the hit distance (>= 0)
+    and the least sum of valid taps' weights (> 0). ReprojectParams() holds the library's defaults
+    (spt_reproject_params_default); keyword arguments replace single fields."""
+    _fields_ = [
+        ("max_history", ctypes.c_float),
+        ("normal_min", ctypes.c_float),
+        ("plane_tolerance", ctypes.c_float),
+        ("min_weight", ctypes.c_float),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        rc = load_library().spt_reproject_params_default(ctypes.byref(self))
+        if rc != SPT_OK:
+            raise SptError(f"spt_reproject_params_default -> {SPT_ERR.get(rc, rc)}")
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown spt_reproject_params field {k}")
             setattr(self, k, v)
 
 
@@ -324,6 +352,21 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_denoised_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)], I),
         "spt_resolve_denoised_rgba8": ([P, ctypes.c_float, P], I),
         "spt_atrous_host": ([P, P, P, U32, U32, ctypes.POINTER(DenoiseParams), P], I),
+        "spt_reproject_params_default": ([ctypes.POINTER(ReprojectParams)], I),
+        "spt_history_capture": ([P, U32], I),
+        "spt_reproject": ([P, ctypes.POINTER(ReprojectParams)], I),
+        "spt_history_clear": ([P], I),
+        "spt_read_history": ([P, P], I),
+        "spt_history_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)], I),
+        "spt_history_blend": ([P, U32], I),
+        "spt_read_blended": ([P, P], I),
+        "spt_blended_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)], I),
+        "spt_resolve_blended_rgba8": ([P, ctypes.c_float, P], I),
+        "spt_denoise_blended": ([P, ctypes.POINTER(DenoiseParams)], I),
+        "spt_set_history_layout": ([P, I], I),
+        "spt_reproject_basis": ([ctypes.POINTER(SptCamera), P, P, ctypes.POINTER(ctypes.c_float)], I),
+        "spt_reproject_host": ([ctypes.POINTER(ReprojectParams), ctypes.POINTER(SptCamera), U32, U32, P, P, P, P, P, P,
+                                U32, P], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -480,6 +523,39 @@ def atrous_host(rgba: np.ndarray, feat_a: np.ndarray, feat_b: np.ndarray,
                                         ctypes.byref(params) if params is not None else None, _ptr(out))
     if rc != SPT_OK:
         raise SptError(f"spt_atrous_host -> {SPT_ERR.get(rc, rc)}")
+    return out
+
+
+def reproject_basis(cam: Optional[SptCamera]):
+    """spt_reproject_basis (host only): (rows (3, 3) = ru, rv, rw; origin (3,); j') of a captured view's camera as
+    the reprojection reads it; None: the reference's camera."""
+    rows, origin, j = np.zeros((3, 3), dtype=np.float32), np.zeros(3, dtype=np.float32), ctypes.c_float(0.0)
+    rc = load_library().spt_reproject_basis(ctypes.byref(cam) if cam is not None else None, _ptr(rows), _ptr(origin),
+                                            ctypes.byref(j))
+    if rc != SPT_OK:
+        raise SptError(f"spt_reproject_basis -> {SPT_ERR.get(rc, rc)}")
+    return rows, origin, float(j.value)
+
+
+def reproject_host(prev_cam: Optional[SptCamera], cur_a: np.ndarray, cur_b: np.ndarray, hist_rgba: np.ndarray,
+                   hist_a: np.ndarray, hist_b: np.ndarray, params: Optional[ReprojectParams] = None,
+                   material_reusable=None) -> np.ndarray:
+    """spt_reproject_host (host only): the captured view (hist_rgba: mean radiance and length; hist_a / hist_b: its
+    features; prev_cam: its camera, None for the reference's) mapped into the view whose features are cur_a /
+    cur_b, all (h, w, 4) float32, by the function the kernels compile: the same bits as Context.reproject.
+    material_reusable: one entry per material, 0 / False for a METAL or DIELECTRIC one; None: all reusable."""
+    arrs = [np.ascontiguousarray(x, dtype=np.float32) for x in (cur_a, cur_b, hist_rgba, hist_a, hist_b)]
+    if arrs[0].ndim != 3 or arrs[0].shape[2] != 4 or any(x.shape != arrs[0].shape for x in arrs):
+        raise ValueError("reproject_host: the five images must be (height, width, 4) arrays of one shape")
+    table = None if material_reusable is None else np.ascontiguousarray(material_reusable, dtype=np.uint32)
+    out = np.empty_like(arrs[0])
+    rc = load_library().spt_reproject_host(ctypes.byref(params) if params is not None else None,
+                                           ctypes.byref(prev_cam) if prev_cam is not None else None,
+                                           arrs[0].shape[1], arrs[0].shape[0], *[_ptr(x) for x in arrs],
+                                           ctypes.c_void_p(table.ctypes.data) if table is not None else None,
+                                           0 if table is None else table.size, _ptr(out))
+    if rc != SPT_OK:
+        raise SptError(f"spt_reproject_host -> {SPT_ERR.get(rc, rc)}")
     return out
 
 
@@ -804,6 +880,65 @@ class Context:
         self._check(self.lib.spt_resolve_denoised_rgba8(self.h, exposure, _ptr(out)), "spt_resolve_denoised_rgba8")
         return out
 
+    def history_capture(self, frame_count: int) -> None:
+        """spt_history_capture: store what is shown now (the active history blended with the frame_count frames
+        accumulated), its features and camera as the captured view (asynchronous)."""
+        self._check(self.lib.spt_history_capture(self.h, frame_count), "spt_history_capture")
+
+    def reproject(self, params: Optional[ReprojectParams] = None) -> None:
+        """spt_reproject: map the captured view into the current camera's; the result is the active history."""
+        self._check(self.lib.spt_reproject(self.h, ctypes.byref(params) if params is not None else None), "spt_reproject")
+
+    def history_clear(self) -> None:
+        self._check(self.lib.spt_history_clear(self.h), "spt_history_clear")
+
+    def set_history_layout(self, layout: int) -> None:
+        """spt_set_history_layout (measurement and tests): 0 the captured view as three images, 1 as 48-byte
+        records, -1 the library's choice. The images are the same."""
+        self._check(self.lib.spt_set_history_layout(self.h, layout), "spt_set_history_layout")
+
+    def read_history(self) -> np.ndarray:
+        """spt_read_history: the active history, (shard_pixels, 4) float32: mean radiance and length in frames."""
+        out = np.empty((self.shard_pixels, 4), dtype=np.float32)
+        self._check(self.lib.spt_read_history(self.h, _ptr(out)), "spt_read_history")
+        return out
+
+    def history_device_ptr(self) -> Tuple[int, int]:
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.lib.spt_history_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n)), "spt_history_device_ptr")
+        return int(p.value or 0), int(n.value)
+
+    def history_blend(self, frame_count: int) -> None:
+        """spt_history_blend: the active history blended with the frame_count frames accumulated, into the ctx's
+        blended image (asynchronous; read_blended / resolve_blended_rgba8 / denoise_blended take it from there)."""
+        self._check(self.lib.spt_history_blend(self.h, frame_count), "spt_history_blend")
+
+    def read_blended(self) -> np.ndarray:
+        out = np.empty((self.shard_pixels, 4), dtype=np.float32)
+        self._check(self.lib.spt_read_blended(self.h, _ptr(out)), "spt_read_blended")
+        return out
+
+    def blended_device_ptr(self) -> Tuple[int, int]:
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.lib.spt_blended_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n)), "spt_blended_device_ptr")
+        return int(p.value or 0), int(n.value)
+
+    def resolve_blended_rgba8(self, exposure: float = 1.0, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """spt_resolve_blended_rgba8: the blended image as RGBA8 (into the registered buffer directly when `out`
+        is that buffer)."""
+        if out is None:
+            out = np.empty(self.shard_pixels, dtype=np.uint32)
+        if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < self.shard_pixels:
+            raise SptError("resolve_blended_rgba8: out must be a C-contiguous uint32 array of >= shard_pixels")
+        self._check(self.lib.spt_resolve_blended_rgba8(self.h, exposure, _ptr(out)), "spt_resolve_blended_rgba8")
+        return out
+
+    def denoise_blended(self, params: Optional[DenoiseParams] = None) -> None:
+        """spt_denoise_blended: the a-trous filter over the blended image, into the denoised image
+        (read_denoised / resolve_denoised_rgba8)."""
+        self._check(self.lib.spt_denoise_blended(self.h, ctypes.byref(params) if params is not None else None),
+                    "spt_denoise_blended")
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -1015,6 +1150,17 @@ class HIPPathTracer(PathTracer):
         self._models = None
         self._models_dirty = False
         self._denoise: Optional[DenoiseParams] = None
+        self._reproject: Optional[ReprojectParams] = None
+
+    def set_reproject(self, params: Optional[ReprojectParams]) -> None:
+        """Not in the reference interface: temporal reprojection. While params is not None, a camera or lens change
+        that arrives with frames accumulated captures the view before it is applied and reprojects it after
+        (Context.history_capture / reproject with these parameters), and get_render_result() returns the blend
+        of that history with the frames since (the denoised blend with set_denoise on). None (the default)
+        switches it off and drops the history."""
+        self._reproject = params
+        if params is None:
+            self._ctx.history_clear()
 
     def set_denoise(self, params: Optional[DenoiseParams]) -> None:
         """Not in the reference interface: while params is not None, get_render_result() returns the denoised
@@ -1082,6 +1228,10 @@ class HIPPathTracer(PathTracer):
             if self._settings_mode:
                 bounces, rr = self._settings.getMaxBounces(), self._settings.getRussianRouletteDepth()
             self._ctx.configure(self._result.width, self._result.height, bounces, rr, self._flags)
+        # (the frame count is 0 here if anything above changed the radiance: nothing is captured then)
+        reuse = self._reproject is not None and self._frame_count > 0 and (self._camera_dirty or self._lens_dirty)
+        if reuse:
+            self._ctx.history_capture(self._frame_count)
         if self._camera_dirty:
             self._frame_count = 0
             self._camera_dirty = False
@@ -1091,6 +1241,8 @@ class HIPPathTracer(PathTracer):
             self._lens_dirty = False
             if self._lens is not None or self._camera is not None:  # (no camera: the ctx has no lens either)
                 self._ctx.set_camera_lens(self._lens)
+        if reuse:
+            self._ctx.reproject(self._reproject)
         if self._frame_count == 0:
             self._ctx.reset()
         if needs_rebuild:
@@ -1118,6 +1270,14 @@ class HIPPathTracer(PathTracer):
         if self._frame_count <= 0:
             raise SptError("No frames rendered yet")  # CPUPathTracer.cpp:89
         exposure = self._settings.getExposure() if self._settings_mode else 1.0
+        if self._reproject is not None:
+            self._ctx.history_blend(self._frame_count)
+            if self._denoise is not None:
+                self._ctx.denoise_blended(self._denoise)
+                self._result.image_buffer = self._ctx.resolve_denoised_rgba8(exposure)
+            else:
+                self._result.image_buffer = self._ctx.resolve_blended_rgba8(exposure)
+            return self._result
         if self._denoise is not None:
             self._ctx.denoise(self._frame_count, self._denoise)
             self._result.image_buffer = self._ctx.resolve_denoised_rgba8(exposure)

@@ -72,7 +72,7 @@ namespace render
 		// (:61); settings mode: getSamplesPerPixel() such frames in one call (k_paths from 4)
 		const uint32_t n = m_settingsMode ? std::max<uint32_t>(1u, m_renderSettings->getSamplesPerPixel()) : 1u;
 		m_resolvedAt = 0;
-		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn)
+		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn && !m_reprojectOn)
 		{
 			// the App reads the result after every render() (App.cpp:230-240): a one-frame call's resolve
 			// rides in the frame's own launch, its pixels stored into the registered result buffer as their
@@ -137,10 +137,33 @@ namespace render
 		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
 	}
 
+	void HIPPathTracer::set_reproject(const spt_reproject_params *params)
+	{
+		m_reprojectOn = params != nullptr;
+		if (params)
+			m_reproject = *params;
+		else
+			SPT_CALL(m_ctx, spt_history_clear(m_ctx));
+		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
+	}
+
 	const PathTracer::RenderResult &HIPPathTracer::get_render_result()
 	{
 		SPT_VERIFY(m_frameCount > 0, "No frames rendered yet");
 		const float exposure = m_settingsMode ? m_renderSettings->getExposure() : 1.0f;
+		if (m_reprojectOn)
+		{
+			// the history (if the ctx holds one) blended with the frames so far: a mean, resolved with divisor 1
+			SPT_CALL(m_ctx, spt_history_blend(m_ctx, m_frameCount));
+			if (m_denoiseOn)
+			{
+				SPT_CALL(m_ctx, spt_denoise_blended(m_ctx, &m_denoise));
+				SPT_CALL(m_ctx, spt_resolve_denoised_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
+			}
+			else
+				SPT_CALL(m_ctx, spt_resolve_blended_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
+			return m_render_result;
+		}
 		if (m_denoiseOn)
 		{
 			// the filtered mean of the frames so far, resolved with divisor 1 (into the registered buffer)
@@ -220,6 +243,11 @@ namespace render
 			cfg.frames_in_flight = 1;  // progressive: one frame per render() call
 			SPT_CALL(m_ctx, spt_configure(m_ctx, &cfg));
 		}
+		// temporal reprojection: what the frames so far show is kept across the move (m_frameCount is 0 here if
+		// anything above changed the radiance: nothing is captured then)
+		const bool reuse = m_reprojectOn && m_frameCount > 0 && (m_cameraChanged || m_lensChanged);
+		if (reuse)
+			SPT_CALL(m_ctx, spt_history_capture(m_ctx, m_frameCount));
 		if (m_cameraChanged)
 		{
 			// another view: a fresh accumulation, and nothing resolved for it yet
@@ -240,6 +268,8 @@ namespace render
 			m_resolvedAt = 0;
 			m_outputDirty = true;
 		}
+		if (reuse)
+			SPT_CALL(m_ctx, spt_reproject(m_ctx, &m_reproject));
 		if (m_frameCount == 0)
 		{
 			SPT_CALL(m_ctx, spt_reset(m_ctx));

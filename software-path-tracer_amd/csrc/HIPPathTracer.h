@@ -74,6 +74,15 @@ namespace render
 		// way, except that a one-frame render() does not fuse the plain resolve into its launch while on.
 		void set_denoise(const spt_denoise_params *params);
 
+		// Not in the reference interface (it restarts at one sample after every change): temporal reprojection
+		// (spt.h spt_reproject with these parameters; copied). While on, a camera or lens change that arrives
+		// with frames accumulated captures the view before it is applied and reprojects it after, and
+		// get_render_result() returns the blend of that history with the frames since (the denoised blend with
+		// set_denoise on). A scene or settings change drops the history through the ctx's own invalidation.
+		// nullptr switches it off and drops the history; off is the default, and the backend is then what it
+		// is without this call (a one-frame render() fuses its resolve only while off).
+		void set_reproject(const spt_reproject_params *params);
+
 	private:
 		void invalidate();
 		void rebuild_scene();
@@ -101,5 +110,7 @@ namespace render
 		bool m_modelsChanged = false;
 		spt_denoise_params m_denoise{};            // set_denoise's, while m_denoiseOn
 		bool m_denoiseOn = false;
+		spt_reproject_params m_reproject{};        // set_reproject's, while m_reprojectOn
+		bool m_reprojectOn = false;
 	};
 } // namespace render

@@ -23,6 +23,7 @@
 #include "spt_jit.h"
 #include "spt_kernels.h"
 #include "spt_launch_plan.h"
+#include "spt_reproject.h"
 
 using namespace spt;
 
@@ -31,6 +32,7 @@ static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kM
               "spt.h spt_material_kind and spt_device.h model_kind");
 static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
 static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes");
+static_assert(sizeof(spt_reproject_params) == 32, "spt_reproject_params is 32 bytes");
 
 namespace {
 
@@ -202,6 +204,23 @@ struct spt_ctx {
     float4* dn[2] = {nullptr, nullptr};
     int dn_result = -1;
     int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
+    // Temporal reprojection, every buffer allocated by the first call that needs it (configure-sized).
+    // spt_history_capture: the captured view — image with lengths, feat_a, feat_b in 3 * pixels float4, laid
+    // out as hist_view_layout says (spt_reproject.h) — and its camera
+    float4* hist_view = nullptr;
+    int hist_view_layout = 0;
+    bool hist_view_valid = false;
+    bool hist_view_has_camera = false;
+    spt_camera hist_view_camera{};
+    float4* hist = nullptr;      // spt_reproject: the active history (rgb, length)
+    bool hist_valid = false;
+    float4* blend = nullptr;     // spt_history_blend: the blended image
+    bool blend_valid = false;
+    int hist_layout = -1;        // spt_set_history_layout: -1 the layout measured faster
+    // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
+    // model is not DIFFUSE (bsdf), dropped with the models
+    uint32_t* d_reusable = nullptr;
+    bool reusable_valid = false;
 
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
@@ -307,6 +326,13 @@ void free_dev(T*& p) {
     p = nullptr;
 }
 
+// The radiance changed (scene, materials, sky, configuration): neither the captured view nor the active history
+// holds an estimate of it any more. A camera or lens change drops the active history alone (view = false).
+void drop_history(spt_ctx* c, bool view) {
+    if (view) c->hist_view_valid = false;
+    c->hist_valid = false;
+}
+
 void free_buffers(spt_ctx* c) {
     for (int k = 0; k < 2; ++k) {
         free_dev(c->q_o[k]);
@@ -346,6 +372,10 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->dn[0]);
     free_dev(c->dn[1]);
     c->dn_result = -1;
+    free_dev(c->hist_view);
+    free_dev(c->hist);
+    free_dev(c->blend);
+    c->hist_view_valid = c->hist_valid = c->blend_valid = false;
 }
 
 // RCCL, resolved at run time (spt.h): the copy already in the process (PyTorch loads its own
@@ -421,6 +451,9 @@ void free_scene(spt_ctx* c) {
     free_dev(c->d_emit);
     free_dev(c->d_mat_map);
     c->feat_valid = false;  // (the first hits were this scene's)
+    drop_history(c, true);
+    free_dev(c->d_reusable);
+    c->reusable_valid = false;
     c->n_prims = c->n_nodes = c->n_dev_nodes = c->n_emit = c->n_emit_spheres = 0;
     c->has_scene = false;
 }
@@ -982,6 +1015,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
         if (indices[j] >= total) return fail(c, SPT_ERR_INVALID, "spt_update_prims: index out of range");
     c->hit_cache_valid = false;  // (moved primitives: k_frame traces the camera segments again)
     c->feat_valid = false;       // (... and spt_render_features the first hits)
+    drop_history(c, true);       // (... and the history other radiance)
     c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
     c->view_valid = false;   // (... and the view's bounce 0)
     // the edits are staged and committed to the host mirror only once the device holds them, so a
@@ -1148,6 +1182,8 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
     c->hit_cache_valid = false;  // (a new image size, shard or flags: the camera hits are traced again)
     c->feat_valid = false;
     c->dn_result = -1;  // (no denoised image of this configuration yet)
+    drop_history(c, true);  // (... no history: another size, or other paths)
+    c->blend_valid = false;
     c->chunk_order_key = 0;
     c->view_valid = false;  // (another size, shard, flags or bounce limit: another bounce 0 per pixel)
     const size_t qn = (size_t)cap * c->n_sub;
@@ -1640,24 +1676,30 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
         c->env_h = height;
     }
     c->view_valid = false;  // (k_paths' view lists hold the sky pixels' radiance)
+    drop_history(c, true);  // (... and the history the old sky's light)
     if (c->configured) return spt_reset(c);  // a different sky: the accumulation restarts
     return SPT_OK;
+}
+
+// nullptr: valid
+static const char* camera_error(const spt_camera& cam) {
+    double w2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(cam.origin[a]) || !std::isfinite(cam.u[a]) || !std::isfinite(cam.v[a]) ||
+            !std::isfinite(cam.w[a]))
+            return "camera: non-finite value";
+        w2 += (double)cam.w[a] * cam.w[a];
+    }
+    if (!(w2 > 0.0)) return "camera: w (forward) is zero";
+    if (cam.flags & ~(uint32_t)SPT_CAMERA_JITTER) return "camera: unknown flags";
+    if (cam.reserved[0] | cam.reserved[1] | cam.reserved[2]) return "camera: reserved must be 0";
+    return nullptr;
 }
 
 int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     if (!c) return SPT_ERR_INVALID;
     if (cam) {
-        double w2 = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            if (!std::isfinite(cam->origin[a]) || !std::isfinite(cam->u[a]) || !std::isfinite(cam->v[a]) ||
-                !std::isfinite(cam->w[a]))
-                return fail(c, SPT_ERR_INVALID, "camera: non-finite value");
-            w2 += (double)cam->w[a] * cam->w[a];
-        }
-        if (!(w2 > 0.0)) return fail(c, SPT_ERR_INVALID, "camera: w (forward) is zero");
-        if (cam->flags & ~(uint32_t)SPT_CAMERA_JITTER) return fail(c, SPT_ERR_INVALID, "camera: unknown flags");
-        if (cam->reserved[0] | cam->reserved[1] | cam->reserved[2])
-            return fail(c, SPT_ERR_INVALID, "camera: reserved must be 0");
+        if (const char* msg = camera_error(*cam)) return fail(c, SPT_ERR_INVALID, msg);
         // the device record; a lens stays, on the new camera's u and v
         const spt_camera old = c->camera;
         c->camera = *cam;
@@ -1675,6 +1717,7 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     c->chunk_order_key = 0;
     c->view_valid = false;  // (k_paths' view lists too)
     c->feat_valid = false;  // (the first hits were the previous camera's)
+    drop_history(c, false);  // (the active history was mapped into the previous view; the captured view stays)
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
     return SPT_OK;
@@ -1708,6 +1751,7 @@ int spt_set_camera_lens(spt_ctx* c, const spt_lens* lens) {
     c->frame_lists = false;
     c->chunk_order_key = 0;
     c->view_valid = false;
+    drop_history(c, false);  // (as spt_set_camera: the frames that follow are another view's)
     prefetch_flat(c);
     if (c->configured) return spt_reset(c);
     return SPT_OK;
@@ -1736,6 +1780,8 @@ int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32
     c->frame_lists = false;
     c->chunk_order_key = 0;
     c->view_valid = false;  // (k_paths' view lists: the kBsdf kernels take none)
+    drop_history(c, true);  // (other materials: other radiance)
+    c->reusable_valid = false;
     if (c->configured) return spt_reset(c);  // other materials: the accumulation restarts
     return SPT_OK;
 }
@@ -1836,14 +1882,13 @@ int spt_denoise_params_default(spt_denoise_params* out) {
     return SPT_OK;
 }
 
-int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* params) {
-    if (!c) return SPT_ERR_INVALID;
+// the filter over `in` / divisor (divisor 0: `in` is already the mean), into the ctx's denoised image
+static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt_denoise_params* params) {
     if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_denoise before spt_configure");
     const spt_denoise_params p = params ? *params : kDenoiseDefaults;
     if (const char* msg = denoise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
     if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, "spt_denoise needs the whole image (shard_count 1)");
-    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
     // (the straight form's grid has a block row per 4 image rows)
     if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise: image taller than 262140 rows");
     const int rc = ensure_features(c);
@@ -1863,13 +1908,20 @@ int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* para
     const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
     for (uint32_t l = 0; l < p.levels; ++l) {
         const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
-        const float4* in = l == 0 ? c->accum : c->dn[(l - 1u) & 1u];
-        launch_atrous(forced >= 0 ? forced : atrous_form_of_step(lv.step), in, l == 0 ? (float)frame_count : 0.0f,
+        const float4* in = l == 0 ? in0 : c->dn[(l - 1u) & 1u];
+        launch_atrous(forced >= 0 ? forced : atrous_form_of_step(lv.step), in, l == 0 ? divisor : 0.0f,
                       c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     }
     c->dn_result = (int)((p.levels - 1u) & 1u);
     return SPT_OK;
+}
+
+int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* params) {
+    if (!c) return SPT_ERR_INVALID;
+    // (no scene or configuration is reported first, by denoise_image; a divisor of 0 would mean "already a mean")
+    if (c->has_scene && c->configured && frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+    return denoise_image(c, c->accum, (float)frame_count, params);
 }
 
 int spt_set_denoise_form(spt_ctx* c, int form) {
@@ -1897,11 +1949,8 @@ int spt_denoised_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
     return SPT_OK;
 }
 
-int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
-    if (!c || !host_out) return SPT_ERR_INVALID;
-    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    const float4* img = c->dn[c->dn_result];
+// spt_resolve_rgba8_exposure of an image that is already a mean (divisor 1)
+static int resolve_mean_rgba8(spt_ctx* c, const float4* img, float exposure, uint32_t* host_out) {
     if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
         // the registered buffer: the kernel's stores go straight to host memory over PCIe
         launch_resolve(img, c->pixels, 1.0f, exposure, (uint32_t*)c->out_dev, on_stream(c));
@@ -1913,6 +1962,13 @@ int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
     }
     SPT_HIP(c, wait_frame(c));
     return SPT_OK;
+}
+
+int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
+    if (!c || !host_out) return SPT_ERR_INVALID;
+    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    return resolve_mean_rgba8(c, c->dn[c->dn_result], exposure, host_out);
 }
 
 int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
@@ -1946,6 +2002,201 @@ int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b,
         in = dst;
     }
     std::memcpy(out, in, sizeof(float) * 4 * n);
+    return SPT_OK;
+}
+
+// ---- temporal reprojection ------------------------------------------------------------------------
+
+namespace {
+const spt_reproject_params kReprojectDefaults = {32.0f, 0.9f, 0.01f, 0.01f, {0u, 0u, 0u, 0u}};
+// nullptr: valid
+const char* reproject_params_error(const spt_reproject_params& p) {
+    if (!std::isfinite(p.max_history) || !(p.max_history >= 1.0f)) return "spt_reproject_params: max_history must be finite and >= 1";
+    if (!std::isfinite(p.normal_min)) return "spt_reproject_params: normal_min must be finite";
+    if (!std::isfinite(p.plane_tolerance) || !(p.plane_tolerance >= 0.0f)) return "spt_reproject_params: plane_tolerance must be finite and >= 0";
+    if (!std::isfinite(p.min_weight) || !(p.min_weight > 0.0f)) return "spt_reproject_params: min_weight must be finite and > 0";
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_reproject_params: reserved must be 0";
+    return nullptr;
+}
+// what spt_history_capture, spt_reproject and spt_history_blend share: a whole image, and for the first two
+// (features) its current feature images
+int history_ready(spt_ctx* c, const char* who, bool features) {
+    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, std::string(who) + " before spt_configure");
+    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, std::string(who) + " needs the whole image (shard_count 1)");
+    // (k_reproject's grid has a block row per 4 image rows)
+    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, std::string(who) + ": image taller than 262140 rows");
+    if (features) return ensure_features(c);
+    SPT_HIP(c, hipSetDevice(c->device));
+    return SPT_OK;
+}
+int alloc_image(spt_ctx* c, float4*& img, size_t pixels, const char* who) {
+    if (img) return SPT_OK;
+    if (hipMalloc(&img, sizeof(float4) * pixels) != hipSuccess) {
+        img = nullptr;
+        (void)hipGetLastError();
+        return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
+    }
+    return SPT_OK;
+}
+int read_image(spt_ctx* c, const float4* img, float* host_rgba) {
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipMemcpyAsync(host_rgba, img, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+}  // namespace
+
+int spt_reproject_params_default(spt_reproject_params* out) {
+    if (!out) return SPT_ERR_INVALID;
+    *out = kReprojectDefaults;
+    return SPT_OK;
+}
+
+int spt_history_capture(spt_ctx* c, uint32_t frame_count) {
+    if (!c) return SPT_ERR_INVALID;
+    if (const int rc = history_ready(c, "spt_history_capture", true); rc != SPT_OK) return rc;
+    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+    if (const int rc = alloc_image(c, c->hist_view, 3 * (size_t)c->pixels, "spt_history_capture"); rc != SPT_OK) return rc;
+    c->hist_view_valid = false;
+    const int layout = c->hist_layout >= 0 ? c->hist_layout : kHistoryDefault;
+    launch_history_capture(layout, c->accum, (float)frame_count, c->hist_valid ? c->hist : nullptr, c->feat_a, c->feat_b,
+                           c->hist_view, c->pixels, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    c->hist_view_layout = layout;
+    c->hist_view_has_camera = c->has_camera;
+    c->hist_view_camera = c->camera;
+    c->hist_view_valid = true;
+    return SPT_OK;
+}
+
+int spt_reproject(spt_ctx* c, const spt_reproject_params* params) {
+    if (!c) return SPT_ERR_INVALID;
+    const spt_reproject_params p = params ? *params : kReprojectDefaults;
+    if (const char* msg = reproject_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
+    if (const int rc = history_ready(c, "spt_reproject", true); rc != SPT_OK) return rc;
+    if (!c->hist_view_valid) return fail(c, SPT_ERR_INVALID, "no captured view: spt_history_capture first");
+    if (const int rc = alloc_image(c, c->hist, c->pixels, "spt_reproject"); rc != SPT_OK) return rc;
+    c->hist_valid = false;
+    const uint32_t n_mats = (uint32_t)c->h_mats.size();
+    if (c->bsdf && !c->reusable_valid) {
+        // (spt_set_material_models drained the stream before it changed the models: nothing reads the old words)
+        std::vector<uint32_t> words(n_mats);
+        for (uint32_t m = 0; m < n_mats; ++m) words[m] = c->h_models[m].kind == SPT_MAT_DIFFUSE ? 1u : 0u;
+        if (!c->d_reusable) SPT_HIP(c, hipMalloc(&c->d_reusable, sizeof(uint32_t) * n_mats));
+        SPT_HIP(c, hipMemcpy(c->d_reusable, words.data(), sizeof(uint32_t) * n_mats, hipMemcpyHostToDevice));
+        c->reusable_valid = true;
+    }
+    const ReprojectView v = reproject_view(c->hist_view_has_camera ? &c->hist_view_camera : nullptr);
+    launch_reproject(c->hist_view_layout, c->feat_a, c->feat_b, c->hist_view, c->hist, c->cfg.width, c->cfg.height, v, p,
+                     c->bsdf ? c->d_reusable : nullptr, n_mats, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    c->hist_valid = true;
+    return SPT_OK;
+}
+
+int spt_history_clear(spt_ctx* c) {
+    if (!c) return SPT_ERR_INVALID;
+    drop_history(c, true);
+    return SPT_OK;
+}
+
+int spt_read_history(spt_ctx* c, float* host_rgba) {
+    if (!c || !host_rgba) return SPT_ERR_INVALID;
+    if (!c->hist_valid) return fail(c, SPT_ERR_INVALID, "no active history: spt_reproject first");
+    return read_image(c, c->hist, host_rgba);
+}
+
+int spt_history_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
+    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
+    if (!c->hist_valid) return fail(c, SPT_ERR_INVALID, "no active history: spt_reproject first");
+    *dptr = c->hist;
+    *bytes = sizeof(float4) * (size_t)c->pixels;
+    return SPT_OK;
+}
+
+int spt_history_blend(spt_ctx* c, uint32_t frame_count) {
+    if (!c) return SPT_ERR_INVALID;
+    if (const int rc = history_ready(c, "spt_history_blend", false); rc != SPT_OK) return rc;
+    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+    if (const int rc = alloc_image(c, c->blend, c->pixels, "spt_history_blend"); rc != SPT_OK) return rc;
+    c->blend_valid = false;
+    launch_history_blend(c->accum, (float)frame_count, c->hist_valid ? c->hist : nullptr, c->blend, c->pixels, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    c->blend_valid = true;
+    return SPT_OK;
+}
+
+int spt_read_blended(spt_ctx* c, float* host_rgba) {
+    if (!c || !host_rgba) return SPT_ERR_INVALID;
+    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
+    return read_image(c, c->blend, host_rgba);
+}
+
+int spt_blended_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
+    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
+    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
+    *dptr = c->blend;
+    *bytes = sizeof(float4) * (size_t)c->pixels;
+    return SPT_OK;
+}
+
+int spt_resolve_blended_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
+    if (!c || !host_out) return SPT_ERR_INVALID;
+    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    return resolve_mean_rgba8(c, c->blend, exposure, host_out);
+}
+
+int spt_denoise_blended(spt_ctx* c, const spt_denoise_params* params) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
+    return denoise_image(c, c->blend, 0.0f, params);
+}
+
+int spt_set_history_layout(spt_ctx* c, int layout) {
+    if (!c) return SPT_ERR_INVALID;
+    if (layout != -1 && layout != kHistoryPlanes && layout != kHistoryRecords)
+        return fail(c, SPT_ERR_INVALID, "spt_set_history_layout: -1 (automatic), 0 (three images) or 1 (48-byte records)");
+    c->hist_layout = layout;
+    return SPT_OK;
+}
+
+int spt_reproject_basis(const spt_camera* cam, float rows[9], float origin[3], float* j) {
+    if (!rows || !origin || !j) return SPT_ERR_INVALID;
+    if (cam && camera_error(*cam)) return SPT_ERR_INVALID;
+    const ReprojectView v = reproject_view(cam);
+    for (int a = 0; a < 3; ++a) {
+        rows[a] = v.ru[a];
+        rows[3 + a] = v.rv[a];
+        rows[6 + a] = v.rw[a];
+        origin[a] = v.o[a];
+    }
+    *j = v.j;
+    return SPT_OK;
+}
+
+int spt_reproject_host(const spt_reproject_params* params, const spt_camera* prev_camera, uint32_t width, uint32_t height,
+                       const float* cur_a, const float* cur_b, const float* hist_rgba, const float* hist_a,
+                       const float* hist_b, const uint32_t* material_reusable, uint32_t n_materials, float* out) {
+    if (!cur_a || !cur_b || !hist_rgba || !hist_a || !hist_b || !out || width == 0 || height == 0) return SPT_ERR_INVALID;
+    if ((uint64_t)width * height >= (1ull << 31)) return SPT_ERR_INVALID;
+    const spt_reproject_params p = params ? *params : kReprojectDefaults;
+    if (reproject_params_error(p)) return SPT_ERR_INVALID;
+    if (prev_camera && camera_error(*prev_camera)) return SPT_ERR_INVALID;
+    const ReprojectView v = reproject_view(prev_camera);
+    auto px = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
+    const size_t n = (size_t)width * height;
+    for (size_t at = 0; at < n; ++at) {
+        const float4 o = reproject_pixel(
+            px(cur_a, at), px(cur_b, at), (int)width, (int)height, v, p, material_reusable, n_materials,
+            [&](size_t q) { return px(hist_a, q); }, [&](size_t q) { return px(hist_b, q); },
+            [&](size_t q) { return px(hist_rgba, q); });
+        out[4 * at + 0] = o.x;
+        out[4 * at + 1] = o.y;
+        out[4 * at + 2] = o.z;
+        out[4 * at + 3] = o.w;
+    }
     return SPT_OK;
 }
 
