@@ -18,6 +18,7 @@
 
 #include "scene.h"
 #include "spt.h"
+#include "spt_ctx_state.h"
 #include "spt_denoise.h"
 #include "spt_device.h"
 #include "spt_jit.h"
@@ -76,10 +77,7 @@ struct ViewHalf {
     hipStream_t stream = nullptr;  // non-blocking, created with the ctx
     hipEvent_t done = nullptr;     // behind the half's last launch of a call: the ctx stream waits on it (the join)
     uint16_t* cost = nullptr;      // the half's first-tier chunk costs and order (PassParams), [pixels / 2 + 64]
-    uint32_t* order = nullptr;
-    uint64_t order_key = 0;        // 0: no order. Cleared when the view's lists are built (every clear of the ctx's
-                                   // chunk_order_key comes with view_valid = false, so the lists are rebuilt before
-                                   // a half launches again), with the buffers, and by a failed launch
+    uint32_t* order = nullptr;     // (its key: DerivedState::half_order_key)
     uint32_t* work = nullptr;      // 2 sets of kWorkWords of its own (k_paths zeroes work_next in stream order:
     uint32_t work_parity = 0;      // a set is never shared across streams)
 };
@@ -109,6 +107,7 @@ struct spt_ctx {
     bool accum_shared = false;
     std::string err;
     uint32_t cu_count = 256;
+    DerivedState derived;  // which of the results cached below are valid (spt_ctx_state.h: what each change drops)
 
     // scene
     float4* d_prims = nullptr;
@@ -151,24 +150,18 @@ struct spt_ctx {
     float4* radiance = nullptr;
     float4* accum = nullptr;
     float2* hit_cache = nullptr;  // k_frame: each shard pixel's camera-segment closest hit (configure-sized)
-    bool hit_cache_valid = false;  // it holds the current scene's and configuration's hits
     uint16_t* chunk_cost = nullptr;   // flat k_paths' first-tier chunk costs and order (PassParams)
     uint32_t* chunk_order = nullptr;
-    uint64_t chunk_order_key = 0;     // 0: no order (cleared with the hit cache by a scene or size change)
     // Flat k_paths' view lists (spt_kernels.h ViewPlan): every pixel's bounce 0, compacted into live-pixel
-    // records and constant pixels. Built behind the first persistent launch after anything that changes a
-    // pixel's bounce 0 (wherever hit_cache_valid or chunk_order_key is cleared, and a new environment map);
-    // the persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
+    // records and constant pixels. Built behind the first persistent launch that finds them dropped; the
+    // persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
     float4* view_live = nullptr;      // [3 * pixels] allocated by the first build
     float4* view_const = nullptr;     // [pixels]
     uint32_t* view_counts = nullptr;  // [2] live, constant; then the compaction's per-block scratch
     uint32_t view_n[2] = {0, 0};      // view_counts[0..1], read back once per build
-    bool view_valid = false;
-    bool view_no_memory = false;      // the lists' allocation failed: the pixel plan runs until the next spt_configure
     int32_t view_cache = 0;           // spt_tuning: 0 = automatic, -1 = never (every launch computes bounce 0 itself)
     bool last_view_cached = false;    // the last persistent launch ran over the lists
-    bool frame_lists = false;     // ... and k_frame takes the compacted lists (hit_mode 3)
-    uint4* live_rec = nullptr;     // ... compacted: the live pixels' records (kFrameHitCache 2)
+    uint4* live_rec = nullptr;     // hit_cache compacted: the live pixels' records (kFrameHitCache 2)
     uint32_t* sky_pix = nullptr;   // ... the sky pixels' indices
     uint32_t* list_counts = nullptr;  // [2] live, sky; then the compaction's per-block scratch
     uint32_t live_pixels = 0;         // list_counts[0], read back once per compaction
@@ -197,30 +190,23 @@ struct spt_ctx {
     float4* feat_a = nullptr;
     float4* feat_b = nullptr;
     float4* feat_albedo = nullptr;
-    bool feat_valid = false;
     uint32_t* d_mat_map = nullptr;
-    // spt_denoise: the filter's two ping-pong images (allocated by the first call) and which one holds
-    // the last call's result (-1: none)
+    // spt_denoise: the filter's two ping-pong images (allocated by the first call)
     float4* dn[2] = {nullptr, nullptr};
-    int dn_result = -1;
     int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
     // Temporal reprojection, every buffer allocated by the first call that needs it (configure-sized).
     // spt_history_capture: the captured view — image with lengths, feat_a, feat_b in 3 * pixels float4, laid
     // out as hist_view_layout says (spt_reproject.h) — and its camera
     float4* hist_view = nullptr;
     int hist_view_layout = 0;
-    bool hist_view_valid = false;
     bool hist_view_has_camera = false;
     spt_camera hist_view_camera{};
     float4* hist = nullptr;      // spt_reproject: the active history (rgb, length)
-    bool hist_valid = false;
     float4* blend = nullptr;     // spt_history_blend: the blended image
-    bool blend_valid = false;
     int hist_layout = -1;        // spt_set_history_layout: -1 the layout measured faster
     // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
-    // model is not DIFFUSE (bsdf), dropped with the models
+    // model is not DIFFUSE (bsdf)
     uint32_t* d_reusable = nullptr;
-    bool reusable_valid = false;
 
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
@@ -326,13 +312,6 @@ void free_dev(T*& p) {
     p = nullptr;
 }
 
-// The radiance changed (scene, materials, sky, configuration): neither the captured view nor the active history
-// holds an estimate of it any more. A camera or lens change drops the active history alone (view = false).
-void drop_history(spt_ctx* c, bool view) {
-    if (view) c->hist_view_valid = false;
-    c->hist_valid = false;
-}
-
 void free_buffers(spt_ctx* c) {
     for (int k = 0; k < 2; ++k) {
         free_dev(c->q_o[k]);
@@ -349,33 +328,26 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->hit_cache);
     free_dev(c->chunk_cost);
     free_dev(c->chunk_order);
-    c->chunk_order_key = 0;
     for (ViewHalf& h : c->half) {
         free_dev(h.cost);
         free_dev(h.order);
-        h.order_key = 0;
     }
     free_dev(c->view_live);
     free_dev(c->view_const);
     free_dev(c->view_counts);
-    c->view_valid = false;
-    c->view_no_memory = false;
     free_dev(c->live_rec);
     free_dev(c->sky_pix);
     free_dev(c->list_counts);
-    c->hit_cache_valid = false;
     free_dev(c->resolved);
     free_dev(c->feat_a);
     free_dev(c->feat_b);
     free_dev(c->feat_albedo);
-    c->feat_valid = false;
     free_dev(c->dn[0]);
     free_dev(c->dn[1]);
-    c->dn_result = -1;
     free_dev(c->hist_view);
     free_dev(c->hist);
     free_dev(c->blend);
-    c->hist_view_valid = c->hist_valid = c->blend_valid = false;
+    c->derived.drop(Change::Buffers);
 }
 
 // RCCL, resolved at run time (spt.h): the copy already in the process (PyTorch loads its own
@@ -440,9 +412,7 @@ void free_comm(spt_ctx* c) {
 }
 
 void free_scene(spt_ctx* c) {
-    c->hit_cache_valid = false;  // (the camera hits were this scene's)
-    c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
-    c->view_valid = false;   // (... and the view's bounce 0)
+    c->derived.drop(Change::Scene);
     free_dev(c->bvh_stack);
     c->bvh_stack_stride = 0;
     free_dev(c->d_prims);
@@ -450,10 +420,7 @@ void free_scene(spt_ctx* c) {
     free_dev(c->d_nodes);
     free_dev(c->d_emit);
     free_dev(c->d_mat_map);
-    c->feat_valid = false;  // (the first hits were this scene's)
-    drop_history(c, true);
     free_dev(c->d_reusable);
-    c->reusable_valid = false;
     c->n_prims = c->n_nodes = c->n_dev_nodes = c->n_emit = c->n_emit_spheres = 0;
     c->has_scene = false;
 }
@@ -1013,11 +980,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     if (!prepare_prims(prims, n, (uint32_t)c->h_mats.size(), upd, &msg)) return fail(c, SPT_ERR_INVALID, msg);
     for (uint32_t j = 0; j < n; ++j)
         if (indices[j] >= total) return fail(c, SPT_ERR_INVALID, "spt_update_prims: index out of range");
-    c->hit_cache_valid = false;  // (moved primitives: k_frame traces the camera segments again)
-    c->feat_valid = false;       // (... and spt_render_features the first hits)
-    drop_history(c, true);       // (... and the history other radiance)
-    c->chunk_order_key = 0;  // (the chunks' costs were this scene's)
-    c->view_valid = false;   // (... and the view's bounce 0)
+    c->derived.drop(Change::Prims);
     // the edits are staged and committed to the host mirror only once the device holds them, so a
     // failed call leaves the ctx's scene as it was
     std::vector<spt_prim> all = c->h_prims;
@@ -1179,13 +1142,7 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
         }
         SPT_HIP(c, hipMalloc(&c->resolved, sizeof(uint32_t) * std::max<size_t>(pixels, 1)));
     }
-    c->hit_cache_valid = false;  // (a new image size, shard or flags: the camera hits are traced again)
-    c->feat_valid = false;
-    c->dn_result = -1;  // (no denoised image of this configuration yet)
-    drop_history(c, true);  // (... no history: another size, or other paths)
-    c->blend_valid = false;
-    c->chunk_order_key = 0;
-    c->view_valid = false;  // (another size, shard, flags or bounce limit: another bounce 0 per pixel)
+    c->derived.drop(Change::Configuration);
     const size_t qn = (size_t)cap * c->n_sub;
     if ((cfg->flags & SPT_FLAG_SORTED_RAYS) && qn && !c->ray_perm) {  // the sorted schedule's buffers
         SPT_HIP(c, hipMalloc(&c->ray_keys, sizeof(uint16_t) * qn));
@@ -1230,7 +1187,7 @@ static int build_view_lists(spt_ctx* c, const PassParams& p) {
             free_dev(c->view_live);
             free_dev(c->view_const);
             free_dev(c->view_counts);
-            c->view_no_memory = true;
+            c->derived.produced(kViewNoMemory);
             return SPT_OK;
         }
     }
@@ -1238,8 +1195,7 @@ static int build_view_lists(spt_ctx* c, const PassParams& p) {
     SPT_HIP(c, hipGetLastError());
     SPT_HIP(c, hipMemcpyAsync(c->view_n, c->view_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, on_stream(c)));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    c->view_valid = true;
-    for (ViewHalf& h : c->half) h.order_key = 0;  // (the halves' chunk orders were the old lists')
+    c->derived.produced_view_lists();
     return SPT_OK;
 }
 
@@ -1271,7 +1227,6 @@ static bool half_buffers(spt_ctx* c) {
             free_dev(h.order);
             return false;
         }
-        h.order_key = 0;
     }
     return true;
 }
@@ -1306,7 +1261,7 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
         vh.work_parity ^= 1u;
         p.chunk_cost = vh.cost;
         p.chunk_order = vh.order;
-        p.chunk_order_key = &vh.order_key;
+        p.chunk_order_key = &c->derived.half_order_key[h];
         if (timed) {
             if (take_events(c, ev[n_ev], 4) != SPT_OK) return SPT_ERR_HIP;
             ++n_ev;
@@ -1317,7 +1272,7 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
         // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) {
-            vh.order_key = 0;
+            c->derived.half_order_key[h] = 0;
             rc = fail(c, SPT_ERR_HIP, std::string("k_paths (split): ") + hipGetErrorString(le));
         }
         if (timed && hipEventRecord(ev[n_ev - 1].b, vh.stream) != hipSuccess) rc = fail(c, SPT_ERR_HIP, "k_paths (split): hipEventRecord");
@@ -1325,7 +1280,7 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
     c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
     if (rc != SPT_OK) {
         for (int i = 0; i < n_ev; ++i) c->free_events.push_back(ev[i]);
-        for (ViewHalf& h : c->half) h.order_key = 0;
+        c->derived.half_order_key[0] = c->derived.half_order_key[1] = 0;
         return rc;
     }
     if (n_ev) {  // one persistent launch: the two pairs as one record
@@ -1362,7 +1317,7 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
     while (done < n_frames) {
         // (a call whose launches over the view may be wide takes at most kWideMaxFrames frames per such launch:
         // the ring's lap byte; decided for the call, as the split is)
-        const bool view_now = c->view_cache >= 0 && c->view_valid && view_lists_scene(p);
+        const bool view_now = c->view_cache >= 0 && c->derived.valid(kViewLists) && view_lists_scene(p);
         const int wide = view_now ? wide_call(c->wide_chunks, wide_eligible(p), wide_first_tier(c->pixels, c->cu_count), c->view_n[0], n_frames) : 0;
         const uint32_t f = std::min(wide ? kWideMaxFrames : kPersistentMaxFrames, n_frames - done);
         p.first_frame = first_frame + done;
@@ -1371,7 +1326,7 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
         // a flat scene's view lists, once they are built (below): the launch runs over them
         const bool view_scene = c->view_cache >= 0 && view_lists_scene(p);
         const ViewPlan view{c->view_live, c->view_const, c->view_n[0], c->view_n[1], 0u};
-        const bool view_on = view_scene && c->view_valid;
+        const bool view_on = view_scene && c->derived.valid(kViewLists);
         // ... in two halves on two streams (the first persistent launch of a view stays whole on the ctx
         // stream: it builds the lists). Decided for the call, not for the launch: the same answer for every
         // launch of the call once the lists exist.
@@ -1391,19 +1346,20 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
         next_work_set(c, p);
         p.chunk_cost = c->chunk_cost;
         p.chunk_order = c->chunk_order;
-        p.chunk_order_key = &c->chunk_order_key;
+        p.chunk_order_key = &c->derived.chunk_order_key;
         c->last_specialized = launch_paths(p, c->counters, on_stream(c), view_on ? &view : nullptr, 0u, wide, &c->last_view_wide);
         c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
         c->last_view_cached = view_on;
         // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
         const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) c->chunk_order_key = 0;
+        if (le != hipSuccess) c->derived.chunk_order_key = 0;
         if (end_persistent(c, ev) != SPT_OK) {
-            c->chunk_order_key = 0;
+            c->derived.chunk_order_key = 0;
             return SPT_ERR_HIP;
         }
         SPT_HIP(c, le);
-        if (view_scene && !c->view_valid && !c->view_no_memory && build_view_lists(c, p) != SPT_OK) return SPT_ERR_HIP;
+        const bool build = view_scene && !c->derived.valid(kViewLists) && !c->derived.valid(kViewNoMemory);
+        if (build && build_view_lists(c, p) != SPT_OK) return SPT_ERR_HIP;
         done += f;
         c->passes++;
     }
@@ -1453,7 +1409,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             p.list_counts = c->list_counts;
             // (a jittered or lens camera: hit_mode 0, the camera segment traced per frame; no cache, no lists, no wait)
             const bool jitter = cam_per_path(p.cam_mode) || p.bsdf != 0u;  // (and so do material models)
-            p.hit_mode = frame_hit_mode(p, c->hit_cache_valid, c->frame_lists);
+            p.hit_mode = frame_hit_mode(p, c->derived.valid(kCameraHits), c->derived.frame_lists());
             p.live_pixels = c->live_pixels;
             if (c->fuse_frames != 0.0f && done + 1u == n_frames) {  // the call's last frame resolves as it ends
                 p.rgba = (uint32_t*)c->out_dev;
@@ -1465,8 +1421,8 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
             if (end_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
             SPT_HIP(c, hipGetLastError());
-            if (!c->hit_cache_valid) c->frame_lists = false;
-            if (!jitter && !c->hit_cache_valid && frame_lists_scene(p, c->counters)) {  // compacted once (stream order)
+            bool lists = c->derived.frame_lists();
+            if (!jitter && !c->derived.valid(kCameraHits) && frame_lists_scene(p, c->counters)) {  // compacted once (stream order)
                 launch_hit_lists(p, c->list_counts + 2, on_stream(c));
                 SPT_HIP(c, hipGetLastError());
                 // the live count sizes the next launches' grids: read back once per scene / configuration
@@ -1474,9 +1430,9 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
                 SPT_HIP(c, hipMemcpyAsync(&c->live_pixels, c->list_counts, sizeof(uint32_t), hipMemcpyDeviceToHost,
                                           on_stream(c)));
                 SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-                c->frame_lists = c->pixels - c->live_pixels >= c->pixels / kFrameListsMinSkyDiv;
+                lists = c->pixels - c->live_pixels >= c->pixels / kFrameListsMinSkyDiv;
             }
-            if (!jitter) c->hit_cache_valid = true;  // (stream order: the next launch reads what this one stored)
+            if (!jitter) c->derived.produced_camera_hits(lists);  // (stream order: the next launch reads what this one stored)
             c->passes++;
         }
         c->frames += n_frames;
@@ -1583,23 +1539,28 @@ int spt_resolve_rgba8(spt_ctx* c, uint32_t frame_count, uint32_t* host_out) {
     return spt_resolve_rgba8_exposure(c, frame_count, 1.0f, host_out);
 }
 
-int spt_resolve_rgba8_exposure(spt_ctx* c, uint32_t frame_count, float exposure, uint32_t* host_out) {
-    if (!c || !host_out) return SPT_ERR_INVALID;
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
-    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");  // CPUPathTracer.cpp:89
+// img / divisor as RGBA8 in host_out, waited for (the sums and a frame count, or a mean and 1)
+static int resolve_image(spt_ctx* c, const float4* img, float divisor, float exposure, uint32_t* host_out) {
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pixels == 0) return SPT_OK;
     if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
         // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, (uint32_t*)c->out_dev, on_stream(c));
+        launch_resolve(img, c->pixels, divisor, exposure, (uint32_t*)c->out_dev, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     } else {
-        launch_resolve(c->accum, c->pixels, (float)frame_count, exposure, c->resolved, on_stream(c));
+        launch_resolve(img, c->pixels, divisor, exposure, c->resolved, on_stream(c));
         SPT_HIP(c, hipGetLastError());
         SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
     }
     SPT_HIP(c, wait_frame(c));
     return SPT_OK;
+}
+
+int spt_resolve_rgba8_exposure(spt_ctx* c, uint32_t frame_count, float exposure, uint32_t* host_out) {
+    if (!c || !host_out) return SPT_ERR_INVALID;
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
+    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");  // CPUPathTracer.cpp:89
+    return resolve_image(c, c->accum, (float)frame_count, exposure, host_out);
 }
 
 int spt_render_resolve_rgba8(spt_ctx* c, uint32_t first_frame, uint32_t n_frames, uint32_t frame_count, float exposure,
@@ -1675,8 +1636,7 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
         c->env_w = width;
         c->env_h = height;
     }
-    c->view_valid = false;  // (k_paths' view lists hold the sky pixels' radiance)
-    drop_history(c, true);  // (... and the history the old sky's light)
+    c->derived.drop(Change::Sky);
     if (c->configured) return spt_reset(c);  // a different sky: the accumulation restarts
     return SPT_OK;
 }
@@ -1711,13 +1671,7 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
         c->has_lens = false;  // (the reference's pinhole has no lens)
     }
     c->has_camera = cam != nullptr;
-    // the camera hits k_frame cached and the chunk costs k_paths recorded were the previous camera's
-    c->hit_cache_valid = false;
-    c->frame_lists = false;
-    c->chunk_order_key = 0;
-    c->view_valid = false;  // (k_paths' view lists too)
-    c->feat_valid = false;  // (the first hits were the previous camera's)
-    drop_history(c, false);  // (the active history was mapped into the previous view; the captured view stays)
+    c->derived.drop(Change::Camera);
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
     return SPT_OK;
@@ -1745,13 +1699,7 @@ int spt_set_camera_lens(spt_ctx* c, const spt_lens* lens) {
         c->lens = old;
         return rc;
     }
-    // as spt_set_camera: what k_frame cached and k_paths recorded were the previous camera rays'. The
-    // feature images stay: they are the chief ray's, whatever the lens (k_features)
-    c->hit_cache_valid = false;
-    c->frame_lists = false;
-    c->chunk_order_key = 0;
-    c->view_valid = false;
-    drop_history(c, false);  // (as spt_set_camera: the frames that follow are another view's)
+    c->derived.drop(Change::Lens);
     prefetch_flat(c);
     if (c->configured) return spt_reset(c);
     return SPT_OK;
@@ -1775,13 +1723,7 @@ int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32
         c->h_models = old;
         return SPT_ERR_HIP;
     }
-    // what was cached for the old materials' kernels: k_frame's camera hits and lists, k_paths' chunk costs
-    c->hit_cache_valid = false;
-    c->frame_lists = false;
-    c->chunk_order_key = 0;
-    c->view_valid = false;  // (k_paths' view lists: the kBsdf kernels take none)
-    drop_history(c, true);  // (other materials: other radiance)
-    c->reusable_valid = false;
+    c->derived.drop(Change::Materials);
     if (c->configured) return spt_reset(c);  // other materials: the accumulation restarts
     return SPT_OK;
 }
@@ -1821,29 +1763,26 @@ const char* denoise_params_error(const spt_denoise_params& p) {
     if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_denoise_params: reserved must be 0";
     return nullptr;
 }
+int alloc_image(spt_ctx* c, float4*& img, size_t pixels, const char* who) {
+    if (img) return SPT_OK;
+    if (hipMalloc(&img, sizeof(float4) * pixels) != hipSuccess) {
+        img = nullptr;
+        (void)hipGetLastError();
+        return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
+    }
+    return SPT_OK;
+}
 // the images are those of the current scene, camera and configuration (rendered now if they are not)
 int ensure_features(spt_ctx* c) {
     if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "features before spt_configure");
     SPT_HIP(c, hipSetDevice(c->device));
-    if (c->feat_valid || c->pixels == 0) return SPT_OK;
-    if (!c->feat_a) {  // all three, or none
-        float4 *a = nullptr, *b = nullptr, *alb = nullptr;
-        const size_t bytes = sizeof(float4) * c->pixels;
-        if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess || hipMalloc(&alb, bytes) != hipSuccess) {
-            free_dev(a);
-            free_dev(b);
-            free_dev(alb);
-            (void)hipGetLastError();
-            return fail(c, SPT_ERR_HIP, "spt_render_features: allocation failed");
-        }
-        c->feat_a = a;
-        c->feat_b = b;
-        c->feat_albedo = alb;
-    }
+    if (c->derived.valid(kFeatures) || c->pixels == 0) return SPT_OK;
+    for (float4** img : {&c->feat_a, &c->feat_b, &c->feat_albedo})
+        if (const int rc = alloc_image(c, *img, c->pixels, "spt_render_features"); rc != SPT_OK) return rc;
     launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, on_stream(c));
     SPT_HIP(c, hipGetLastError());
-    c->feat_valid = true;
+    c->derived.produced(kFeatures);
     return SPT_OK;
 }
 }  // namespace
@@ -1893,18 +1832,9 @@ static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt
     if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise: image taller than 262140 rows");
     const int rc = ensure_features(c);
     if (rc != SPT_OK || c->pixels == 0) return rc;
-    if (!c->dn[0]) {  // both, or none
-        float4 *a = nullptr, *b = nullptr;
-        if (hipMalloc(&a, sizeof(float4) * c->pixels) != hipSuccess || hipMalloc(&b, sizeof(float4) * c->pixels) != hipSuccess) {
-            free_dev(a);
-            free_dev(b);
-            (void)hipGetLastError();
-            return fail(c, SPT_ERR_HIP, "spt_denoise: allocation failed");
-        }
-        c->dn[0] = a;
-        c->dn[1] = b;
-    }
-    c->dn_result = -1;
+    for (float4*& img : c->dn)
+        if (const int rc = alloc_image(c, img, c->pixels, "spt_denoise"); rc != SPT_OK) return rc;
+    c->derived.begin(kDenoised);
     const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
     for (uint32_t l = 0; l < p.levels; ++l) {
         const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
@@ -1913,7 +1843,7 @@ static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt
                       c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     }
-    c->dn_result = (int)((p.levels - 1u) & 1u);
+    c->derived.produced_denoised((int)((p.levels - 1u) & 1u));
     return SPT_OK;
 }
 
@@ -1932,43 +1862,53 @@ int spt_set_denoise_form(spt_ctx* c, int form) {
     return SPT_OK;
 }
 
-int spt_read_denoised(spt_ctx* c, float* host_rgba) {
+// ---- the post-processed images: denoised, active history, blended ---------------------------------
+// Each is described once: a pointer, whether it is valid (spt_ctx_state.h) and what to say when it is not.
+// Reading one back, handing out its address and resolving it to RGBA8 are one body each, for all of them.
+enum PostImage { kImgDenoised, kImgHistory, kImgBlended };
+// the image, or nullptr with the ctx's error set: there is none
+static float4* post_image(spt_ctx* c, PostImage which) {
+    const DerivedState& d = c->derived;
+    const struct {
+        float4* img;  // (a valid one was allocated: never nullptr)
+        const char* missing;
+    } images[] = {{d.valid(kDenoised) ? c->dn[d.dn_result] : nullptr, "no denoised image: spt_denoise first"},
+                  {d.valid(kHistory) ? c->hist : nullptr, "no active history: spt_reproject first"},
+                  {d.valid(kBlended) ? c->blend : nullptr, "no blended image: spt_history_blend first"}};
+    if (!images[which].img) fail(c, SPT_ERR_INVALID, images[which].missing);
+    return images[which].img;
+}
+
+static int read_image(spt_ctx* c, PostImage which, float* host_rgba) {
     if (!c || !host_rgba) return SPT_ERR_INVALID;
-    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
+    const float4* img = post_image(c, which);
+    if (!img) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_rgba, c->dn[c->dn_result], sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipMemcpyAsync(host_rgba, img, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
     return SPT_OK;
 }
 
-int spt_denoised_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
+static int image_device_ptr(spt_ctx* c, PostImage which, void** dptr, size_t* bytes) {
     if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
-    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
-    *dptr = c->dn[c->dn_result];
+    float4* img = post_image(c, which);
+    if (!img) return SPT_ERR_INVALID;
+    *dptr = img;
     *bytes = sizeof(float4) * (size_t)c->pixels;
     return SPT_OK;
 }
 
 // spt_resolve_rgba8_exposure of an image that is already a mean (divisor 1)
-static int resolve_mean_rgba8(spt_ctx* c, const float4* img, float exposure, uint32_t* host_out) {
-    if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
-        // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch_resolve(img, c->pixels, 1.0f, exposure, (uint32_t*)c->out_dev, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-    } else {
-        launch_resolve(img, c->pixels, 1.0f, exposure, c->resolved, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    }
-    SPT_HIP(c, wait_frame(c));
-    return SPT_OK;
+static int resolve_mean_rgba8(spt_ctx* c, PostImage which, float exposure, uint32_t* host_out) {
+    if (!c || !host_out) return SPT_ERR_INVALID;
+    const float4* img = post_image(c, which);
+    return img ? resolve_image(c, img, 1.0f, exposure, host_out) : SPT_ERR_INVALID;
 }
 
+int spt_read_denoised(spt_ctx* c, float* host_rgba) { return read_image(c, kImgDenoised, host_rgba); }
+int spt_denoised_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgDenoised, dptr, bytes); }
 int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
-    if (!c || !host_out) return SPT_ERR_INVALID;
-    if (c->dn_result < 0) return fail(c, SPT_ERR_INVALID, "no denoised image: spt_denoise first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    return resolve_mean_rgba8(c, c->dn[c->dn_result], exposure, host_out);
+    return resolve_mean_rgba8(c, kImgDenoised, exposure, host_out);
 }
 
 int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
@@ -2030,21 +1970,6 @@ int history_ready(spt_ctx* c, const char* who, bool features) {
     SPT_HIP(c, hipSetDevice(c->device));
     return SPT_OK;
 }
-int alloc_image(spt_ctx* c, float4*& img, size_t pixels, const char* who) {
-    if (img) return SPT_OK;
-    if (hipMalloc(&img, sizeof(float4) * pixels) != hipSuccess) {
-        img = nullptr;
-        (void)hipGetLastError();
-        return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
-    }
-    return SPT_OK;
-}
-int read_image(spt_ctx* c, const float4* img, float* host_rgba) {
-    SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_rgba, img, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
 }  // namespace
 
 int spt_reproject_params_default(spt_reproject_params* out) {
@@ -2058,15 +1983,15 @@ int spt_history_capture(spt_ctx* c, uint32_t frame_count) {
     if (const int rc = history_ready(c, "spt_history_capture", true); rc != SPT_OK) return rc;
     if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
     if (const int rc = alloc_image(c, c->hist_view, 3 * (size_t)c->pixels, "spt_history_capture"); rc != SPT_OK) return rc;
-    c->hist_view_valid = false;
+    c->derived.begin(kCapturedView);
     const int layout = c->hist_layout >= 0 ? c->hist_layout : kHistoryDefault;
-    launch_history_capture(layout, c->accum, (float)frame_count, c->hist_valid ? c->hist : nullptr, c->feat_a, c->feat_b,
+    launch_history_capture(layout, c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->feat_a, c->feat_b,
                            c->hist_view, c->pixels, on_stream(c));
     SPT_HIP(c, hipGetLastError());
     c->hist_view_layout = layout;
     c->hist_view_has_camera = c->has_camera;
     c->hist_view_camera = c->camera;
-    c->hist_view_valid = true;
+    c->derived.produced(kCapturedView);
     return SPT_OK;
 }
 
@@ -2075,83 +2000,57 @@ int spt_reproject(spt_ctx* c, const spt_reproject_params* params) {
     const spt_reproject_params p = params ? *params : kReprojectDefaults;
     if (const char* msg = reproject_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
     if (const int rc = history_ready(c, "spt_reproject", true); rc != SPT_OK) return rc;
-    if (!c->hist_view_valid) return fail(c, SPT_ERR_INVALID, "no captured view: spt_history_capture first");
+    if (!c->derived.valid(kCapturedView)) return fail(c, SPT_ERR_INVALID, "no captured view: spt_history_capture first");
     if (const int rc = alloc_image(c, c->hist, c->pixels, "spt_reproject"); rc != SPT_OK) return rc;
-    c->hist_valid = false;
+    c->derived.begin(kHistory);
     const uint32_t n_mats = (uint32_t)c->h_mats.size();
-    if (c->bsdf && !c->reusable_valid) {
+    if (c->bsdf && !c->derived.valid(kReusable)) {
         // (spt_set_material_models drained the stream before it changed the models: nothing reads the old words)
         std::vector<uint32_t> words(n_mats);
         for (uint32_t m = 0; m < n_mats; ++m) words[m] = c->h_models[m].kind == SPT_MAT_DIFFUSE ? 1u : 0u;
         if (!c->d_reusable) SPT_HIP(c, hipMalloc(&c->d_reusable, sizeof(uint32_t) * n_mats));
         SPT_HIP(c, hipMemcpy(c->d_reusable, words.data(), sizeof(uint32_t) * n_mats, hipMemcpyHostToDevice));
-        c->reusable_valid = true;
+        c->derived.produced(kReusable);
     }
     const ReprojectView v = reproject_view(c->hist_view_has_camera ? &c->hist_view_camera : nullptr);
     launch_reproject(c->hist_view_layout, c->feat_a, c->feat_b, c->hist_view, c->hist, c->cfg.width, c->cfg.height, v, p,
                      c->bsdf ? c->d_reusable : nullptr, n_mats, on_stream(c));
     SPT_HIP(c, hipGetLastError());
-    c->hist_valid = true;
+    c->derived.produced(kHistory);
     return SPT_OK;
 }
 
 int spt_history_clear(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
-    drop_history(c, true);
+    c->derived.drop(Change::HistoryClear);
     return SPT_OK;
 }
 
-int spt_read_history(spt_ctx* c, float* host_rgba) {
-    if (!c || !host_rgba) return SPT_ERR_INVALID;
-    if (!c->hist_valid) return fail(c, SPT_ERR_INVALID, "no active history: spt_reproject first");
-    return read_image(c, c->hist, host_rgba);
-}
-
-int spt_history_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
-    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
-    if (!c->hist_valid) return fail(c, SPT_ERR_INVALID, "no active history: spt_reproject first");
-    *dptr = c->hist;
-    *bytes = sizeof(float4) * (size_t)c->pixels;
-    return SPT_OK;
-}
+int spt_read_history(spt_ctx* c, float* host_rgba) { return read_image(c, kImgHistory, host_rgba); }
+int spt_history_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgHistory, dptr, bytes); }
 
 int spt_history_blend(spt_ctx* c, uint32_t frame_count) {
     if (!c) return SPT_ERR_INVALID;
     if (const int rc = history_ready(c, "spt_history_blend", false); rc != SPT_OK) return rc;
     if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
     if (const int rc = alloc_image(c, c->blend, c->pixels, "spt_history_blend"); rc != SPT_OK) return rc;
-    c->blend_valid = false;
-    launch_history_blend(c->accum, (float)frame_count, c->hist_valid ? c->hist : nullptr, c->blend, c->pixels, on_stream(c));
+    c->derived.begin(kBlended);
+    launch_history_blend(c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->blend, c->pixels, on_stream(c));
     SPT_HIP(c, hipGetLastError());
-    c->blend_valid = true;
+    c->derived.produced(kBlended);
     return SPT_OK;
 }
 
-int spt_read_blended(spt_ctx* c, float* host_rgba) {
-    if (!c || !host_rgba) return SPT_ERR_INVALID;
-    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
-    return read_image(c, c->blend, host_rgba);
-}
-
-int spt_blended_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) {
-    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
-    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
-    *dptr = c->blend;
-    *bytes = sizeof(float4) * (size_t)c->pixels;
-    return SPT_OK;
-}
-
+int spt_read_blended(spt_ctx* c, float* host_rgba) { return read_image(c, kImgBlended, host_rgba); }
+int spt_blended_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgBlended, dptr, bytes); }
 int spt_resolve_blended_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
-    if (!c || !host_out) return SPT_ERR_INVALID;
-    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    return resolve_mean_rgba8(c, c->blend, exposure, host_out);
+    return resolve_mean_rgba8(c, kImgBlended, exposure, host_out);
 }
 
 int spt_denoise_blended(spt_ctx* c, const spt_denoise_params* params) {
     if (!c) return SPT_ERR_INVALID;
-    if (!c->blend_valid) return fail(c, SPT_ERR_INVALID, "no blended image: spt_history_blend first");
-    return denoise_image(c, c->blend, 0.0f, params);
+    const float4* img = post_image(c, kImgBlended);
+    return img ? denoise_image(c, img, 0.0f, params) : SPT_ERR_INVALID;
 }
 
 int spt_set_history_layout(spt_ctx* c, int layout) {
@@ -2333,10 +2232,8 @@ int spt_set_profiling(spt_ctx* c, int mode) {
     c->profiling = (mode & (SPT_PROFILE_EVENTS | SPT_PROFILE_SPAN)) != 0;
     c->span = span;
     const bool counters = (mode & SPT_PROFILE_COUNTERS) != 0;
-    // k_frame's compacted camera-hit lists were chosen for the kernels of the old counters setting
-    // (frame_lists_scene: the counting kernels never hold a scene in LDS): decided again
-    if (counters != c->counters) c->hit_cache_valid = false;
-    if (counters != c->counters) c->view_valid = false;  // (k_paths' view lists with them)
+    // (frame_lists_scene: the counting kernels never hold a scene in LDS, so the lists are decided again)
+    if (counters != c->counters) c->derived.drop(Change::Counters);
     c->counters = counters;
     return SPT_OK;
 }
@@ -2388,7 +2285,7 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
     out->stack_need = c->bvh_stack_need;
     out->stalled_waves = tot[kTotStalled];
     out->view_cached = c->last_view_cached ? 1u : 0u;
-    out->view_live_pixels = c->view_valid ? c->view_n[0] : 0u;
+    out->view_live_pixels = c->derived.valid(kViewLists) ? c->view_n[0] : 0u;
     out->flat_pairs = c->last_specialized ? c->last_pairs : 0u;
     out->flat_pair_second_passes = tot[kTotPairSecond];
     out->flat_sphere_second_passes = tot[kTotSphereSecond];
