@@ -605,6 +605,101 @@ int spt_reproject_host(const spt_reproject_params* params, const spt_camera* pre
                        const float* hist_a, const float* hist_b, const uint32_t* material_reusable,
                        uint32_t n_materials, float* out);
 
+/* ---- exposure and tone mapping (the reference's RenderSettings: setExposure, setAutoExposure(enabled,
+ * target_luminance), getAutoExposure, getTargetLuminance) ---------------------------------------------
+ * A luminance meter (an integer histogram of the image), the exposure that brings the histogram's trimmed
+ * log-average to a target, and a display resolve with a tone-mapping operator. Everything the existing
+ * resolves do stays as it is; these are entry points beside them. The meter caches nothing in the ctx.
+ *
+ * Definition (spt_display_host / spt_luminance_histogram_host compute it on the CPU from the functions the
+ * kernels compile, csrc/spt_display.h: the same bits). All fp32, no contraction, `/` correctly rounded.
+ *
+ * Luminance and its bin, for a pixel p of an image with divisor f (the frame count for the sums, 1 for a mean):
+ *   m = p / f on r, g, b;   L = (0.2126f*m.r + 0.7152f*m.g) + 0.0722f*m.b   (the denoiser's luminance)
+ *   key = L > 0 ? (int)(bits(L) >> 20) : 0      (the exponent and three mantissa bits; NaN, zero, negatives: 0)
+ *   bin = min(max(key, 888) - 888, 255)
+ * Bin 0 is "black": everything below 2^-16 * 1.125, with NaN, zero and negatives; it is left out of the average.
+ * Bins 1..254 are eight sub-bins per octave from there upward; bin 255 is everything from 2^15 * 1.875 up, +inf
+ * included. Integer operations and one comparison only; the counts are uint32_t, so they do not depend on the
+ * order of addition, and the counts of row shards add up to the whole image's.
+ *
+ * Exposure from a histogram (host only; in double, in this order, rounded to float once at the end):
+ *   1. n = sum of counts[1..255]; n == 0: the exposure is 1.0f.
+ *   2. lo = low_fraction * n;  hi = (1 - high_fraction) * n.
+ *   3. for b = 1..255, with the cumulative count c0 before bin b and c1 = c0 + counts[b] after it:
+ *        w = max(0, min(c1, hi) - max(c0, lo));  key = 888 + b;  e = (key >> 3) - 127;  k = key & 7;
+ *        centre = e + log2(1 + (k + 0.5) / 8);   sw += w;  sl += w * centre.
+ *   4. exposure = target_luminance / exp2(sl / sw), clamped to [min_exposure, max_exposure].
+ * The two fractions are the shares of non-black pixels left out at the dark and the bright end, so that a light
+ * source or a black corner does not steer the picture.
+ *
+ * Display transform, per channel v of r, g, b: x = (v / f) * exposure.
+ *   SPT_TONEMAP_CLAMP:    clamp x to [0, 1], NaN becomes 0, (uint8)(x * 255.0f): spt_resolve_rgba8_exposure's.
+ *   the other two first:  x = x > 0 ? fminf(x, 65536.0f) : 0.0f   (NaN and negatives 0; inf never reaches them)
+ *   SPT_TONEMAP_REINHARD: y = x / (1.0f + x)
+ *   SPT_TONEMAP_ACES:     y = (x*(2.51f*x + 0.03f)) / (x*(2.43f*x + 0.59f) + 0.14f)   (the common rational fit)
+ *   both then clamp y to [0, 1] and take (uint8)(y * 255.0f).
+ * Alpha is (uint8)(clamp(a / f) * 255.0f), without exposure or operator; the bytes are packed as the other
+ * resolves pack them (R in the high byte). Not covered: an sRGB transfer curve, exposure smoothed over time. */
+#define SPT_METER_BINS 256
+enum spt_image {
+    SPT_IMAGE_ACCUM = 0,     /* the accumulated sums; frame_count is the divisor                     */
+    SPT_IMAGE_DENOISED = 1,  /* the last spt_denoise's image: a mean, divisor 1, frame_count ignored */
+    SPT_IMAGE_BLENDED = 2    /* the last spt_history_blend's image: a mean too                       */
+};
+enum spt_tonemap {
+    SPT_TONEMAP_CLAMP = 0,
+    SPT_TONEMAP_REINHARD = 1,
+    SPT_TONEMAP_ACES = 2
+};
+typedef struct spt_exposure_params {   /* 32 bytes */
+    float    target_luminance;  /* finite, > 0; default 0.18f: RenderSettings'                          */
+    float    low_fraction;      /* finite, >= 0; default 0.1f: the share of non-black pixels left out
+                                   at the dark end                                                      */
+    float    high_fraction;     /* finite, >= 0; default 0.02f: ... at the bright end; both below 1 in sum */
+    float    min_exposure;      /* finite, > 0; default 0.015625f                                       */
+    float    max_exposure;      /* finite, >= min_exposure; default 64.0f                               */
+    uint32_t reserved[3];       /* must be 0                                                            */
+} spt_exposure_params;
+typedef struct spt_display {           /* 16 bytes */
+    uint32_t tonemap;           /* spt_tonemap                                                          */
+    float    exposure;          /* finite, >= 0                                                         */
+    uint32_t reserved[2];       /* must be 0                                                            */
+} spt_display;
+/* Host only: the defaults above. SPT_ERR_INVALID for NULL. */
+int spt_exposure_params_default(spt_exposure_params* out);
+/* The histogram of the ctx's image (of its shard: the shards' counts add up to the whole image's) on the ctx
+ * stream, waited for. SPT_ERR_NOT_CONFIGURED before spt_configure; SPT_ERR_INVALID for an unknown image, a
+ * DENOISED or BLENDED image that does not exist, frame_count == 0 for ACCUM, or a null pointer. */
+int spt_meter_luminance(spt_ctx* ctx, uint32_t image, uint32_t frame_count, uint32_t counts[SPT_METER_BINS]);
+/* The same for n_pixels float RGBA pixels in the caller's device memory (the image spt_gather_image assembled on
+ * rank 0, for one). SPT_ERR_INVALID for a null pointer, n_pixels == 0 or a divisor that is not finite and > 0. */
+int spt_meter_device_image(spt_ctx* ctx, const void* device_rgba, uint64_t n_pixels, float divisor,
+                           uint32_t counts[SPT_METER_BINS]);
+/* The ctx's image through the display transform as RGBA8 in host_out, as spt_resolve_rgba8_exposure resolves (the
+ * registered host buffer is written directly, any other through the ctx's staging image; waits). Errors as
+ * spt_meter_luminance, and SPT_ERR_INVALID for an unknown operator, an exposure that is not finite and >= 0 or
+ * a non-zero reserved word. */
+int spt_resolve_display_rgba8(spt_ctx* ctx, uint32_t image, uint32_t frame_count, const spt_display* display,
+                              uint32_t* host_out);
+/* The same for the caller's device image, always through a staging image of the ctx's that grows on demand. */
+int spt_resolve_display_device_image(spt_ctx* ctx, const void* device_rgba, uint64_t n_pixels, float divisor,
+                                     const spt_display* display, uint32_t* host_out);
+/* Measurement and tests (the counts never depend on it): the kernel form of later meterings: 0 one LDS add per
+ * lane, 1 one add per distinct bin of a wave, -1 (the default) the one that measured faster.
+ * SPT_ERR_INVALID otherwise. */
+int spt_set_meter_form(spt_ctx* ctx, int form);
+/* Host only, no device needed: the definition above by the functions the kernels compile: the same bits.
+ * SPT_ERR_INVALID for a null pointer, n_pixels == 0, a divisor that is not finite and > 0, or parameters out
+ * of range (a non-finite value; target_luminance, min_exposure or max_exposure not > 0; min_exposure >
+ * max_exposure; a negative fraction; low_fraction + high_fraction >= 1; a non-zero reserved word). params = NULL:
+ * the defaults. */
+int spt_meter_bin(float luminance, uint32_t* bin);
+int spt_luminance_histogram_host(const float* rgba, uint64_t n_pixels, float divisor, uint32_t counts[SPT_METER_BINS]);
+int spt_exposure_from_histogram(const uint32_t counts[SPT_METER_BINS], const spt_exposure_params* params,
+                                float* exposure);
+int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const spt_display* display, uint32_t* out);
+
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */
 /* Miss radiance from an octahedral environment map instead of sample_sky's gradient (only while

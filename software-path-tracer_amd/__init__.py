@@ -72,6 +72,9 @@ assert PRIM_DTYPE.itemsize == 64 and MATERIAL_DTYPE.itemsize == 24
 MATERIAL_MODEL_DTYPE = np.dtype([("kind", "<u4"), ("param", "<f4"), ("reserved", "<u4", (2,))])
 assert MATERIAL_MODEL_DTYPE.itemsize == 16
 MAT_DIFFUSE, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2  # spt_material_kind
+METER_BINS = 256  # SPT_METER_BINS
+IMAGE_ACCUM, IMAGE_DENOISED, IMAGE_BLENDED = 0, 1, 2  # spt_image
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2  # spt_tonemap
 
 
 class SptEnv(ctypes.Structure):
@@ -193,6 +196,9 @@ EXPORTED_SYMBOLS = (
     "spt_history_device_ptr", "spt_history_blend", "spt_read_blended", "spt_blended_device_ptr",
     "spt_resolve_blended_rgba8", "spt_denoise_blended", "spt_set_history_layout", "spt_reproject_basis",
     "spt_reproject_host",
+    "spt_exposure_params_default", "spt_meter_luminance", "spt_meter_device_image", "spt_resolve_display_rgba8",
+    "spt_resolve_display_device_image", "spt_set_meter_form", "spt_meter_bin", "spt_luminance_histogram_host",
+    "spt_exposure_from_histogram", "spt_display_host",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -268,6 +274,44 @@ class ReprojectParams(ctypes.Structure):
             if k not in dict(self._fields_):
                 raise TypeError(f"unknown spt_reproject_params field {k}")
             setattr(self, k, v)
+
+
+class ExposureParams(ctypes.Structure):
+    """spt_exposure_params (32 bytes): the luminance the histogram's trimmed log-average is brought to (> 0), the
+    shares of non-black pixels left out at the dark and the bright end (>= 0, below 1 in sum) and the limits of
+    the result (> 0). ExposureParams() holds the library's defaults (spt_exposure_params_default); keyword
+    arguments replace single fields."""
+    _fields_ = [
+        ("target_luminance", ctypes.c_float),
+        ("low_fraction", ctypes.c_float),
+        ("high_fraction", ctypes.c_float),
+        ("min_exposure", ctypes.c_float),
+        ("max_exposure", ctypes.c_float),
+        ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        rc = load_library().spt_exposure_params_default(ctypes.byref(self))
+        if rc != SPT_OK:
+            raise SptError(f"spt_exposure_params_default -> {SPT_ERR.get(rc, rc)}")
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown spt_exposure_params field {k}")
+            setattr(self, k, v)
+
+
+class Display(ctypes.Structure):
+    """spt_display (16 bytes): the tone-mapping operator (TONEMAP_CLAMP, the default: the plain resolve's clamp;
+    TONEMAP_REINHARD; TONEMAP_ACES) and the exposure (finite, >= 0; default 1)."""
+    _fields_ = [
+        ("tonemap", ctypes.c_uint32),
+        ("exposure", ctypes.c_float),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+    def __init__(self, tonemap: int = TONEMAP_CLAMP, exposure: float = 1.0):
+        super().__init__(tonemap=tonemap, exposure=exposure)
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -367,6 +411,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_reproject_basis": ([ctypes.POINTER(SptCamera), P, P, ctypes.POINTER(ctypes.c_float)], I),
         "spt_reproject_host": ([ctypes.POINTER(ReprojectParams), ctypes.POINTER(SptCamera), U32, U32, P, P, P, P, P, P,
                                 U32, P], I),
+        "spt_exposure_params_default": ([ctypes.POINTER(ExposureParams)], I),
+        "spt_meter_luminance": ([P, U32, U32, P], I),
+        "spt_meter_device_image": ([P, P, ctypes.c_uint64, ctypes.c_float, P], I),
+        "spt_resolve_display_rgba8": ([P, U32, U32, ctypes.POINTER(Display), P], I),
+        "spt_resolve_display_device_image": ([P, P, ctypes.c_uint64, ctypes.c_float, ctypes.POINTER(Display), P], I),
+        "spt_set_meter_form": ([P, I], I),
+        "spt_meter_bin": ([ctypes.c_float, ctypes.POINTER(U32)], I),
+        "spt_luminance_histogram_host": ([P, ctypes.c_uint64, ctypes.c_float, P], I),
+        "spt_exposure_from_histogram": ([P, ctypes.POINTER(ExposureParams), ctypes.POINTER(ctypes.c_float)], I),
+        "spt_display_host": ([P, ctypes.c_uint64, ctypes.c_float, ctypes.POINTER(Display), P], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -556,6 +610,59 @@ def reproject_host(prev_cam: Optional[SptCamera], cur_a: np.ndarray, cur_b: np.n
                                            0 if table is None else table.size, _ptr(out))
     if rc != SPT_OK:
         raise SptError(f"spt_reproject_host -> {SPT_ERR.get(rc, rc)}")
+    return out
+
+
+def _pixels(rgba: np.ndarray, who: str) -> np.ndarray:
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    if a.ndim < 1 or a.shape[-1] != 4:
+        raise ValueError(f"{who}: rgba must be an array of float RGBA pixels (last axis 4)")
+    return a
+
+
+def meter_bin(luminance) -> int:
+    """spt_meter_bin (host only): the histogram bin of one luminance value, by the function the kernel compiles."""
+    b = ctypes.c_uint32(0)
+    rc = load_library().spt_meter_bin(ctypes.c_float(luminance), ctypes.byref(b))
+    if rc != SPT_OK:
+        raise SptError(f"spt_meter_bin -> {SPT_ERR.get(rc, rc)}")
+    return int(b.value)
+
+
+def luminance_histogram_host(rgba: np.ndarray, divisor: float = 1.0) -> np.ndarray:
+    """spt_luminance_histogram_host (host only): the METER_BINS counts of rgba / divisor (float RGBA pixels, any
+    leading shape), by the functions the kernel compiles: the same counts as Context.meter_luminance."""
+    a = _pixels(rgba, "luminance_histogram_host")
+    counts = np.zeros(METER_BINS, dtype=np.uint32)
+    rc = load_library().spt_luminance_histogram_host(_ptr(a), a.size // 4, divisor, _ptr(counts))
+    if rc != SPT_OK:
+        raise SptError(f"spt_luminance_histogram_host -> {SPT_ERR.get(rc, rc)}")
+    return counts
+
+
+def exposure_from_histogram(counts: np.ndarray, params: Optional[ExposureParams] = None) -> float:
+    """spt_exposure_from_histogram (host only): the exposure that brings the trimmed log-average luminance of a
+    histogram (METER_BINS counts; shards' counts added up) to params.target_luminance; 1.0 for an all-black one."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.shape != (METER_BINS,):
+        raise ValueError("exposure_from_histogram: counts must hold METER_BINS values")
+    e = ctypes.c_float(0.0)
+    rc = load_library().spt_exposure_from_histogram(_ptr(c), ctypes.byref(params) if params is not None else None,
+                                                    ctypes.byref(e))
+    if rc != SPT_OK:
+        raise SptError(f"spt_exposure_from_histogram -> {SPT_ERR.get(rc, rc)}")
+    return float(e.value)
+
+
+def display_host(rgba: np.ndarray, display: Display, divisor: float = 1.0) -> np.ndarray:
+    """spt_display_host (host only): rgba / divisor through the display transform as RGBA8 (uint32, R in the high
+    byte; the shape of rgba without its last axis), by the function the kernel compiles: the same bytes as
+    Context.resolve_display_rgba8."""
+    a = _pixels(rgba, "display_host")
+    out = np.zeros(a.shape[:-1], dtype=np.uint32)
+    rc = load_library().spt_display_host(_ptr(a), a.size // 4, divisor, ctypes.byref(display), _ptr(out))
+    if rc != SPT_OK:
+        raise SptError(f"spt_display_host -> {SPT_ERR.get(rc, rc)}")
     return out
 
 
@@ -939,6 +1046,50 @@ class Context:
         self._check(self.lib.spt_denoise_blended(self.h, ctypes.byref(params) if params is not None else None),
                     "spt_denoise_blended")
 
+    def meter_luminance(self, frame_count: int = 0, image: int = IMAGE_ACCUM) -> np.ndarray:
+        """spt_meter_luminance: the METER_BINS counts of the ctx's image (of its shard; shards' counts add up):
+        the accumulation over frame_count, or the denoised or blended image (a mean: frame_count is ignored)."""
+        counts = np.zeros(METER_BINS, dtype=np.uint32)
+        self._check(self.lib.spt_meter_luminance(self.h, image, frame_count, _ptr(counts)), "spt_meter_luminance")
+        return counts
+
+    def meter_device_image(self, dev_ptr: int, n_pixels: int, divisor: float = 1.0) -> np.ndarray:
+        """spt_meter_device_image: the same for n_pixels float RGBA pixels at a device address of the caller's."""
+        counts = np.zeros(METER_BINS, dtype=np.uint32)
+        self._check(self.lib.spt_meter_device_image(self.h, ctypes.c_void_p(dev_ptr), n_pixels, divisor, _ptr(counts)),
+                    "spt_meter_device_image")
+        return counts
+
+    def set_meter_form(self, form: int) -> None:
+        """spt_set_meter_form (measurement and tests): 0 one LDS add per lane in later meterings, 1 one add per
+        distinct bin of a wave, -1 the library's choice. The counts are the same."""
+        self._check(self.lib.spt_set_meter_form(self.h, form), "spt_set_meter_form")
+
+    def resolve_display_rgba8(self, frame_count: int, display: Display, image: int = IMAGE_ACCUM,
+                              out: Optional[np.ndarray] = None) -> np.ndarray:
+        """spt_resolve_display_rgba8: the ctx's image through the display transform as RGBA8 (into the registered
+        buffer directly when `out` is that buffer)."""
+        if out is None:
+            out = np.zeros(self.shard_pixels, dtype=np.uint32)
+        elif out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"] or out.size < self.shard_pixels:
+            raise SptError("resolve_display_rgba8: out must be a C-contiguous uint32 array of >= shard_pixels")
+        self._check(self.lib.spt_resolve_display_rgba8(self.h, image, frame_count, ctypes.byref(display), _ptr(out)),
+                    "spt_resolve_display_rgba8")
+        return out
+
+    def resolve_display_device_image(self, dev_ptr: int, n_pixels: int, display: Display, divisor: float = 1.0,
+                                     out: Optional[np.ndarray] = None) -> np.ndarray:
+        """spt_resolve_display_device_image: n_pixels float RGBA pixels at a device address of the caller's through
+        the display transform as RGBA8."""
+        if out is None:
+            out = np.zeros(n_pixels, dtype=np.uint32)
+        elif out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"] or out.size < n_pixels:
+            raise SptError("resolve_display_device_image: out must be a C-contiguous uint32 array of >= n_pixels")
+        self._check(self.lib.spt_resolve_display_device_image(self.h, ctypes.c_void_p(dev_ptr), n_pixels, divisor,
+                                                              ctypes.byref(display), _ptr(out)),
+                    "spt_resolve_display_device_image")
+        return out
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -1001,6 +1152,7 @@ class RenderSettings:
         self._progressive = True
         self._spp, self._max_bounces, self._rr_depth = 64, 8, 3
         self._exposure = 1.0
+        self._auto_exposure, self._target_luminance = False, 0.18
         self._dirty = True  # dirty on construction
 
     def _set(self, name, value):
@@ -1027,6 +1179,17 @@ class RenderSettings:
 
     def setExposure(self, v: float) -> None:
         self._set("_exposure", v)
+
+    def setAutoExposure(self, enabled: bool, target_luminance: float = 0.18) -> None:
+        if (self._auto_exposure, self._target_luminance) != (enabled, target_luminance):
+            self._auto_exposure, self._target_luminance = enabled, target_luminance
+            self._dirty = True
+
+    def getAutoExposure(self) -> bool:
+        return self._auto_exposure
+
+    def getTargetLuminance(self) -> float:
+        return self._target_luminance
 
     def getProgressive(self) -> bool:
         return self._progressive
@@ -1151,6 +1314,34 @@ class HIPPathTracer(PathTracer):
         self._models_dirty = False
         self._denoise: Optional[DenoiseParams] = None
         self._reproject: Optional[ReprojectParams] = None
+        self._tonemap = TONEMAP_CLAMP
+        self._exposure_params: Optional[ExposureParams] = None
+
+    def set_tonemap(self, tonemap: int) -> None:
+        """Not in the reference interface: the tone-mapping operator of get_render_result() (TONEMAP_CLAMP, the
+        default: the plain resolve; TONEMAP_REINHARD; TONEMAP_ACES). render() and the accumulation are the same."""
+        if tonemap not in (TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES):
+            raise SptError("set_tonemap: unknown operator")
+        self._tonemap = tonemap
+
+    def set_exposure_params(self, params: Optional[ExposureParams]) -> None:
+        """Not in the reference interface: the auto-exposure's parameters besides the target, which always comes
+        from the settings (setAutoExposure); None: the library's defaults."""
+        self._exposure_params = params
+
+    def _display_on(self) -> bool:
+        return self._tonemap != TONEMAP_CLAMP or (self._settings_mode and self._settings.getAutoExposure())
+
+    def _resolve_display(self, image: int, exposure: float) -> np.ndarray:
+        """Meter the image about to be shown (settings mode with auto-exposure), then resolve it with the operator."""
+        if self._settings_mode and self._settings.getAutoExposure():
+            p = ExposureParams()
+            if self._exposure_params is not None:
+                ctypes.memmove(ctypes.byref(p), ctypes.byref(self._exposure_params), ctypes.sizeof(p))
+            p.target_luminance = self._settings.getTargetLuminance()
+            auto = exposure_from_histogram(self._ctx.meter_luminance(self._frame_count, image), p)
+            exposure = float(np.float32(auto) * np.float32(exposure))  # (the setting is the compensation)
+        return self._ctx.resolve_display_rgba8(self._frame_count, Display(self._tonemap, exposure), image)
 
     def set_reproject(self, params: Optional[ReprojectParams]) -> None:
         """Not in the reference interface: temporal reprojection. While params is not None, a camera or lens change
@@ -1270,17 +1461,24 @@ class HIPPathTracer(PathTracer):
         if self._frame_count <= 0:
             raise SptError("No frames rendered yet")  # CPUPathTracer.cpp:89
         exposure = self._settings.getExposure() if self._settings_mode else 1.0
+        display = self._display_on()  # auto-exposure or an operator: the metered display resolve of the same image
         if self._reproject is not None:
             self._ctx.history_blend(self._frame_count)
             if self._denoise is not None:
                 self._ctx.denoise_blended(self._denoise)
-                self._result.image_buffer = self._ctx.resolve_denoised_rgba8(exposure)
+                self._result.image_buffer = (self._resolve_display(IMAGE_DENOISED, exposure) if display else
+                                             self._ctx.resolve_denoised_rgba8(exposure))
             else:
-                self._result.image_buffer = self._ctx.resolve_blended_rgba8(exposure)
+                self._result.image_buffer = (self._resolve_display(IMAGE_BLENDED, exposure) if display else
+                                             self._ctx.resolve_blended_rgba8(exposure))
             return self._result
         if self._denoise is not None:
             self._ctx.denoise(self._frame_count, self._denoise)
-            self._result.image_buffer = self._ctx.resolve_denoised_rgba8(exposure)
+            self._result.image_buffer = (self._resolve_display(IMAGE_DENOISED, exposure) if display else
+                                         self._ctx.resolve_denoised_rgba8(exposure))
+            return self._result
+        if display:
+            self._result.image_buffer = self._resolve_display(IMAGE_ACCUM, exposure)
             return self._result
         self._result.image_buffer = self._ctx.resolve_rgba8(self._frame_count, exposure)
         return self._result

@@ -72,7 +72,7 @@ namespace render
 		// (:61); settings mode: getSamplesPerPixel() such frames in one call (k_paths from 4)
 		const uint32_t n = m_settingsMode ? std::max<uint32_t>(1u, m_renderSettings->getSamplesPerPixel()) : 1u;
 		m_resolvedAt = 0;
-		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn && !m_reprojectOn)
+		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn && !m_reprojectOn && !display_on())
 		{
 			// the App reads the result after every render() (App.cpp:230-240): a one-frame call's resolve
 			// rides in the frame's own launch, its pixels stored into the registered result buffer as their
@@ -147,19 +147,63 @@ namespace render
 		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
 	}
 
+	void HIPPathTracer::set_tonemap(uint32_t tonemap)
+	{
+		SPT_VERIFY(tonemap <= SPT_TONEMAP_ACES, "unknown tone-mapping operator");
+		m_tonemap = tonemap;
+		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
+	}
+
+	void HIPPathTracer::set_exposure_params(const spt_exposure_params *params)
+	{
+		m_hasExposureParams = params != nullptr;
+		if (params)
+			m_exposureParams = *params;
+	}
+
+	bool HIPPathTracer::display_on() const
+	{
+		return m_tonemap != SPT_TONEMAP_CLAMP || (m_settingsMode && m_renderSettings->getAutoExposure());
+	}
+
+	void HIPPathTracer::resolve_display(uint32_t image, float exposure)
+	{
+		if (m_settingsMode && m_renderSettings->getAutoExposure())
+		{
+			// meter the image about to be shown; the setting's exposure is the compensation on top
+			uint32_t counts[SPT_METER_BINS];
+			SPT_CALL(m_ctx, spt_meter_luminance(m_ctx, image, m_frameCount, counts));
+			spt_exposure_params p;
+			SPT_CALL(m_ctx, spt_exposure_params_default(&p));
+			if (m_hasExposureParams)
+				p = m_exposureParams;
+			p.target_luminance = m_renderSettings->getTargetLuminance();
+			float metered = 1.0f;
+			SPT_VERIFY(spt_exposure_from_histogram(counts, &p, &metered) == SPT_OK, "invalid auto-exposure parameters");
+			exposure = metered * exposure;
+		}
+		spt_display d{};
+		d.tonemap = m_tonemap;
+		d.exposure = exposure;
+		SPT_CALL(m_ctx, spt_resolve_display_rgba8(m_ctx, image, m_frameCount, &d, m_render_result.image_buffer.data()));
+		m_resolvedAt = 0; // (the buffer no longer holds what render() resolved: auto-exposure is switched on the settings)
+	}
+
 	const PathTracer::RenderResult &HIPPathTracer::get_render_result()
 	{
 		SPT_VERIFY(m_frameCount > 0, "No frames rendered yet");
 		const float exposure = m_settingsMode ? m_renderSettings->getExposure() : 1.0f;
+		const bool display = display_on(); // auto-exposure or an operator: the metered display resolve of the same image
 		if (m_reprojectOn)
 		{
 			// the history (if the ctx holds one) blended with the frames so far: a mean, resolved with divisor 1
 			SPT_CALL(m_ctx, spt_history_blend(m_ctx, m_frameCount));
 			if (m_denoiseOn)
-			{
 				SPT_CALL(m_ctx, spt_denoise_blended(m_ctx, &m_denoise));
+			if (display)
+				resolve_display(m_denoiseOn ? SPT_IMAGE_DENOISED : SPT_IMAGE_BLENDED, exposure);
+			else if (m_denoiseOn)
 				SPT_CALL(m_ctx, spt_resolve_denoised_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
-			}
 			else
 				SPT_CALL(m_ctx, spt_resolve_blended_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
 			return m_render_result;
@@ -168,7 +212,15 @@ namespace render
 		{
 			// the filtered mean of the frames so far, resolved with divisor 1 (into the registered buffer)
 			SPT_CALL(m_ctx, spt_denoise(m_ctx, m_frameCount, &m_denoise));
-			SPT_CALL(m_ctx, spt_resolve_denoised_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
+			if (display)
+				resolve_display(SPT_IMAGE_DENOISED, exposure);
+			else
+				SPT_CALL(m_ctx, spt_resolve_denoised_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
+			return m_render_result;
+		}
+		if (display)
+		{
+			resolve_display(SPT_IMAGE_ACCUM, exposure);
 			return m_render_result;
 		}
 		if (m_resolvedAt == m_frameCount && m_resolvedExposure == exposure)

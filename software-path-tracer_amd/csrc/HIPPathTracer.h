@@ -83,8 +83,22 @@ namespace render
 		// is without this call (a one-frame render() fuses its resolve only while off).
 		void set_reproject(const spt_reproject_params *params);
 
+		// Not in the reference interface (its resolve clamps): the tone-mapping operator of get_render_result()
+		// (spt.h spt_tonemap); SPT_TONEMAP_CLAMP, the default, is the plain resolve. With another operator, or in
+		// settings mode with RenderSettings::getAutoExposure(), get_render_result() meters the image it is about
+		// to show (spt_meter_luminance), takes spt_exposure_from_histogram with getTargetLuminance() as the
+		// target, multiplies it by getExposure() (the compensation) and resolves with spt_resolve_display_rgba8;
+		// a one-frame render() then does not fuse the plain resolve into its launch. render() and the
+		// accumulation are the same either way.
+		void set_tonemap(uint32_t tonemap);
+		// The auto-exposure's parameters besides the target, which always comes from the settings (copied);
+		// nullptr: the library's defaults.
+		void set_exposure_params(const spt_exposure_params *params);
+
 	private:
 		void invalidate();
+		bool display_on() const;
+		void resolve_display(uint32_t image, float exposure);
 		void rebuild_scene();
 
 		spt_ctx *m_ctx = nullptr;
@@ -112,5 +126,8 @@ namespace render
 		bool m_denoiseOn = false;
 		spt_reproject_params m_reproject{};        // set_reproject's, while m_reprojectOn
 		bool m_reprojectOn = false;
+		uint32_t m_tonemap = SPT_TONEMAP_CLAMP;    // set_tonemap's
+		spt_exposure_params m_exposureParams{};    // set_exposure_params's, while m_hasExposureParams
+		bool m_hasExposureParams = false;
 	};
 } // namespace render

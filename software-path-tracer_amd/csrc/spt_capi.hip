@@ -21,6 +21,7 @@
 #include "spt_ctx_state.h"
 #include "spt_denoise.h"
 #include "spt_device.h"
+#include "spt_display.h"
 #include "spt_jit.h"
 #include "spt_kernels.h"
 #include "spt_launch_plan.h"
@@ -34,6 +35,8 @@ static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kM
 static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
 static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes");
 static_assert(sizeof(spt_reproject_params) == 32, "spt_reproject_params is 32 bytes");
+static_assert(sizeof(spt_exposure_params) == 32, "spt_exposure_params is 32 bytes");
+static_assert(sizeof(spt_display) == 16, "spt_display is 16 bytes");
 
 namespace {
 
@@ -207,6 +210,13 @@ struct spt_ctx {
     // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
     // model is not DIFFUSE (bsdf)
     uint32_t* d_reusable = nullptr;
+    // The luminance meter and the display transform: scratch only, nothing a change could make stale. The 256
+    // device words a metering sums into, the staging image of spt_resolve_display_device_image (grown on
+    // demand) and spt_set_meter_form's choice (-1: the form measured faster).
+    uint32_t* meter_counts = nullptr;
+    uint32_t* display_stage = nullptr;
+    uint64_t display_stage_pixels = 0;
+    int meter_form = -1;
 
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
@@ -805,6 +815,8 @@ void spt_destroy(spt_ctx* c) {
     free_dev(c->d_env);
     free_dev(c->d_camera);
     free_dev(c->work);
+    free_dev(c->meter_counts);
+    free_dev(c->display_stage);
     if (c->out_host) (void)hipHostUnregister(c->out_host);
     for (ViewHalf& h : c->half) {
         if (h.done) (void)hipEventDestroy(h.done);
@@ -1539,21 +1551,31 @@ int spt_resolve_rgba8(spt_ctx* c, uint32_t frame_count, uint32_t* host_out) {
     return spt_resolve_rgba8_exposure(c, frame_count, 1.0f, host_out);
 }
 
-// img / divisor as RGBA8 in host_out, waited for (the sums and a frame count, or a mean and 1)
-static int resolve_image(spt_ctx* c, const float4* img, float divisor, float exposure, uint32_t* host_out) {
+// The ctx's image as RGBA8 in host_out, waited for; launch(out, stream) enqueues the kernel that writes it.
+extern "C++" {  // (a template inside the C-ABI's linkage block)
+template <class Launch>
+static int resolve_image_by(spt_ctx* c, uint32_t* host_out, Launch&& launch) {
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pixels == 0) return SPT_OK;
     if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
         // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch_resolve(img, c->pixels, divisor, exposure, (uint32_t*)c->out_dev, on_stream(c));
+        launch((uint32_t*)c->out_dev, on_stream(c));
         SPT_HIP(c, hipGetLastError());
     } else {
-        launch_resolve(img, c->pixels, divisor, exposure, c->resolved, on_stream(c));
+        launch(c->resolved, on_stream(c));
         SPT_HIP(c, hipGetLastError());
         SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
     }
     SPT_HIP(c, wait_frame(c));
     return SPT_OK;
+}
+}  // extern "C++"
+
+// img / divisor as RGBA8 in host_out, waited for (the sums and a frame count, or a mean and 1)
+static int resolve_image(spt_ctx* c, const float4* img, float divisor, float exposure, uint32_t* host_out) {
+    return resolve_image_by(c, host_out, [&](uint32_t* out, hipStream_t s) {
+        launch_resolve(img, c->pixels, divisor, exposure, out, s);
+    });
 }
 
 int spt_resolve_rgba8_exposure(spt_ctx* c, uint32_t frame_count, float exposure, uint32_t* host_out) {
@@ -2096,6 +2118,186 @@ int spt_reproject_host(const spt_reproject_params* params, const spt_camera* pre
         out[4 * at + 2] = o.z;
         out[4 * at + 3] = o.w;
     }
+    return SPT_OK;
+}
+
+// ---- exposure and tone mapping: the luminance meter and the display resolve -------------------------
+
+namespace {
+const spt_exposure_params kExposureDefaults = {0.18f, 0.1f, 0.02f, 0.015625f, 64.0f, {0u, 0u, 0u}};
+bool exposure_params_ok(const spt_exposure_params& p) {
+    for (const float v : {p.target_luminance, p.low_fraction, p.high_fraction, p.min_exposure, p.max_exposure})
+        if (!std::isfinite(v)) return false;
+    if (!(p.target_luminance > 0.0f) || !(p.min_exposure > 0.0f) || !(p.max_exposure > 0.0f)) return false;
+    if (p.min_exposure > p.max_exposure) return false;
+    if (p.low_fraction < 0.0f || p.high_fraction < 0.0f) return false;
+    if ((double)p.low_fraction + (double)p.high_fraction >= 1.0) return false;
+    return !(p.reserved[0] | p.reserved[1] | p.reserved[2]);
+}
+// nullptr: valid
+const char* display_error(const spt_display& d) {
+    if (d.tonemap > SPT_TONEMAP_ACES) return "spt_display: unknown tonemap operator";
+    if (!std::isfinite(d.exposure) || d.exposure < 0.0f) return "spt_display: exposure must be finite and >= 0";
+    if (d.reserved[0] | d.reserved[1]) return "spt_display: reserved must be 0";
+    return nullptr;
+}
+bool divisor_ok(float divisor) { return std::isfinite(divisor) && divisor > 0.0f; }
+
+// The ctx image `image` with its divisor (the frame count for the sums, 1 for a mean), or nullptr with the
+// status to return in *rc.
+const float4* display_source(spt_ctx* c, uint32_t image, uint32_t frame_count, float* divisor, int* rc) {
+    *rc = SPT_ERR_INVALID;
+    if (image > SPT_IMAGE_BLENDED) {
+        fail(c, SPT_ERR_INVALID, "unknown image: SPT_IMAGE_ACCUM, SPT_IMAGE_DENOISED or SPT_IMAGE_BLENDED");
+        return nullptr;
+    }
+    if (!c->configured) {
+        *rc = fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
+        return nullptr;
+    }
+    *divisor = 1.0f;
+    if (image != SPT_IMAGE_ACCUM) return post_image(c, image == SPT_IMAGE_DENOISED ? kImgDenoised : kImgBlended);
+    if (frame_count == 0) {
+        fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+        return nullptr;
+    }
+    *divisor = (float)frame_count;
+    return c->accum;
+}
+
+// counts = the histogram of img[0..n) / divisor, waited for
+int meter_image(spt_ctx* c, const float4* img, uint64_t n, float divisor, uint32_t* counts) {
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (!c->meter_counts) SPT_HIP(c, hipMalloc(&c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS));
+    SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_METER_BINS, on_stream(c)));
+    launch_meter(c->meter_form >= 0 ? c->meter_form : meter_default_form(), img, n, divisor, c->meter_counts, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    SPT_HIP(c, hipMemcpyAsync(counts, c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+
+float4 pixel_of(const float* a, uint64_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); }
+}  // namespace
+
+int spt_exposure_params_default(spt_exposure_params* out) {
+    if (!out) return SPT_ERR_INVALID;
+    *out = kExposureDefaults;
+    return SPT_OK;
+}
+
+int spt_meter_luminance(spt_ctx* c, uint32_t image, uint32_t frame_count, uint32_t counts[SPT_METER_BINS]) {
+    if (!c || !counts) return SPT_ERR_INVALID;
+    float divisor = 1.0f;
+    int rc = SPT_OK;
+    const float4* img = display_source(c, image, frame_count, &divisor, &rc);
+    if (!img) return rc;
+    return meter_image(c, img, c->pixels, divisor, counts);
+}
+
+int spt_meter_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixels, float divisor,
+                           uint32_t counts[SPT_METER_BINS]) {
+    if (!c || !device_rgba || !counts) return SPT_ERR_INVALID;
+    if (n_pixels == 0) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: no pixels");
+    if (!divisor_ok(divisor)) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: divisor must be finite and > 0");
+    return meter_image(c, (const float4*)device_rgba, n_pixels, divisor, counts);
+}
+
+int spt_resolve_display_rgba8(spt_ctx* c, uint32_t image, uint32_t frame_count, const spt_display* display,
+                              uint32_t* host_out) {
+    if (!c || !display || !host_out) return SPT_ERR_INVALID;
+    const spt_display d = *display;
+    if (const char* msg = display_error(d)) return fail(c, SPT_ERR_INVALID, msg);
+    float divisor = 1.0f;
+    int rc = SPT_OK;
+    const float4* img = display_source(c, image, frame_count, &divisor, &rc);
+    if (!img) return rc;
+    return resolve_image_by(c, host_out, [&](uint32_t* out, hipStream_t s) {
+        launch_display(img, c->pixels, divisor, d, out, s);
+    });
+}
+
+int spt_resolve_display_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixels, float divisor,
+                                     const spt_display* display, uint32_t* host_out) {
+    if (!c || !device_rgba || !display || !host_out) return SPT_ERR_INVALID;
+    if (n_pixels == 0) return fail(c, SPT_ERR_INVALID, "spt_resolve_display_device_image: no pixels");
+    if (!divisor_ok(divisor))
+        return fail(c, SPT_ERR_INVALID, "spt_resolve_display_device_image: divisor must be finite and > 0");
+    const spt_display d = *display;
+    if (const char* msg = display_error(d)) return fail(c, SPT_ERR_INVALID, msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->display_stage_pixels < n_pixels) {
+        SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (no earlier resolve may still read the old one)
+        free_dev(c->display_stage);
+        c->display_stage_pixels = 0;
+        if (hipMalloc(&c->display_stage, sizeof(uint32_t) * n_pixels) != hipSuccess) {
+            c->display_stage = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SPT_ERR_HIP, "spt_resolve_display_device_image: allocation failed");
+        }
+        c->display_stage_pixels = n_pixels;
+    }
+    launch_display((const float4*)device_rgba, n_pixels, divisor, d, c->display_stage, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    SPT_HIP(c, hipMemcpyAsync(host_out, c->display_stage, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+
+int spt_set_meter_form(spt_ctx* c, int form) {
+    if (!c) return SPT_ERR_INVALID;
+    if (form != -1 && form != kMeterLanes && form != kMeterPeel)
+        return fail(c, SPT_ERR_INVALID, "spt_set_meter_form: -1 (automatic), 0 (an add per lane) or 1 (an add per distinct bin)");
+    c->meter_form = form;
+    return SPT_OK;
+}
+
+int spt_meter_bin(float luminance, uint32_t* bin) {
+    if (!bin) return SPT_ERR_INVALID;
+    *bin = meter_bin(luminance);
+    return SPT_OK;
+}
+
+int spt_luminance_histogram_host(const float* rgba, uint64_t n_pixels, float divisor, uint32_t counts[SPT_METER_BINS]) {
+    if (!rgba || !counts || n_pixels == 0 || !divisor_ok(divisor)) return SPT_ERR_INVALID;
+    std::memset(counts, 0, sizeof(uint32_t) * SPT_METER_BINS);
+    for (uint64_t i = 0; i < n_pixels; ++i) counts[meter_bin(pixel_luminance(pixel_of(rgba, i), divisor))] += 1u;
+    return SPT_OK;
+}
+
+int spt_exposure_from_histogram(const uint32_t counts[SPT_METER_BINS], const spt_exposure_params* params, float* exposure) {
+    if (!counts || !exposure) return SPT_ERR_INVALID;
+    const spt_exposure_params p = params ? *params : kExposureDefaults;
+    if (!exposure_params_ok(p)) return SPT_ERR_INVALID;
+    uint64_t total = 0;
+    for (int b = 1; b < SPT_METER_BINS; ++b) total += counts[b];
+    if (total == 0) {
+        *exposure = 1.0f;
+        return SPT_OK;
+    }
+    const double n = (double)total;
+    const double lo = (double)p.low_fraction * n, hi = (1.0 - (double)p.high_fraction) * n;
+    double c0 = 0.0, sw = 0.0, sl = 0.0;
+    for (int b = 1; b < SPT_METER_BINS; ++b) {
+        const double c1 = c0 + (double)counts[b];
+        const double w = std::max(0.0, std::min(c1, hi) - std::max(c0, lo));
+        const int key = kMeterKeyBase + b, e = (key >> 3) - 127, k = key & 7;
+        const double centre = (double)e + std::log2(1.0 + ((double)k + 0.5) / 8.0);
+        sw += w;
+        sl += w * centre;
+        c0 = c1;
+    }
+    double x = (double)p.target_luminance / std::exp2(sl / sw);
+    x = std::min(std::max(x, (double)p.min_exposure), (double)p.max_exposure);
+    *exposure = (float)x;
+    return SPT_OK;
+}
+
+int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const spt_display* display, uint32_t* out) {
+    if (!rgba || !display || !out || n_pixels == 0 || !divisor_ok(divisor)) return SPT_ERR_INVALID;
+    const spt_display d = *display;
+    if (display_error(d)) return SPT_ERR_INVALID;
+    for (uint64_t i = 0; i < n_pixels; ++i) out[i] = display_rgba8(pixel_of(rgba, i), divisor, d);
     return SPT_OK;
 }
 
