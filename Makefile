@@ -3,7 +3,7 @@
 #   make            libspt_hip.so (C-ABI + gfx950 kernels) and libspt_render.so (C++ render::PathTracer backend)
 #   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so), its restatement with
 #                   material models (tests/cpp/libref_materials.so), the lens's device check (tests/cpp/test_device_lens)
-#                   and the sphere pass's (tests/cpp/test_sphere_cull)
+#                   the sphere pass's (tests/cpp/test_sphere_cull) and the guard-free forms' (tests/cpp/test_device_ranges)
 #   make cpp-tests  the C++ interface test driver (tests/cpp)
 #
 # Every float operation on the hot path is compiled with -ffp-contract=off, on the device and on the
@@ -62,7 +62,8 @@ $(RLIB): $(RENDER_SRCS) $(LIB) $(wildcard include/render/*.h) $(CSRC)/HIPPathTra
 REFMAT := tests/cpp/libref_materials.so
 DEVLENS := tests/cpp/test_device_lens
 SPHCULL := tests/cpp/test_sphere_cull
-oracle: $(REFMAT) $(DEVLENS) $(SPHCULL)
+DEVRANGES := tests/cpp/test_device_ranges
+oracle: $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES)
 
 oracle/build/libcpu_ref.so: oracle/cpu_ref.c oracle/cpu_ref.h include/spt.h oracle/Makefile
 	$(MAKE) -C oracle
@@ -85,11 +86,17 @@ $(DEVLENS): tests/cpp/test_device_lens.hip $(CSRC)/spt_device.h
 $(SPHCULL): tests/cpp/test_sphere_cull.hip $(CSRC)/spt_device.h
 	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
 
+# GPU program (run by tests/test_gpu_flat_ranges.py): spt_device.h's guard-free forms (inv_sqrt_ranged,
+# rr_divide_ranged, bounce_tangent_ranged, the path start's emission) against '/', sqrtf and the guarded forms over
+# the ranges scene.cpp flat_ranges_ok admits; test infrastructure
+$(DEVRANGES): tests/cpp/test_device_ranges.hip $(CSRC)/spt_device.h
+	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
+
 cpp-tests: $(RLIB) oracle
 	$(MAKE) -C tests/cpp
 
 clean:
 	rm -rf $(OBJ) $(LIB) $(RLIB)
 	$(MAKE) -C oracle clean
-	rm -f $(REFMAT) $(DEVLENS) $(SPHCULL)
+	rm -f $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES)
 	-$(MAKE) -C tests/cpp clean

@@ -731,6 +731,12 @@ int spt_stats_clear(spt_ctx* ctx);
  * list (spt_tuning.wide_chunks; same results), else 0. A query of its own beside spt_stats.view_cached and
  * view_split: spt_stats keeps its size. */
 int spt_get_view_wide(spt_ctx* ctx, uint64_t* view_wide);
+/* *flat_ranges = 1 when the last k_paths launch ran a kernel compiled with the scene's range bit in force: a flat
+ * scene whose albedos are 0 or in [2^-5, 1] with one channel nonzero throughout, whose emission is >= +0, whose
+ * spheres and stored normals are well scaled (DESIGN.md 3.1d states the predicate), traced with at most 9
+ * bounces; the step loop then runs its divisions and inverse roots without their per-lane range tests (same
+ * results). 0 for every other kernel. A query of its own, like spt_get_view_wide: spt_stats keeps its size. */
+int spt_get_flat_ranges(spt_ctx* ctx, uint64_t* flat_ranges);
 
 /* ---- multi-GPU: row shards gathered over RCCL ------------------------------
  * One process and one ctx per GPU; ctx r is configured with shard_rank = r, shard_count = N. The

@@ -1,7 +1,10 @@
 """Static instruction profile of one k_paths instantiation between the SPT_MARK comments of a
 -DSPT_STATIC_PROFILE build (analysis only: the markers constrain scheduling a little).
 
-    python scripts/static_profile.py [--no-pairs] [extra hipcc -D flags ...]
+    python scripts/static_profile.py [--no-pairs] [--wide] [--ranges] [extra hipcc -D flags ...]
+
+--wide: the C2 kernel's wide form (64-pixel chunks over a view's lists, the benchmark's) instead of the plain one.
+--ranges: with the scene's range bit in the key (spt_kernels.h kShapeRanges): the step loop's guard-free forms.
 
 Compiles the C2 shape-specialized flat kernel and the two BVH k_paths instantiations to assembly and
 prints, per section of the step loop, the VALU / SALU / LDS / scalar-memory / vector-memory
@@ -24,14 +27,20 @@ if "--no-pairs" in sys.argv:  # the same kernel with every wall tested (the key 
     sys.argv.remove("--no-pairs")
 else:
     C2_SHAPE |= (1 | 1 << 2) << 57  # one opposite pair on x, one on y (flat_wall_pairs)
+WIDE = "--wide" in sys.argv
+if WIDE:
+    sys.argv.remove("--wide")
+if "--ranges" in sys.argv:
+    sys.argv.remove("--ranges")
+    C2_SHAPE |= 1 << 63
 INST = r"""#include "spt_kernels.hip"
 namespace spt {
-#define I(S, B, SH, W) template __global__ void k_paths<S, B, 0, SH, W>(const float4* __restrict__, const float4* __restrict__, \
+#define I(S, B, SH, W, WIDE) template __global__ void k_paths<S, B, 0, SH, W, false, 0, false, false, WIDE>(const float4* __restrict__, const float4* __restrict__, \
     const float4* __restrict__, uint32_t, float4* __restrict__, unsigned long long* __restrict__, uint32_t* __restrict__, \
     uint32_t* __restrict__, ShadeParams, CameraParams, uint32_t, ChunkPlan, NeeParams, ViewPlan);
-I(false, false, %dull, 0)
+I(false, false, %dull, 0, %s)
 }
-""" % C2_SHAPE
+""" % (C2_SHAPE, "true" if WIDE else "false")
 
 
 def classify(op):
@@ -62,7 +71,7 @@ def main():
                "-DSPT_STATIC_PROFILE", *flags, "-o", asm, src]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         lines = open(asm).read().split("\n")
-    for kname in ("_ZN3spt7k_pathsILb0ELb0ELi0ELm%dELi0E" % C2_SHAPE, "_ZN3spt7k_pathsILb0ELb1ELi0ELm0ELi8E",
+    for kname in ("_ZN3spt7k_pathsILb0ELb0ELi0ELm%dELi0ELb0ELi0ELb0ELb0ELb%dE" % (C2_SHAPE, WIDE), "_ZN3spt7k_pathsILb0ELb1ELi0ELm0ELi8E",
                   "_ZN3spt7k_pathsILb0ELb1ELi0ELm0ELi0E"):
         on, sec = False, "prologue"
         cnt = collections.defaultdict(collections.Counter)

@@ -165,6 +165,8 @@ class SptStats(ctypes.Structure):
     # spt_get_view_wide's answer, set by Context.stats(): 1 when the last k_paths launch ran the wide form
     # (a query of its own: spt_stats keeps its size)
     view_wide = 0
+    # spt_get_flat_ranges' answer, likewise: 1 when the last k_paths launch ran with the scene's range bit in force
+    flat_ranges = 0
 
     def as_dict(self) -> dict:
         d = {}
@@ -172,6 +174,7 @@ class SptStats(ctypes.Structure):
             v = getattr(self, k)
             d[k] = list(v) if isinstance(v, ctypes.Array) else v
         d["view_wide"] = self.view_wide
+        d["flat_ranges"] = self.flat_ranges
         return d
 
 
@@ -181,7 +184,7 @@ EXPORTED_SYMBOLS = (
     "spt_set_scene", "spt_configure", "spt_reset", "spt_get_frame_count", "spt_render", "spt_synchronize",
     "spt_shard_pixels", "spt_read_accum", "spt_accum_device_ptr", "spt_copy_accum_device", "spt_resolve_rgba8",
     "spt_resolve_rgba8_exposure", "spt_register_host_output", "spt_render_resolve_rgba8", "spt_assemble_rows",
-    "spt_set_profiling", "spt_get_stats", "spt_get_view_wide", "spt_stats_clear", "spt_build_scene",
+    "spt_set_profiling", "spt_get_stats", "spt_get_view_wide", "spt_get_flat_ranges", "spt_stats_clear", "spt_build_scene",
     "spt_set_env_map", "spt_env_octa_from_equirect",
     "spt_comm_available", "spt_comm_unique_id", "spt_comm_init", "spt_gather_image", "spt_gather_image_overlapped", "spt_gather_wait",
     "spt_comm_destroy", "spt_set_tuning",
@@ -357,6 +360,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_env_octa_from_equirect": ([P, U32, U32, P, U32, U32], I),
         "spt_get_stats": ([P, ctypes.POINTER(SptStats)], I),
         "spt_get_view_wide": ([P, ctypes.POINTER(ctypes.c_uint64)], I),
+        "spt_get_flat_ranges": ([P, ctypes.POINTER(ctypes.c_uint64)], I),
         "spt_stats_clear": ([P], I),
         "spt_build_scene": ([U32, P, ctypes.POINTER(U32), P, ctypes.POINTER(U32), ctypes.POINTER(SptEnv)], I),
         "spt_comm_available": ([], I),
@@ -1105,6 +1109,10 @@ class Context:
         wide = ctypes.c_uint64(0)
         self._check(self.lib.spt_get_view_wide(self.h, ctypes.byref(wide)), "spt_get_view_wide")
         s.view_wide = int(wide.value)
+        ranges = ctypes.c_uint64(0)
+        if not os.environ.get("SPT_LIB_PATH") or hasattr(self.lib, "spt_get_flat_ranges"):  # (an older A/B library: 0)
+            self._check(self.lib.spt_get_flat_ranges(self.h, ctypes.byref(ranges)), "spt_get_flat_ranges")
+        s.flat_ranges = int(ranges.value)
         return s
 
     def clear_stats(self) -> None:

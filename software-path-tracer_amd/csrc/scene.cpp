@@ -145,6 +145,58 @@ bool fast_division_ok(const spt_prim* prims, uint32_t n, const std::vector<DevPr
     return true;
 }
 
+bool flat_ranges_ok(const spt_prim* prims, uint32_t n, const spt_material* mats, uint32_t n_mats,
+                    const std::vector<DevPrim>& dp) {
+    if (dp.size() < n || !fast_division_ok(prims, n, dp)) return false;
+    auto in_window = [](float x) { return x >= 0x1p-90f && x <= 0x1p90f; };  // (NaN: false)
+    bool channel[3] = {true, true, true};  // nonzero in every material
+    for (uint32_t i = 0; i < n_mats; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            const float a = mats[i].albedo[k], e = mats[i].emission[k];
+            if (!(a == 0.0f || (a >= 0x1p-5f && a <= 1.0f))) return false;
+            if (a == 0.0f) channel[k] = false;
+            if (!(e >= 0.0f) || (f2u(e) >> 31) != 0u) return false;
+        }
+    }
+    if (!(channel[0] || channel[1] || channel[2])) return false;
+    double extent = 0.0;  // E: fast_division_ok's bound of every coordinate of the scene
+    for (uint32_t i = 0; i < n; ++i) {
+        const spt_prim& p = prims[i];
+        for (int k = 0; k < 3; ++k) {
+            if (p.type == SPT_PRIM_SPHERE)
+                extent = std::max(extent, std::fabs((double)p.p0[k]) + (double)p.p0[3]);
+            else if (p.type == SPT_PRIM_QUAD)
+                extent = std::max(extent, std::fabs((double)p.p0[k]) + std::fabs((double)p.p1[k]) + std::fabs((double)p.p2[k]));
+            else
+                extent = std::max(extent, std::max(std::fabs((double)p.p0[k]),
+                                                   std::max(std::fabs((double)p.p1[k]), std::fabs((double)p.p2[k]))));
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const spt_prim& p = prims[i];
+        if (p.type == SPT_PRIM_SPHERE) {
+            if (!in_window(dp[i].b[0]) || !((double)p.p0[3] * 32.0 >= extent)) return false;
+            continue;
+        }
+        // the stored normal as the shading record holds it (spt_kernels.hip make_shade_recs), its squared
+        // length, the unit normal and its tangents' squared lengths with the device's expressions; the
+        // two-sided flip negates every component, which changes no square and neither pole test
+        const float* g = p.type == SPT_PRIM_QUAD ? dp[i].b : dp[i].d;
+        const float x = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+        if (!in_window(x)) return false;
+        const float inv = 1.0f / std::sqrt(x);
+        const float nv[3] = {g[0] * inv, g[1] * inv, g[2] * inv};
+        const float up_z[3] = {0.0f, 0.0f, 1.0f}, up_x[3] = {1.0f, 0.0f, 0.0f};
+        for (int form = 0; form < 2; ++form) {  // bounce_tangent: SPT_FLAG_ABS_FLOAT, then the reference's abs(int)
+            const bool not_pole = form == 0 ? (std::fabs(nv[2]) < 0.999f) : ((int)nv[2] == 0);
+            float t[3];
+            cross3(not_pole ? up_z : up_x, nv, t);
+            if (!in_window(dot3(t, t))) return false;
+        }
+    }
+    return true;
+}
+
 uint32_t flat_kind(const DevPrim& p) {
     const uint32_t type = f2u(p.d[3]) & ((1u << kMetaTypeBits) - 1u);
     if (type == SPT_PRIM_SPHERE) return 0;

@@ -70,6 +70,20 @@ void prepare_materials(const spt_material* mats, uint32_t n, std::vector<DevMate
 // `dp` are the prims prepared from them.
 bool fast_division_ok(const spt_prim* prims, uint32_t n, const std::vector<DevPrim>& dp);
 
+// Whether the specialized flat k_paths may drop the per-lane range tests of its step loop's divisions and
+// inverse roots (spt_kernels.h kShapeRanges; spt_device.h rr_divide_ranged, inv_sqrt_ranged and the path start's
+// emission state the proofs that lean on each term). `mats` are the materials the primitives use. True when
+//   - the scene passes fast_division_ok (every coordinate bound m of it is < 2^28; E: the largest m);
+//   - every albedo component is 0 or in [2^-5, 1], and some channel is nonzero in every material (so a
+//     throughput never becomes 0 in all three channels);
+//   - every emission component is >= +0 with the sign bit clear;
+//   - every sphere's r * r (the device's product) lies in [2^-90, 2^90] and r >= E / 32 (a hit point's computed
+//     distance from the centre then stays above r / 4);
+//   - every stored normal of a quad or triangle has a squared length (the device's sum) in [2^-90, 2^90], and
+//     the tangent bounce_tangent builds on its unit normal, with and without SPT_FLAG_ABS_FLOAT, has one too.
+bool flat_ranges_ok(const spt_prim* prims, uint32_t n, const spt_material* mats, uint32_t n_mats,
+                    const std::vector<DevPrim>& dp);
+
 // The flat fast path's kind-major copy (spt_kernels.hip closest_flat): the prepared primitives
 // stably grouped as spheres | quads with normal +-x | +-y | +-z | other quads | triangles, so the
 // device tests each group in a loop of its own with no per-primitive type dispatch. ends[g] is the

@@ -133,6 +133,7 @@ struct spt_ctx {
     uint32_t flat_rect = 0;  // flat_rect_bits of the kind-major copy (part of the shape key)
     uint32_t flat_pairs = 0; // flat_wall_pairs of the kind-major copy (part of the shape key)
     bool fast_div = false;  // scene.cpp fast_division_ok: the flat loop's unscaled divisions apply
+    bool flat_ranges = false;  // scene.cpp flat_ranges_ok: the shape key's range bit (spt_kernels.h kShapeRanges)
     uint64_t scene_bytes = 0;
     uint64_t stack_bytes = 0;  // the persistent kernels' global traversal stacks (BVH scenes)
 
@@ -282,6 +283,7 @@ struct spt_ctx {
     uint32_t* ray_cursor = nullptr;
     bool last_specialized = false; // the last persistent / frame launch ran the specialized kernel
     uint32_t last_pairs = 0;       // ... whose key held this many wall pairs (flat_shape_pairs)
+    bool last_ranges = false;      // ... a k_paths whose step loop ran its guard-free forms (flat_ranges_baked)
 
     // multi-GPU (spt_comm_init / spt_gather_image)
     ncclComm_t comm = nullptr;
@@ -578,7 +580,7 @@ void next_work_set(spt_ctx* c, PassParams& p) {
 // The run-time specialized kernels' key of the ctx's flat scene: its shape and, once configured, the
 // launch configuration (spt_kernels.h jit_config_key).
 static uint64_t flat_jit_key(const spt_ctx* c) {
-    const uint64_t shape = flat_shape_key(c->flat_ends, c->n_prims, c->flat_rect, c->flat_pairs);
+    const uint64_t shape = flat_shape_key(c->flat_ends, c->n_prims, c->flat_rect, c->flat_pairs, c->flat_ranges);
     if (!c->configured) return shape;
     const uint32_t flags = (c->cfg.flags & ~spt::kFlagFastDiv) | (c->fast_div ? spt::kFlagFastDiv : 0u);
     return jit_config_key(shape, c->cfg.max_bounces, c->cfg.rr_depth, c->env.sky_enabled ? 1u : 0u, flags, c->has_camera);
@@ -873,6 +875,8 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     const char* msg = nullptr;
     if (!prepare_prims(prims, n_prims, n_mats, dp, &msg)) return fail(c, SPT_ERR_INVALID, msg);
     const bool fast_div = fast_division_ok(prims, n_prims, dp);  // before build_bvh reorders dp
+    // (a flat scene's: of the materials its primitives use, so an edit that brings another one in re-derives it)
+    const bool flat_ranges = n_prims && n_prims <= kFlatSceneMax && flat_ranges_ok(prims, n_prims, mats, n_mats, dp);
     std::vector<DevMaterial> dm;
     prepare_materials(mats, n_mats, dm);
     std::vector<DevEmitter> emit;  // SPT_FLAG_NEE's emitters (built for every scene: the flag may come later)
@@ -942,6 +946,7 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     c->env = *env;
     c->has_scene = true;
     c->fast_div = fast_div;
+    c->flat_ranges = flat_ranges;
     c->flat_ends = flat_ends;
     c->flat_rect = flat_rect;
     c->flat_pairs = flat_pairs;
@@ -1290,6 +1295,7 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
         if (timed && hipEventRecord(ev[n_ev - 1].b, vh.stream) != hipSuccess) rc = fail(c, SPT_ERR_HIP, "k_paths (split): hipEventRecord");
     }
     c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
+    c->last_ranges = c->last_specialized && flat_ranges_baked(p.jit_shape);
     if (rc != SPT_OK) {
         for (int i = 0; i < n_ev; ++i) c->free_events.push_back(ev[i]);
         c->derived.half_order_key[0] = c->derived.half_order_key[1] = 0;
@@ -1361,6 +1367,7 @@ static int render_persistent(spt_ctx* c, PassParams& p, uint32_t first_frame, ui
         p.chunk_order_key = &c->derived.chunk_order_key;
         c->last_specialized = launch_paths(p, c->counters, on_stream(c), view_on ? &view : nullptr, 0u, wide, &c->last_view_wide);
         c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
+        c->last_ranges = c->last_specialized && flat_ranges_baked(p.jit_shape);
         c->last_view_cached = view_on;
         // a failed launch leaves no chunk order behind (a retry must not read an unsorted buffer)
         const hipError_t le = hipGetLastError();
@@ -1431,6 +1438,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
             }
             c->last_specialized = launch_frame(p, c->counters, on_stream(c));
             c->last_pairs = c->last_specialized ? flat_shape_pairs(p.jit_shape) : 0u;
+            c->last_ranges = false;  // (k_frame has no such forms)
             if (end_persistent(c, ev) != SPT_OK) return SPT_ERR_HIP;
             SPT_HIP(c, hipGetLastError());
             bool lists = c->derived.frame_lists();
@@ -1454,6 +1462,7 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
     }
     c->last_schedule = schedule_fused(c) ? SPT_SCHEDULE_FUSED : SPT_SCHEDULE_SPLIT;
     c->last_specialized = false;
+    c->last_ranges = false;
     while (done < n_frames) {
         const uint32_t f = std::min(c->frames_per_pass, n_frames - done);
         p.first_frame = first_frame + done;
@@ -2501,6 +2510,12 @@ int spt_get_stats(spt_ctx* c, spt_stats* out) {
 int spt_get_view_wide(spt_ctx* c, uint64_t* view_wide) {
     if (!c || !view_wide) return SPT_ERR_INVALID;
     *view_wide = c->last_view_wide ? 1u : 0u;
+    return SPT_OK;
+}
+
+int spt_get_flat_ranges(spt_ctx* c, uint64_t* flat_ranges) {
+    if (!c || !flat_ranges) return SPT_ERR_INVALID;
+    *flat_ranges = c->last_ranges ? 1u : 0u;
     return SPT_OK;
 }
 

@@ -78,6 +78,24 @@ __host__ __device__ __forceinline__ F3 normalize3(F3 v) {
     const float inv = inv_sqrt_ref(dot3(v, v));
     return F3{v.x * inv, v.y * inv, v.z * inv};
 }
+// inv_sqrt_ref for an x the CALLER knows to lie in [2^-96, 2^96): the same sequence without the window test
+// (the compare and its exec-mask branch). Only for the k_paths step loop of a scene that passed flat_ranges_ok
+// (scene.h; spt_kernels.h flat_ranges_baked); each call site states why its x is inside. Same bits there:
+// tests/cpp/test_device_ranges.hip compares it with 1.0f / sqrtf(x) over the whole window.
+__host__ __device__ __forceinline__ float inv_sqrt_ranged(float x) {
+#if !defined(__HIP_DEVICE_COMPILE__) || defined(SPT_EXPERIMENT_FAST_NORM)
+    return inv_sqrt_ref(x);
+#else
+    const float s = sqrt_unit(x);
+    const float y0 = __builtin_amdgcn_rcpf(s);
+    const float e = __builtin_fmaf(-s, y0, 1.0f);
+    const float y1 = __builtin_fmaf(e, y0, y0);
+    const float r0 = __builtin_fmaf(-s, y1, 1.0f);
+    const float q1 = __builtin_fmaf(r0, y1, y1);
+    const float r1 = __builtin_fmaf(-s, q1, 1.0f);
+    return __builtin_fmaf(r1, y1, q1);
+#endif
+}
 
 // get_rng_state, CPUPathTracer.cpp:192-195 (frame = m_frameCount + 1 at the call site :61).
 __device__ __forceinline__ uint32_t rng_seed(uint32_t x, uint32_t y, uint32_t width, uint32_t frame1) {
@@ -293,6 +311,24 @@ __host__ __device__ __forceinline__ F3 bounce_tangent(F3 n, uint32_t flags) {
     const F3 up = not_pole ? F3{0.0f, 0.0f, 1.0f} : F3{1.0f, 0.0f, 0.0f};
     return normalize3(cross3(up, n));
 }
+// bounce_tangent without the window test of its inverse root (inv_sqrt_ranged), for the shading normal n of a
+// hit in k_paths' step loop under spt_kernels.h flat_tangent_baked. x = |up x n|^2 is in [2^-96, 2^96):
+//   - n = ng * inv_len with ng's squared length in the window (the call site's argument), so each component
+//     carries at most 3 roundings and |n|^2 = 1 +- 2^-21; no component exceeds 1 + 2^-22, so x < 4.
+//   - SPT_FLAG_ABS_FLOAT: off the pole (|n.z| < 0.999f) up = z and up x n = (-n.y, n.x, 0), so
+//     x = n.x^2 + n.y^2 >= (1 - 2^-21) - 0.999^2 - 2^-21 > 2^-10; at the pole up = x and up x n = (0, -n.z, n.y),
+//     so x >= n.z^2 (1 - 2^-23) > 0.99.
+//   - without the flag the pole test is (int)n.z == 0, which a unit normal with n.z = 1 - 2^-24 and
+//     n.x = n.y = 0 passes with x = 0: no bound holds for a normal computed on the device (a sphere's). The
+//     form is then used only for a shape without spheres, whose normals are the stored ones: flat_ranges_ok
+//     (scene.cpp) has evaluated this very x for each of them, in both forms, and found it inside.
+__device__ __forceinline__ F3 bounce_tangent_ranged(F3 n, uint32_t flags) {
+    const bool not_pole = (flags & kFlagAbsFloat) ? (fabsf(n.z) < 0.999f) : ((int)n.z == 0);
+    const F3 up = not_pole ? F3{0.0f, 0.0f, 1.0f} : F3{1.0f, 0.0f, 0.0f};
+    const F3 c = cross3(up, n);
+    const float inv = inv_sqrt_ranged(dot3(c, c));
+    return F3{c.x * inv, c.y * inv, c.z * inv};
+}
 
 // sin and cos of phi in [0, 2*pi] in fp64 (the reference calls the C double cos/sin here, see
 // bounce_dir_frame). Cody-Waite reduction by pi/2 (k <= 4: k * kPio2Hi and phi - k * kPio2Hi are
@@ -462,6 +498,23 @@ __device__ __forceinline__ F3 rr_divide(F3 T, float p) {
         return F3{div_ref(T.x, r), div_ref(T.y, r), div_ref(T.z, r)};
     }
     return F3{T.x / p, T.y / p, T.z / p};
+}
+
+// rr_divide without its range predicates (8 compares and their mask arithmetic), for k_paths' step loop under
+// spt_kernels.h flat_ranges_baked: a scene that passed flat_ranges_ok (scene.cpp) traced with max_bounces <= 9.
+// Every operand is then in div_ref's range:
+//   - T starts as 1 * albedo and is multiplied by one albedo per hit; roulette runs at bounce_count <
+//     max_bounces, so T is a product of at most 8 albedos, with divisions by earlier p in between.
+//   - An albedo component is 0 or in [2^-5, 1]. Rounding is monotone and powers of two are floats, so a product
+//     of two components in [2^-a, 1] and [2^-b, 1] rounds into [2^-(a+b), 1]; a division by p in (0, 1] of a
+//     component <= p rounds into [component, 1]. By induction each T component is 0 or in [2^-40, 1].
+//   - Some channel is nonzero in every material, so that component of T is never 0 and p = max(T) is in
+//     [2^-40, 1] (never the p == 0 whose 0 / 0 only the general division reproduces).
+// So p is in [2^-40, 2^20] and each numerator is 0 or in [2^-100, 2^50]: rr_divide takes its first branch for
+// every lane, and this is that branch. tests/cpp/test_device_ranges.hip compares it with '/' and rr_divide.
+__device__ __forceinline__ F3 rr_divide_ranged(F3 T, float p) {
+    const RcpRef r = rcp_ref(p);
+    return F3{div_ref(T.x, r), div_ref(T.y, r), div_ref(T.z, r)};
 }
 
 // isect_sphere for |d| ~ 1 (a = d . d in [0.5, 2], two_a's reciprocal refined once per ray in

@@ -168,10 +168,13 @@ constexpr uint64_t kShapeValid = 1ull << 36;
 // whose quads then take the short form without the per-quad scalar check
 // ... and 6 bits (57-62): per axis, 2 bits, the opposite wall pairs at the head of its group (scene.h
 // flat_wall_pairs; 0-3, only in a group whose rect bit is set): the unrolled fast path tests one wall of each
+// ... and 1 bit (63): the scene passed flat_ranges_ok (scene.h): the value ranges under which k_paths' step loop
+// runs its divisions and inverse roots without their per-lane range tests (flat_ranges_baked below)
+constexpr uint64_t kShapeRanges = 1ull << 63;
 __host__ __device__ constexpr uint64_t flat_shape_key(uint32_t flat_ends, uint32_t n_prims, uint32_t rect_bits = 0u,
-                                                      uint32_t pair_bits = 0u) {
+                                                      uint32_t pair_bits = 0u, bool ranges = false) {
     return kShapeValid | (uint64_t)(n_prims & 63u) << 30 | (flat_ends & 0x3fffffffu) | (uint64_t)(rect_bits & 7u) << 53 |
-           (uint64_t)(pair_bits & 63u) << 57;
+           (uint64_t)(pair_bits & 63u) << 57 | (ranges ? kShapeRanges : 0ull);
 }
 // the wall pairs of axis ax (0..2) in a shape key, and of all three
 __host__ __device__ constexpr uint32_t flat_shape_pairs(uint64_t key, uint32_t ax) {
@@ -204,6 +207,20 @@ __host__ __device__ constexpr uint64_t jit_config_key(uint64_t shape, uint32_t m
     return shape | kConfigValid | (uint64_t)max_bounces << 38 | (uint64_t)rr_depth << 44 |
            (uint64_t)(sky_enabled != 0u) << 50 | (uint64_t)((flags & kFlagAbsFloatBit) != 0u) << 51 |
            (uint64_t)((flags & kFlagFastDiv) != 0u) << 52 | (camera ? kConfigCamera : 0ull);
+}
+// What a k_paths compiled for `key` does with the scene's range bit (kShapeRanges). The ranges hold for a
+// bounded number of throughput products, so they count only with the configuration baked in and at most
+// kRangesMaxBounces bounces: a throughput component is then 0 or >= (2^-5)^(max_bounces - 1) >= 2^-40 when
+// Russian roulette divides it (spt_device.h rr_divide_ranged states the proof).
+constexpr uint32_t kRangesMaxBounces = 9;
+__host__ __device__ constexpr bool flat_ranges_baked(uint64_t key) {
+    return (key & kShapeRanges) != 0ull && (key & kConfigValid) != 0ull && ((uint32_t)(key >> 38) & 63u) <= kRangesMaxBounces;
+}
+// ... and whether the tangent of a hit's normal needs no range test either: with SPT_FLAG_ABS_FLOAT for every
+// unit normal, without it only for normals the host has seen (a shape without spheres: flat_ranges_ok checks
+// the tangent of every stored normal). spt_device.h bounce_tangent_ranged states why.
+__host__ __device__ constexpr bool flat_tangent_baked(uint64_t key) {
+    return flat_ranges_baked(key) && ((((key >> 51) & 1ull) != 0ull) || (key & 63ull) == 0ull);
 }
 
 // BVH traversal stack of the persistent kernels: a global buffer (PassParams::stack), the 64 lanes'

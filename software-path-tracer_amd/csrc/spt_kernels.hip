@@ -980,7 +980,10 @@ struct ModelHit {
     bool entering;  // a sphere: not (d . n > 0); a quad or triangle: hit on its stored normal's side
     bool flip;      // nf = -n: a sphere hit from inside (n stays the outward normal)
 };
-template <int kEnv = 2, bool kRec = false, bool kNee = false, bool kBsdf = false>
+// kRanged (k_paths' step loop of a flat scene under spt_kernels.h flat_ranges_baked, with kRec): the shading
+// normal's inverse root and Russian roulette's divisions run without their range tests (inv_sqrt_ranged,
+// rr_divide_ranged: the same bits where the ranges hold, which scene.cpp flat_ranges_ok has checked).
+template <int kEnv = 2, bool kRec = false, bool kNee = false, bool kBsdf = false, bool kRanged = false>
 __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, const float4* __restrict__ mats,
                                           const ShadeParams& sp, uint32_t bounce_count, float t, uint32_t k, F3& o,
                                           F3 d, F3& T, uint32_t& rng, bool& alive, F3& add, F3& n,
@@ -1035,7 +1038,23 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
         emi = mats[2 * m + 1];
     }
     // n = Ng / |Ng| (:244-250)
-    const float inv_len = inv_sqrt_ref(ng.x * ng.x + ng.y * ng.y + ng.z * ng.z);
+    // kRanged: x = |Ng|^2 is in inv_sqrt_ranged's window [2^-96, 2^96).
+    //   - A quad's or triangle's Ng is the stored normal (or its negation: the same squares), and flat_ranges_ok
+    //     has evaluated this sum for it: in [2^-90, 2^90].
+    //   - A sphere's Ng = hit - centre is computed. With E the scene's coordinate bound (every |centre| + r,
+    //     every point of a quad or triangle <= E < 2^28), the ray starts at a hit point (|o| <= E (1 + 2^-10))
+    //     and |d|^2 = 1 +- 2^-20, so |L| <= 3.5 E, |b| <= 7 E, 4 a |c| <= 53 E^2, and the computed discriminant
+    //     is within 2^-13.3 E^2 of the exact quadratic's (b: 2^-18 E; b^2: 2^-14 E^2; 4 a c: 2^-15 E^2; the
+    //     subtraction: 2^-18 E^2). A point of the ray at parameter t lies sqrt(p^2 + (t - t_mid)^2 |d|^2) from
+    //     the centre, p the ray's distance from it. If p >= r / 2 that is >= r / 2 whatever t is. Otherwise the
+    //     exact discriminant is >= 2.99 r^2, the root's error is <= 2^-13.3 E^2 / (1.7 r), and with r >= E / 32
+    //     the computed t is within 2^-10 E = r / 32 of the exact root, which lies sqrt(r^2 - p^2) >= 0.86 r
+    //     from t_mid: the point is >= 0.8 r from the centre. Forming hit and hit - centre adds <= 2^-20 E =
+    //     2^-15 r per component. So |Ng| >= r / 4 and x >= r^2 / 17 >= 2^-95 (r * r >= 2^-90), and |Ng| <= 4 E
+    //     gives x < 2^61. (The general isect_sphere of a repeated ray and flat_sphere_pass form b, c and the
+    //     discriminant with the same operations.)
+    const float nn = ng.x * ng.x + ng.y * ng.y + ng.z * ng.z;
+    const float inv_len = (kRanged && kRec) ? inv_sqrt_ranged(nn) : inv_sqrt_ref(nn);
     n = F3{ng.x * inv_len, ng.y * inv_len, ng.z * inv_len};
     if constexpr (kBsdf) {
         const bool inside = sphere && dot3(d, n) > 0.0f;
@@ -1058,7 +1077,7 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
             if (random_float(rng) > cp) {
                 alive = false;
             } else {
-                T = rr_divide(T, cp);
+                T = (kRanged && kRec) ? rr_divide_ranged(T, cp) : rr_divide(T, cp);
             }
         }
         if (alive && !kBsdf) o = F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};  // :277-280
@@ -1109,11 +1128,13 @@ __device__ __forceinline__ bool shade_segment(const float4* __restrict__ prims, 
 // ---- next-event estimation (SPT_FLAG_NEE; oracle ref_trace_ray's NEE block) ----
 // The second half of shade_hit for a path past its light sample: Russian roulette (:264-270) with
 // bounce_count (after the increment); false ends the path.
+// kRanged: shade_hit's (rr_divide_ranged)
+template <bool kRanged = false>
 __device__ __forceinline__ bool rr_continue(const ShadeParams& sp, uint32_t bounce_count, F3& T, uint32_t& rng) {
     if (bounce_count > sp.rr_depth) {
         const float cp = fmaxf(fmaxf(T.x, T.y), T.z);
         if (random_float(rng) > cp) return false;
-        T = rr_divide(T, cp);
+        T = kRanged ? rr_divide_ranged(T, cp) : rr_divide(T, cp);
     }
     return true;
 }
@@ -1640,6 +1661,10 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     constexpr bool kView = !kBvh && !kStart0;
     static_assert(!kWide || (kView && !kChan && !kNee), "the wide form: the flat pixel-lane kernel over a view's lists");
     bake_config<kShape>(sp);
+    // the scene's range bit (spt_kernels.h kShapeRanges, scene.cpp flat_ranges_ok) with the configuration it holds
+    // for: the step loop's guard-free forms (shade_hit's kRanged, bounce_tangent_ranged, the path start's emission)
+    constexpr bool kRanged = !kBvh && !kStart0 && flat_ranges_baked(kShape);
+    constexpr bool kTanRanged = kRanged && flat_tangent_baked(kShape);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
     extern __shared__ float4 s_scene[];
@@ -2101,13 +2126,23 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         // so that a wave always leaves it and the grid drains.
         uint32_t steps_left = (n_slots + 64u) * ((kNee ? 2u : 1u) * sp.max_bounces + 2u) + n_frames + 4096u;
         const uint32_t steps_init = steps_left;
+        // the wide form under the range bit keeps the frame a new direction is drawn around (dn, dt) across the
+        // trips; in the other forms it measured more scratch (channel lanes, NEE, counting), so they keep theirs
+        constexpr bool kCarry = kRanged && kWide;
+        [[maybe_unused]] F3 dn_loop{0.f, 0.f, 0.f}, dt_loop{0.f, 0.f, 0.f};
         uint32_t titer = 0;  // BVH NEE kernels: the chunk's traversal iterations (its cost, with the steps)
         while ((__ballot(have) != 0ull || next < n_slots || oldest_s < n_slots) && steps_left-- != 0u) {
             // ---- one segment (bounce >= 1) for every lane with a live path ----
             SPT_MARK(step);
             bool fin = false;
             bool pend = false;  // a new direction is to be drawn around (dn, dt) below
+            // (kCarry: dn and dt live across the trips — they are assigned wherever `pend` is set, so the zero
+            // defaults are never read — and the trip starts without six moves and ends without the copies back)
             F3 dn{0.f, 0.f, 0.f}, dt{0.f, 0.f, 0.f};
+            if constexpr (kCarry) {
+                dn = dn_loop;
+                dt = dt_loop;
+            }
             bool snew = false;  // kNee: a shadow ray starts (its direction in d; the continuation's goes to nd)
             // kNee: the hit's draws (o: its offset point, n: its normal, bc: the bounce count after the hit):
             // the light sample, then Russian roulette; the direction around (dn, dt) is drawn at the step's
@@ -2127,7 +2162,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     snew = true;
                     if (kStats) atomicAdd(&s_shadow[0], 1u);
                 }
-                after = rr_continue(sp, bc, T, rng);
+                after = rr_continue<kRanged>(sp, bc, T, rng);
                 if (after) {
                     dn = n;
                     pend = true;
@@ -2198,8 +2233,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                 contributes = shade_hit<kEnv, !kBvh, true, true>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o,
                                                                                  d, T, rng, alive, add, n, &mh, spec);
                             else
-                                contributes = shade_hit<kEnv, !kBvh, true>(sh_prims, sh_mats, sp, bc + 1u, best_t,
-                                                                           best_k, o, d, T, rng, alive, add, n);
+                                contributes = shade_hit<kEnv, !kBvh, true, false, kRanged>(sh_prims, sh_mats, sp, bc + 1u, best_t,
+                                                                                           best_k, o, d, T, rng, alive, add, n);
                             if (contributes) L = F3{L.x + add.x, L.y + add.y, L.z + add.z};
                             if (kStats) {
                                 atomicAdd(&s_seg[bc], 1u);
@@ -2223,7 +2258,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                 if (kBsdf) spec = false;
                                 o = offset_origin(o, n);
                                 nee_hit(n, fin);
-                                if (pend) dt = bounce_tangent(n, sp.flags);
+                                if (pend) dt = kTanRanged ? bounce_tangent_ranged(n, sp.flags) : bounce_tangent(n, sp.flags);
                             }
                         }
                     } else {
@@ -2232,7 +2267,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     ModelHit mh{0u, true, false};
                     SPT_MARK(shade);
                     const bool contributes =
-                        shade_hit<kEnv, !kBvh, false, kBsdf>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, dn, &mh);
+                        shade_hit<kEnv, !kBvh, false, kBsdf, kRanged>(sh_prims, sh_mats, sp, bc + 1u, best_t, best_k, o, d, T, rng, alive, add, dn, &mh);
                     bool scattered = false;  // kBsdf: a METAL / DIELECTRIC hit has set o and d
                     if constexpr (kBsdf) {
                         if (alive && mh.word != 0u) {
@@ -2246,7 +2281,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         }
                     }
                     if (alive && !scattered) {
-                        dt = bounce_tangent(dn, sp.flags);
+                        dt = kTanRanged ? bounce_tangent_ranged(dn, sp.flags) : bounce_tangent(dn, sp.flags);
                         pend = true;
                     }
                     if (contributes) L = F3{L.x + add.x, L.y + add.y, L.z + add.z};
@@ -2308,6 +2343,12 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     const uint32_t k = __float_as_uint(p1.w) & ~kHitBit;
                     const float4 alb = s_scene[3u * k + 1u];
                     const float4 emi = s_scene[3u * k + 2u];
+                    // kRanged: every emission component is >= +0 with the sign bit clear (flat_ranges_ok), so
+                    // 1.0f * e = e and 0.0f + e = e bit for bit (only -0 would change), and a material
+                    // without the flag (emi.w == 0: every component compares equal to 0) holds +0 itself: the
+                    // record's three words are the select's result either way
+                    if (kRanged) L = F3{emi.x, emi.y, emi.z};
+                    else
                     L = emi.w != 0.0f ? F3{0.0f + 1.0f * emi.x, 0.0f + 1.0f * emi.y, 0.0f + 1.0f * emi.z}
                                       : F3{0.f, 0.f, 0.f};
                     T = F3{1.0f * alb.x, 1.0f * alb.y, 1.0f * alb.z};
@@ -2334,7 +2375,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 if (1u > sp.rr_depth) {  // Russian roulette at bounce_count 1 (:264-270)
                     const float cp = fmaxf(fmaxf(T.x, T.y), T.z);
                     if (random_float(rng) > cp) alive = false;
-                    else T = rr_divide(T, cp);
+                    else T = kRanged ? rr_divide_ranged(T, cp) : rr_divide(T, cp);
                 }
                 if (alive) {
                     const float4 p2 = kWide ? p2w : s_px[wave][kR2][r];
@@ -2389,6 +2430,10 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     }
                 }
                 finish(fin_s);
+            }
+            if constexpr (kCarry) {
+                dn_loop = dn;
+                dt_loop = dt;
             }
         }
         // the bound reached (steps_left wrapped): a logic error, reported instead of a silent partial image
