@@ -700,6 +700,103 @@ int spt_exposure_from_histogram(const uint32_t counts[SPT_METER_BINS], const spt
                                 float* exposure);
 int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const spt_display* display, uint32_t* out);
 
+/* ---- noise estimate (a superset: the reference renders until its window closes) --------------------
+ * How noisy is the image, and may the renderer stop? The accumulation after a call minus the accumulation
+ * before it is that call's batch of frames, and the variance of the batch means estimates the error of the
+ * mean. One streaming pass beside spt_render keeps two moments of the luminance per pixel; a meter turns them
+ * into a per-pixel relative error and an integer histogram of it; a host rule reads a quantile off the
+ * histogram. spt_render, the accumulation, the frame count and the stats are untouched, and a ctx that never
+ * calls these allocates nothing for them.
+ *
+ * Definition (spt_noise_update_host / spt_noise_meter_host compute it on the CPU from the functions the kernels
+ * compile, csrc/spt_noise.h: the same bits). Every value is fp32 without contraction, every `/` correctly
+ * rounded; only `+ - * /`, comparisons and integer operations on a float's bits are used. (Where an operation
+ * creates a NaN, inf / inf or inf - inf on moments no render produces, its sign is the hardware's: the host and
+ * the device then agree that e2 is a NaN, which is all its bin asks.)
+ *
+ * State. Per pixel one float4 (mean, m2, prevL, 0). Per ctx, on the host: the batch count B and the frames
+ * folded so far W, a float holding an integer; an update that would bring W above 2^24 is refused.
+ *
+ * Update with a batch, the frames in (frames_before, frame_count]. Once, on the host:
+ *   w = (float)(frame_count - frames_before);   Wn = W + w;   r = w / Wn.
+ * Per pixel, with a the accumulation (the sums):
+ *   L = (0.2126f*a.r + 0.7152f*a.g) + 0.0722f*a.b
+ *   d = (L - prevL) / w;   delta = d - mean
+ *   mean' = mean + r*delta;   m2' = m2 + (w*delta)*(d - mean');   prevL' = L;   the fourth word is 0.
+ * Then B' = B + 1 and W' = Wn. This is West's weighted form of Welford's update: calls of different lengths
+ * fold in correctly, and m2 / (B - 1) estimates the variance of one frame. The first batch after a restart
+ * starts from a zeroed state with B = W = 0.
+ *
+ * Noise of a pixel: needs B >= 2, a pooling radius of 0..2 and a dark_floor (finite, >= 0; default 0.01f).
+ *   inv = 1.0f / ((float)(B - 1) * W), once, on the host.
+ *   radius 0:  s_m2 = m2;  s_mean = mean.
+ *   radius > 0: each is a sum that starts at 0.0f and adds the taps of the (2*radius + 1)^2 window that lie
+ *              inside the image, rows outer and columns inner, and is then divided by the tap count as a float.
+ *   v = s_m2 * inv;   t = s_mean + dark_floor;   e2 = v / (t*t)
+ * e2 is the squared relative standard error of the mean luminance. Its bin:
+ *   bin = 255 if e2 is NaN; otherwise bin = e2 > 0 ? min(max((int)(bits(e2) >> 20), 792) - 792, 255) : 0.
+ * 792 is the key of 2^-28: the bins are eight per octave from 2^-28 to 2^4, a relative error of 0.006 % to
+ * 400 %. Bin 0 also holds zero, negatives and everything below; bin 255 also holds everything from 15 up,
+ * +inf and NaN. The counts are uint32_t, so they do not depend on the order of addition; with radius 0 the
+ * counts of row shards add up to the whole image's. Pooling is not defined on a row shard (its rows are not
+ * neighbours).
+ *
+ * Stop rule (host, in double): total = the sum of the counts; the first bin b at which the cumulative count
+ * reaches quantile * total. rel_error = sqrt(the lower edge of bin b + 1), the float whose bits are
+ * (793 + b) << 20: the bin's upper edge, so it errs on the safe side. +inf for b = 255; 0 for b = 0 and for an
+ * empty histogram.
+ * Not covered: per-channel moments, variance-guided filter weights, adaptive sampling, a false-colour resolve
+ * of the noise image, an estimate smoothed over time, pooling across row shards. */
+#define SPT_NOISE_BINS 256
+typedef struct spt_noise_params {      /* 16 bytes */
+    uint32_t radius;            /* 0, 1 or 2; default 1                                                 */
+    float    dark_floor;        /* finite, >= 0; default 0.01f                                          */
+    uint32_t reserved[2];       /* must be 0                                                            */
+} spt_noise_params;
+/* Host only: the defaults above. SPT_ERR_INVALID for NULL. */
+int spt_noise_params_default(spt_noise_params* out);
+/* Fold the frames since the last update (or since the accumulation restarted) into the ctx's moments;
+ * frame_count is the number of frames the accumulation holds, as the resolves take it. Asynchronous on the ctx
+ * stream. The first call allocates the state, 16 bytes per pixel (of the shard); spt_configure frees it when it
+ * reallocates the ctx's buffers. spt_reset, and with it every entry point that restarts the accumulation, sets
+ * B = W = 0 and has the next update start from a zeroed state. SPT_ERR_NOT_CONFIGURED before spt_configure;
+ * SPT_ERR_INVALID when frame_count is not greater than the frames already folded, or above 2^24. */
+int spt_noise_update(spt_ctx* ctx, uint32_t frame_count);
+/* Host only: the batches and frames folded since the last restart (either may be NULL). */
+int spt_noise_batches(const spt_ctx* ctx, uint32_t* batches, uint32_t* frames);
+/* The histogram of the ctx's per-pixel e2 on the ctx stream, waited for; also writes the e2 image (4 bytes per
+ * pixel, allocated by the first call). params = NULL: the defaults. SPT_ERR_INVALID before the second update
+ * since a restart (B < 2), for a parameter out of range or a non-zero reserved word, and for radius > 0 on a
+ * row shard (shard_count > 1). */
+int spt_noise_meter(spt_ctx* ctx, const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS]);
+/* The state (4 floats per pixel) and the last metering's e2 image (1 float per pixel) of the shard, waited for;
+ * SPT_ERR_INVALID while there is none (no update since spt_configure allocated; no metering). */
+int spt_read_noise_moments(spt_ctx* ctx, float* host_moments);
+int spt_read_noise(spt_ctx* ctx, float* host_e2);
+/* Their device addresses, valid until the next spt_configure (either output may be NULL; an image that does not
+ * exist yet gives a null address). *pixels: the shard's pixel count. */
+int spt_noise_device_ptr(spt_ctx* ctx, void** moments, void** e2, uint64_t* pixels);
+/* The same kernels over width * height moments in the caller's device memory, with the caller's B and W: the
+ * counterpart of spt_meter_device_image, for a gathered multi-GPU image. device_e2 (may be NULL): width * height
+ * floats of the caller's device memory for the per-pixel values. SPT_ERR_INVALID for a null pointer, an empty or
+ * too large image (>= 2^31 pixels), batches < 2, a W that is not an integer in [1, 2^24] or invalid parameters. */
+int spt_noise_meter_device_image(spt_ctx* ctx, const void* device_moments, uint32_t width, uint32_t height,
+                                 uint32_t batches, float frames, const spt_noise_params* params,
+                                 uint32_t counts[SPT_NOISE_BINS], void* device_e2);
+/* Host only, no device needed: the definition above by the functions the kernels compile: the same bits.
+ * spt_noise_update_host folds one batch of batch_frames frames into moments (n_pixels * 4 floats, in place),
+ * which held frames_before frames (0: they are taken as zero, whatever they hold); accum_rgba is the accumulation
+ * after the batch. SPT_ERR_INVALID for a null pointer, n_pixels == 0, a count that is not an integer, batch_frames
+ * < 1 or frames_before + batch_frames > 2^24.
+ * spt_noise_meter_host: counts and, if e2 is not NULL, the width * height per-pixel values; errors as
+ * spt_noise_meter_device_image.
+ * spt_noise_from_histogram: the stop rule; SPT_ERR_INVALID for a null pointer or a quantile outside (0, 1]. */
+int spt_noise_update_host(const float* accum_rgba, uint64_t n_pixels, float batch_frames, float frames_before,
+                          float* moments);
+int spt_noise_meter_host(const float* moments, uint32_t width, uint32_t height, uint32_t batches, float frames,
+                         const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS], float* e2);
+int spt_noise_from_histogram(const uint32_t counts[SPT_NOISE_BINS], double quantile, double* rel_error);
+
 /* ---- environment map (superset — the reference's SkyBox, Scene.h:268-278,
  * is loaded by dead code and never sampled) -------------------------------------------------- */
 /* Miss radiance from an octahedral environment map instead of sample_sky's gradient (only while

@@ -73,6 +73,7 @@ MATERIAL_MODEL_DTYPE = np.dtype([("kind", "<u4"), ("param", "<f4"), ("reserved",
 assert MATERIAL_MODEL_DTYPE.itemsize == 16
 MAT_DIFFUSE, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2  # spt_material_kind
 METER_BINS = 256  # SPT_METER_BINS
+NOISE_BINS = 256  # SPT_NOISE_BINS
 IMAGE_ACCUM, IMAGE_DENOISED, IMAGE_BLENDED = 0, 1, 2  # spt_image
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2  # spt_tonemap
 
@@ -202,6 +203,9 @@ EXPORTED_SYMBOLS = (
     "spt_exposure_params_default", "spt_meter_luminance", "spt_meter_device_image", "spt_resolve_display_rgba8",
     "spt_resolve_display_device_image", "spt_set_meter_form", "spt_meter_bin", "spt_luminance_histogram_host",
     "spt_exposure_from_histogram", "spt_display_host",
+    "spt_noise_params_default", "spt_noise_update", "spt_noise_batches", "spt_noise_meter", "spt_read_noise_moments",
+    "spt_read_noise", "spt_noise_device_ptr", "spt_noise_meter_device_image",
+    "spt_noise_update_host", "spt_noise_meter_host", "spt_noise_from_histogram",
 )
 COMM_ID_BYTES = 128  # SPT_COMM_ID_BYTES
 
@@ -317,6 +321,27 @@ class Display(ctypes.Structure):
         super().__init__(tonemap=tonemap, exposure=exposure)
 
 
+class NoiseParams(ctypes.Structure):
+    """spt_noise_params (16 bytes): the pooling radius of the noise meter (0, 1 or 2) and the luminance added to
+    a pixel's mean before the error is taken relative to it (finite, >= 0). NoiseParams() holds the library's
+    defaults (spt_noise_params_default); keyword arguments replace single fields."""
+    _fields_ = [
+        ("radius", ctypes.c_uint32),
+        ("dark_floor", ctypes.c_float),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        rc = load_library().spt_noise_params_default(ctypes.byref(self))
+        if rc != SPT_OK:
+            raise SptError(f"spt_noise_params_default -> {SPT_ERR.get(rc, rc)}")
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown spt_noise_params field {k}")
+            setattr(self, k, v)
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -425,6 +450,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_luminance_histogram_host": ([P, ctypes.c_uint64, ctypes.c_float, P], I),
         "spt_exposure_from_histogram": ([P, ctypes.POINTER(ExposureParams), ctypes.POINTER(ctypes.c_float)], I),
         "spt_display_host": ([P, ctypes.c_uint64, ctypes.c_float, ctypes.POINTER(Display), P], I),
+        "spt_noise_params_default": ([ctypes.POINTER(NoiseParams)], I),
+        "spt_noise_update": ([P, U32], I),
+        "spt_noise_batches": ([P, ctypes.POINTER(U32), ctypes.POINTER(U32)], I),
+        "spt_noise_meter": ([P, ctypes.POINTER(NoiseParams), P], I),
+        "spt_read_noise_moments": ([P, P], I),
+        "spt_read_noise": ([P, P], I),
+        "spt_noise_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64)], I),
+        "spt_noise_meter_device_image": ([P, P, U32, U32, U32, ctypes.c_float, ctypes.POINTER(NoiseParams), P, P], I),
+        "spt_noise_update_host": ([P, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, P], I),
+        "spt_noise_meter_host": ([P, U32, U32, U32, ctypes.c_float, ctypes.POINTER(NoiseParams), P, P], I),
+        "spt_noise_from_histogram": ([P, ctypes.c_double, ctypes.POINTER(ctypes.c_double)], I),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SPT_LIB_PATH") and not hasattr(lib, name):
@@ -668,6 +704,58 @@ def display_host(rgba: np.ndarray, display: Display, divisor: float = 1.0) -> np
     if rc != SPT_OK:
         raise SptError(f"spt_display_host -> {SPT_ERR.get(rc, rc)}")
     return out
+
+
+def noise_update_host(accum: np.ndarray, batch_frames: float, frames_before: float = 0.0,
+                      moments: Optional[np.ndarray] = None) -> np.ndarray:
+    """spt_noise_update_host (host only): the moments (the shape of accum) after folding one batch of batch_frames
+    frames into `moments`, which held frames_before frames (None with frames_before 0: the first batch); accum is
+    the accumulation after the batch. By the function the kernel compiles: the same bits as Context.noise_update."""
+    a = _pixels(accum, "noise_update_host")
+    if moments is None:
+        if frames_before != 0:
+            raise ValueError("noise_update_host: moments are needed once frames were folded")
+        m = np.zeros_like(a)
+    else:
+        m = np.array(moments, dtype=np.float32, order="C")
+        if m.shape != a.shape:
+            raise ValueError("noise_update_host: moments and accum differ in shape")
+    rc = load_library().spt_noise_update_host(_ptr(a), a.size // 4, batch_frames, frames_before, _ptr(m))
+    if rc != SPT_OK:
+        raise SptError(f"spt_noise_update_host -> {SPT_ERR.get(rc, rc)}")
+    return m
+
+
+def noise_meter_host(moments: np.ndarray, batches: int, frames: float, params: Optional[NoiseParams] = None
+                     ) -> Tuple[np.ndarray, np.ndarray]:
+    """spt_noise_meter_host (host only): (counts, e2) of a (height, width, 4) image of moments after `batches`
+    batches of `frames` frames in all: the NOISE_BINS counts and the (height, width) squared relative errors, by
+    the functions the kernels compile: the same bits as Context.noise_meter / read_noise."""
+    m = _pixels(moments, "noise_meter_host")
+    if m.ndim != 3:
+        raise ValueError("noise_meter_host: moments must be (height, width, 4)")
+    h, w = m.shape[:2]
+    counts = np.zeros(NOISE_BINS, dtype=np.uint32)
+    e2 = np.zeros((h, w), dtype=np.float32)
+    rc = load_library().spt_noise_meter_host(_ptr(m), w, h, batches, frames,
+                                             ctypes.byref(params) if params is not None else None, _ptr(counts), _ptr(e2))
+    if rc != SPT_OK:
+        raise SptError(f"spt_noise_meter_host -> {SPT_ERR.get(rc, rc)}")
+    return counts, e2
+
+
+def noise_from_histogram(counts: np.ndarray, quantile: float = 0.95) -> float:
+    """spt_noise_from_histogram (host only): the relative error that the share `quantile` of the pixels stays
+    below: the square root of the upper edge of the bin at which the cumulative count reaches it. 0 for bin 0 and
+    an empty histogram, inf for the last bin."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.shape != (NOISE_BINS,):
+        raise ValueError("noise_from_histogram: counts must hold NOISE_BINS values")
+    e = ctypes.c_double(0.0)
+    rc = load_library().spt_noise_from_histogram(_ptr(c), quantile, ctypes.byref(e))
+    if rc != SPT_OK:
+        raise SptError(f"spt_noise_from_histogram -> {SPT_ERR.get(rc, rc)}")
+    return float(e.value)
 
 
 def build_scene(scene: "int | str") -> Tuple[np.ndarray, np.ndarray, SptEnv]:
@@ -1094,6 +1182,56 @@ class Context:
                     "spt_resolve_display_device_image")
         return out
 
+    def noise_update(self, frame_count: int) -> None:
+        """spt_noise_update: fold the frames since the last update (or restart) into the per-pixel moments;
+        frame_count: the frames the accumulation holds. Asynchronous on the ctx stream."""
+        self._check(self.lib.spt_noise_update(self.h, frame_count), "spt_noise_update")
+
+    def noise_batches(self) -> Tuple[int, int]:
+        """spt_noise_batches: (batches, frames) folded since the accumulation last restarted."""
+        b, f = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(self.lib.spt_noise_batches(self.h, ctypes.byref(b), ctypes.byref(f)), "spt_noise_batches")
+        return int(b.value), int(f.value)
+
+    def noise_meter(self, radius: int = 1, dark_floor: float = 0.01) -> np.ndarray:
+        """spt_noise_meter: the NOISE_BINS counts of the per-pixel squared relative error (noise_from_histogram
+        reads a quantile off them), pooled over (2 radius + 1)^2 windows; also writes the image read_noise
+        returns. Needs two updates since the last restart."""
+        counts = np.zeros(NOISE_BINS, dtype=np.uint32)
+        p = NoiseParams(radius=radius, dark_floor=dark_floor)
+        self._check(self.lib.spt_noise_meter(self.h, ctypes.byref(p), _ptr(counts)), "spt_noise_meter")
+        return counts
+
+    def read_noise_moments(self) -> np.ndarray:
+        """spt_read_noise_moments: (shard pixels, 4) float32: mean, m2, prevL, 0."""
+        out = np.zeros((self.shard_pixels, 4), dtype=np.float32)
+        self._check(self.lib.spt_read_noise_moments(self.h, _ptr(out)), "spt_read_noise_moments")
+        return out
+
+    def read_noise(self) -> np.ndarray:
+        """spt_read_noise: the last metering's squared relative error per pixel of the shard."""
+        out = np.zeros(self.shard_pixels, dtype=np.float32)
+        self._check(self.lib.spt_read_noise(self.h, _ptr(out)), "spt_read_noise")
+        return out
+
+    def noise_device_ptr(self) -> Tuple[int, int, int]:
+        """spt_noise_device_ptr: (moments address, e2 address, pixels); an address is 0 while its image does not exist."""
+        m, e, n = ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_uint64(0)
+        self._check(self.lib.spt_noise_device_ptr(self.h, ctypes.byref(m), ctypes.byref(e), ctypes.byref(n)),
+                    "spt_noise_device_ptr")
+        return int(m.value or 0), int(e.value or 0), int(n.value)
+
+    def noise_meter_device_image(self, dev_ptr: int, width: int, height: int, batches: int, frames: float,
+                                 params: Optional[NoiseParams] = None, e2_dev_ptr: int = 0) -> np.ndarray:
+        """spt_noise_meter_device_image: the counts of width * height moments at a device address of the caller's
+        after `batches` batches of `frames` frames in all; e2_dev_ptr (0: none) receives the per-pixel values."""
+        counts = np.zeros(NOISE_BINS, dtype=np.uint32)
+        self._check(self.lib.spt_noise_meter_device_image(
+            self.h, ctypes.c_void_p(dev_ptr), width, height, batches, frames,
+            ctypes.byref(params) if params is not None else None, _ptr(counts), ctypes.c_void_p(e2_dev_ptr)),
+            "spt_noise_meter_device_image")
+        return counts
+
     def set_profiling(self, enable, counters: bool = False, span: bool = False) -> None:
         """enable: HIP-event timing of every launch; counters: k_paths also counts segments per
         bounce (a slower kernel variant; the wavefront schedules always count); span: instead of
@@ -1324,6 +1462,47 @@ class HIPPathTracer(PathTracer):
         self._reproject: Optional[ReprojectParams] = None
         self._tonemap = TONEMAP_CLAMP
         self._exposure_params: Optional[ExposureParams] = None
+        self._noise_target, self._noise_quantile = 0.0, 0.95
+        self._noise, self._converged, self._noise_folds = float("inf"), False, 0
+
+    # HIPPathTracer::kNoiseUpdateEvery / kNoiseMeterEvery
+    NOISE_UPDATE_EVERY = 8
+    NOISE_METER_EVERY = 4
+
+    def set_noise_target(self, rel_error: float, quantile: float = 0.95) -> None:
+        """Not in the reference interface: a stop rule. While rel_error > 0, render() folds the frames since the
+        last fold into the ctx's noise estimate (Context.noise_update) once NOISE_UPDATE_EVERY frames have
+        gathered, meters it after every NOISE_METER_EVERY folds (Context.noise_meter, default parameters) and takes
+        noise_from_histogram at `quantile`: noise(). Once that is at most rel_error the tracer is converged():
+        render() returns without tracing and the frame count stays. Anything that restarts the accumulation
+        clears both. rel_error <= 0 (the default) switches it off."""
+        if not 0.0 < quantile <= 1.0:
+            raise SptError("set_noise_target: the quantile must be in (0, 1]")
+        self._noise_target = rel_error if rel_error > 0.0 else 0.0
+        self._noise_quantile = quantile
+        self._noise, self._converged = float("inf"), False
+
+    def noise(self) -> float:
+        """The last metered value; inf before the first metering."""
+        return self._noise
+
+    def converged(self) -> bool:
+        return self._converged
+
+    def frame_count(self) -> int:
+        return self._frame_count
+
+    def _noise_step(self) -> None:
+        batches, folded = self._ctx.noise_batches()  # (a target switched on over unfolded frames: the first batch)
+        if self._frame_count - folded < self.NOISE_UPDATE_EVERY:
+            return
+        self._ctx.noise_update(self._frame_count)
+        self._noise_folds += 1
+        if self._noise_folds < self.NOISE_METER_EVERY or batches + 1 < 2:
+            return
+        self._noise_folds = 0
+        self._noise = noise_from_histogram(self._ctx.noise_meter(), self._noise_quantile)
+        self._converged = self._noise <= self._noise_target
 
     def set_tonemap(self, tonemap: int) -> None:
         """Not in the reference interface: the tone-mapping operator of get_render_result() (TONEMAP_CLAMP, the
@@ -1461,9 +1640,16 @@ class HIPPathTracer(PathTracer):
         if self._settings_mode and not self._settings.getProgressive():
             self._frame_count = 0  # a fresh accumulation every call
         self._invalidate()
+        if self._noise_target > 0.0:
+            if self._frame_count == 0:  # (the ctx's estimate restarted with the accumulation)
+                self._noise, self._converged, self._noise_folds = float("inf"), False, 0
+            elif self._converged:
+                return  # nothing traced, the frame count stays
         n = max(1, self._settings.getSamplesPerPixel()) if self._settings_mode else 1
         self._ctx.render(self._frame_count, n)
         self._frame_count += n
+        if self._noise_target > 0.0:
+            self._noise_step()
 
     def get_render_result(self) -> RenderResult:
         if self._frame_count <= 0:

@@ -68,6 +68,13 @@ namespace render
 		if (m_settingsMode && !m_renderSettings->getProgressive())
 			m_frameCount = 0; // a fresh accumulation every call
 		invalidate();
+		if (m_noiseTarget > 0.0)
+		{
+			if (m_frameCount == 0)
+				noise_restart(); // (the ctx's estimate restarted with the accumulation: spt_reset)
+			else if (m_converged)
+				return; // nothing traced, the frame count stays, what render() resolved stays valid
+		}
 		// reference mode: one progressive frame = 1 sample per pixel, seeded with m_frameCount + 1
 		// (:61); settings mode: getSamplesPerPixel() such frames in one call (k_paths from 4)
 		const uint32_t n = m_settingsMode ? std::max<uint32_t>(1u, m_renderSettings->getSamplesPerPixel()) : 1u;
@@ -88,6 +95,42 @@ namespace render
 			SPT_CALL(m_ctx, spt_render(m_ctx, m_frameCount, n));
 		}
 		m_frameCount += n;
+		if (m_noiseTarget > 0.0)
+			noise_step();
+	}
+
+	void HIPPathTracer::set_noise_target(double rel_error, double quantile)
+	{
+		SPT_VERIFY(quantile > 0.0 && quantile <= 1.0, "the noise quantile must be in (0, 1]");
+		m_noiseTarget = rel_error > 0.0 ? rel_error : 0.0; // (NaN: off)
+		m_noiseQuantile = quantile;
+		// (another quantile reads another value off the next metering's histogram: not converged until then)
+		m_noise = HUGE_VAL;
+		m_converged = false;
+	}
+
+	void HIPPathTracer::noise_restart()
+	{
+		m_noise = HUGE_VAL;
+		m_converged = false;
+		m_noiseFolds = 0;
+	}
+
+	void HIPPathTracer::noise_step()
+	{
+		// a target switched on over frames that were never folded: they are the first batch
+		uint32_t batches = 0, folded = 0;
+		SPT_CALL(m_ctx, spt_noise_batches(m_ctx, &batches, &folded));
+		if (m_frameCount - folded < kNoiseUpdateEvery)
+			return;
+		SPT_CALL(m_ctx, spt_noise_update(m_ctx, m_frameCount));
+		if (++m_noiseFolds < kNoiseMeterEvery || batches + 1u < 2u)
+			return;
+		m_noiseFolds = 0;
+		uint32_t counts[SPT_NOISE_BINS];
+		SPT_CALL(m_ctx, spt_noise_meter(m_ctx, nullptr, counts));
+		SPT_VERIFY(spt_noise_from_histogram(counts, m_noiseQuantile, &m_noise) == SPT_OK, "invalid noise quantile");
+		m_converged = m_noise <= m_noiseTarget;
 	}
 
 	void HIPPathTracer::set_settings_mode(bool enabled)

@@ -7,6 +7,7 @@
 // (render_assert.h:15-25).
 #pragma once
 
+#include <cmath>
 #include <memory>
 #include <vector>
 
@@ -95,6 +96,22 @@ namespace render
 		// nullptr: the library's defaults.
 		void set_exposure_params(const spt_exposure_params *params);
 
+		// Not in the reference interface (it renders for as long as its window is open): a stop rule. While
+		// rel_error > 0, render() folds the frames since the last fold into the ctx's noise estimate
+		// (spt_noise_update) once kNoiseUpdateEvery frames have gathered, and after every kNoiseMeterEvery folds
+		// meters it (spt_noise_meter with the default parameters: one stream wait and a 1 KB copy) and takes
+		// spt_noise_from_histogram at `quantile`: noise(). Once that is at most rel_error the tracer is
+		// converged(): render() then returns without tracing, the frame count stays, and get_render_result()
+		// goes on returning the converged image through whichever path is selected. Anything that restarts the
+		// accumulation clears converged() and noise(). rel_error <= 0 switches it off, which is the default:
+		// the backend then makes exactly the calls it makes without this. The cadences keep the folds and the
+		// waits below 5 % each of the frames they follow at 1920 x 1080.
+		static constexpr uint32_t kNoiseUpdateEvery = 8;
+		static constexpr uint32_t kNoiseMeterEvery = 4;
+		void set_noise_target(double rel_error, double quantile = 0.95);
+		double noise() const { return m_noise; }  // the last metered value; +inf before the first metering
+		bool converged() const { return m_converged; }
+
 	private:
 		void invalidate();
 		bool display_on() const;
@@ -129,5 +146,12 @@ namespace render
 		uint32_t m_tonemap = SPT_TONEMAP_CLAMP;    // set_tonemap's
 		spt_exposure_params m_exposureParams{};    // set_exposure_params's, while m_hasExposureParams
 		bool m_hasExposureParams = false;
+		double m_noiseTarget = 0.0;                // set_noise_target's; <= 0: off
+		double m_noiseQuantile = 0.95;
+		double m_noise = HUGE_VAL;
+		bool m_converged = false;
+		uint32_t m_noiseFolds = 0;                 // folds since the last metering
+		void noise_restart();
+		void noise_step();
 	};
 } // namespace render

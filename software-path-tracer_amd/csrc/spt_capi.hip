@@ -25,6 +25,7 @@
 #include "spt_jit.h"
 #include "spt_kernels.h"
 #include "spt_launch_plan.h"
+#include "spt_noise.h"
 #include "spt_reproject.h"
 
 using namespace spt;
@@ -37,6 +38,7 @@ static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes"
 static_assert(sizeof(spt_reproject_params) == 32, "spt_reproject_params is 32 bytes");
 static_assert(sizeof(spt_exposure_params) == 32, "spt_exposure_params is 32 bytes");
 static_assert(sizeof(spt_display) == 16, "spt_display is 16 bytes");
+static_assert(sizeof(spt_noise_params) == 16, "spt_noise_params is 16 bytes");
 
 namespace {
 
@@ -218,6 +220,15 @@ struct spt_ctx {
     uint32_t* display_stage = nullptr;
     uint64_t display_stage_pixels = 0;
     int meter_form = -1;
+    // The noise estimate (spt_noise_update / spt_noise_meter): the per-pixel moments and the e2 image
+    // (configure-sized, each allocated by the first call that writes it), and the batches B and frames W folded
+    // since the accumulation last restarted (noise_frames: W as the caller counts it). spt_reset clears the
+    // counts; an update that finds B = 0 zeroes the moments first.
+    float4* noise_state = nullptr;
+    float* noise_e2 = nullptr;
+    bool noise_metered = false;  // noise_e2 holds a metering of the current state's accumulation
+    uint32_t noise_batches = 0, noise_frames = 0;
+    float noise_W = 0.0f;
 
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
@@ -359,6 +370,9 @@ void free_buffers(spt_ctx* c) {
     free_dev(c->hist_view);
     free_dev(c->hist);
     free_dev(c->blend);
+    free_dev(c->noise_state);
+    free_dev(c->noise_e2);
+    c->noise_metered = false;
     c->derived.drop(Change::Buffers);
 }
 
@@ -1180,6 +1194,9 @@ int spt_reset(spt_ctx* c) {
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipMemsetAsync(c->accum, 0, sizeof(float4) * std::max<size_t>(c->pixels, 1), on_stream(c)));
     c->frame_count = 0;
+    c->noise_batches = c->noise_frames = 0;  // (the noise estimate restarts with the accumulation)
+    c->noise_W = 0.0f;
+    c->noise_metered = false;
     return SPT_OK;
 }
 
@@ -2308,6 +2325,107 @@ int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const 
     if (display_error(d)) return SPT_ERR_INVALID;
     for (uint64_t i = 0; i < n_pixels; ++i) out[i] = display_rgba8(pixel_of(rgba, i), divisor, d);
     return SPT_OK;
+}
+
+// ---- noise estimate: batch moments, the meter, the stop rule ------------------------------------------
+
+namespace {
+// counts and the e2 image (may be nullptr) of width x height device moments, waited for
+int noise_meter_image(spt_ctx* c, const float4* state, uint32_t width, uint32_t height, uint32_t batches, float W,
+                      const spt_noise_params& p, uint32_t* counts, float* e2) {
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (!c->meter_counts) SPT_HIP(c, hipMalloc(&c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS));
+    SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS, on_stream(c)));
+    launch_noise_meter(state, width, height, (int)p.radius, noise_inv(batches, W), p.dark_floor, c->meter_counts, e2, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    SPT_HIP(c, hipMemcpyAsync(counts, c->meter_counts, sizeof(uint32_t) * SPT_NOISE_BINS, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+static_assert(SPT_NOISE_BINS == SPT_METER_BINS, "the two meters share the ctx's 256 device words");
+}  // namespace
+
+int spt_noise_update(spt_ctx* c, uint32_t frame_count) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_noise_update before spt_configure");
+    if (frame_count <= c->noise_frames) return fail(c, SPT_ERR_INVALID, "spt_noise_update: no frames since the last update");
+    if (frame_count > (1u << 24)) return fail(c, SPT_ERR_INVALID, "spt_noise_update: more than 2^24 frames");
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t pixels = std::max<size_t>(c->pixels, 1);
+    if (!c->noise_state) SPT_HIP(c, hipMalloc(&c->noise_state, sizeof(float4) * pixels));
+    if (c->noise_batches == 0) SPT_HIP(c, hipMemsetAsync(c->noise_state, 0, sizeof(float4) * pixels, on_stream(c)));
+    const float w = (float)(frame_count - c->noise_frames);
+    launch_noise_update(c->accum, c->noise_state, c->pixels, noise_batch(w, c->noise_W), on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    c->noise_W = c->noise_W + w;
+    c->noise_frames = frame_count;
+    c->noise_batches += 1u;
+    c->noise_metered = false;
+    return SPT_OK;
+}
+
+int spt_noise_batches(const spt_ctx* c, uint32_t* batches, uint32_t* frames) {
+    if (!c) return SPT_ERR_INVALID;
+    if (batches) *batches = c->noise_batches;
+    if (frames) *frames = c->noise_frames;
+    return SPT_OK;
+}
+
+int spt_noise_meter(spt_ctx* c, const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS]) {
+    if (!c || !counts) return SPT_ERR_INVALID;
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_noise_meter before spt_configure");
+    const spt_noise_params p = params ? *params : kNoiseDefaults;
+    if (const char* msg = noise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
+    if (c->noise_batches < 2) return fail(c, SPT_ERR_INVALID, "spt_noise_meter: fewer than two updates since the accumulation restarted");
+    if (p.radius > 0 && c->cfg.shard_count != 1u)
+        return fail(c, SPT_ERR_INVALID, "spt_noise_meter: pooling (radius > 0) needs the whole image (shard_count 1)");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pixels == 0) {
+        std::memset(counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS);
+        return SPT_OK;
+    }
+    if (!c->noise_e2) SPT_HIP(c, hipMalloc(&c->noise_e2, sizeof(float) * c->pixels));
+    const int rc = noise_meter_image(c, c->noise_state, c->cfg.width, c->rows, c->noise_batches, c->noise_W, p, counts, c->noise_e2);
+    c->noise_metered = rc == SPT_OK;
+    return rc;
+}
+
+int spt_read_noise_moments(spt_ctx* c, float* host_moments) {
+    if (!c || !host_moments) return SPT_ERR_INVALID;
+    if (!c->noise_state || c->noise_batches == 0) return fail(c, SPT_ERR_INVALID, "no noise moments: spt_noise_update first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pixels == 0) return SPT_OK;
+    SPT_HIP(c, hipMemcpyAsync(host_moments, c->noise_state, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+
+int spt_read_noise(spt_ctx* c, float* host_e2) {
+    if (!c || !host_e2) return SPT_ERR_INVALID;
+    if (!c->noise_e2 || !c->noise_metered) return fail(c, SPT_ERR_INVALID, "no noise image: spt_noise_meter first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipMemcpyAsync(host_e2, c->noise_e2, sizeof(float) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
+}
+
+int spt_noise_device_ptr(spt_ctx* c, void** moments, void** e2, uint64_t* pixels) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
+    if (moments) *moments = c->noise_state;
+    if (e2) *e2 = c->noise_e2;
+    if (pixels) *pixels = c->pixels;
+    return SPT_OK;
+}
+
+int spt_noise_meter_device_image(spt_ctx* c, const void* device_moments, uint32_t width, uint32_t height, uint32_t batches,
+                                 float frames, const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS],
+                                 void* device_e2) {
+    if (!c || !device_moments || !counts) return SPT_ERR_INVALID;
+    const spt_noise_params p = params ? *params : kNoiseDefaults;
+    if (const char* msg = noise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
+    if (const char* msg = noise_image_error(width, height, batches, frames)) return fail(c, SPT_ERR_INVALID, msg);
+    return noise_meter_image(c, (const float4*)device_moments, width, height, batches, frames, p, counts, (float*)device_e2);
 }
 
 int spt_camera_look_at(const float eye[3], const float target[3], const float up[3], float vfov_degrees,
