@@ -20,6 +20,7 @@
 #include "spt.h"
 #include "spt_ctx_state.h"
 #include "spt_denoise.h"
+#include "spt_dev_mem.h"
 #include "spt_device.h"
 #include "spt_display.h"
 #include "spt_jit.h"
@@ -81,15 +82,100 @@ struct EventPair {
 struct ViewHalf {
     hipStream_t stream = nullptr;  // non-blocking, created with the ctx
     hipEvent_t done = nullptr;     // behind the half's last launch of a call: the ctx stream waits on it (the join)
-    uint16_t* cost = nullptr;      // the half's first-tier chunk costs and order (PassParams), [pixels / 2 + 64]
-    uint32_t* order = nullptr;     // (its key: DerivedState::half_order_key)
-    uint32_t* work = nullptr;      // 2 sets of kWorkWords of its own (k_paths zeroes work_next in stream order:
-    uint32_t work_parity = 0;      // a set is never shared across streams)
+    uint32_t* work = nullptr;      // 2 sets of kWorkWords of its own, inside the ctx's `work` (k_paths zeroes work_next
+    uint32_t work_parity = 0;      // in stream order: a set is never shared across streams)
+};
+
+// ---- device memory: every allocation has an owner (spt_dev_mem.h), in the record of what frees it ----
+struct HipAlloc {
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) == hipSuccess) return p;
+        (void)hipGetLastError();  // (the caller reports the failure: no sticky error is left for a later check)
+        return nullptr;
+    }
+    static void free(void* p) { (void)hipFree(p); }
+};
+template <class T>
+using Dev = DevBuf<T, HipAlloc>;
+
+// float4s in n records of a device array the kernels address as float4 (scene.h DevPrim, DevMaterial, DevEmitter)
+template <class Rec>
+size_t float4s(size_t n) {
+    static_assert(sizeof(Rec) % sizeof(float4) == 0, "a device record is whole float4s");
+    return n * (sizeof(Rec) / sizeof(float4));
+}
+static_assert(kDevNodeBytes % sizeof(float4) == 0, "a device node is whole float4s");
+
+// The scene's: freed by free_scene (spt_set_scene, a failed upload, spt_destroy).
+struct SceneMem {
+    Dev<float4> d_prims;
+    Dev<float4> d_mats;
+    Dev<float4> d_nodes;
+    Dev<float4> d_emit;  // SPT_FLAG_NEE: the sampled emitters (scene.h DevEmitter), n_emit records
+    Dev<uint32_t> d_mat_map;  // the caller's material index behind each device material (h_dev_mat)
+    // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
+    // model is not DIFFUSE (bsdf)
+    Dev<uint32_t> d_reusable;
+    Dev<uint8_t> bvh_stack;  // the persistent kernels' traversal stacks (global memory)
+};
+
+// The configuration's, each sized by it: freed by free_buffers (a reallocating spt_configure, spt_destroy), so
+// none outlives the size it was allocated for. What spt_configure does not allocate, the first call that
+// writes it does.
+struct ConfigMem {
+    Dev<float4> q_o[2], q_d[2], q_t[2];
+    Dev<float2> hit;
+    Dev<float4> radiance;
+    Dev<float4> accum;
+    Dev<float2> hit_cache;  // k_frame: each shard pixel's camera-segment closest hit
+    Dev<uint16_t> chunk_cost;  // flat k_paths' first-tier chunk costs and order (PassParams)
+    Dev<uint32_t> chunk_order;
+    struct {  // ... and each half's of a split view, [pixels / 2 + 64] (its key: DerivedState::half_order_key)
+        Dev<uint16_t> cost;
+        Dev<uint32_t> order;
+    } half_mem[2];
+    // Flat k_paths' view lists (spt_kernels.h ViewPlan): every pixel's bounce 0, compacted into live-pixel
+    // records and constant pixels. Built behind the first persistent launch that finds them dropped; the
+    // persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
+    Dev<float4> view_live;      // [3 * pixels]
+    Dev<float4> view_const;     // [pixels]
+    Dev<uint32_t> view_counts;  // [2] live, constant; then the compaction's per-block scratch
+    Dev<uint4> live_rec;        // hit_cache compacted: the live pixels' records (kFrameHitCache 2)
+    Dev<uint32_t> sky_pix;      // ... the sky pixels' indices
+    Dev<uint32_t> list_counts;  // [2] live, sky; then the compaction's per-block scratch
+    Dev<uint32_t> resolved;
+    // sorted ray queues (SPT_FLAG_SORTED_RAYS)
+    Dev<uint16_t> ray_keys;
+    Dev<uint32_t> ray_perm, ray_bins, ray_cursor;
+    Dev<float4> feat_a, feat_b, feat_albedo;  // spt_render_features: the first-hit images
+    Dev<float4> dn[2];                        // spt_denoise: the filter's two ping-pong images
+    // Temporal reprojection. spt_history_capture: the captured view — image with lengths, feat_a, feat_b in
+    // 3 * pixels float4, laid out as hist_view_layout says (spt_reproject.h)
+    Dev<float4> hist_view;
+    Dev<float4> hist;         // spt_reproject: the active history (rgb, length)
+    Dev<float4> blend;        // spt_history_blend: the blended image
+    Dev<float4> noise_state;  // spt_noise_update: the per-pixel moments
+    Dev<float> noise_e2;      // spt_noise_meter: the e2 image
+};
+
+// The context's own: freed by spt_destroy (gather_buf by free_comm as well).
+struct OwnMem {
+    Dev<uint32_t> counts;
+    Dev<unsigned long long> totals;
+    Dev<uint32_t> work;  // k_paths / k_frame work heads: 2 sets of kWorkWords, alternating per launch; then two per view half
+    Dev<float4> d_env;   // octahedral environment map (spt_set_env_map) or empty
+    Dev<float4> d_camera;  // the camera's device record (PassParams::cam_pose), allocated by the first spt_set_camera
+    // The luminance meter and the display transform: scratch only, nothing a change could make stale. The 256
+    // device words a metering sums into and the staging image of spt_resolve_display_device_image (grown on demand)
+    Dev<uint32_t> meter_counts;
+    Dev<uint32_t> display_stage;
+    Dev<float4> gather_buf;  // rank 0: comm_ranks padded shards; other ranks: their padded shard
 };
 
 }  // namespace
 
-struct spt_ctx {
+struct spt_ctx : SceneMem, ConfigMem, OwnMem {  // (as bases: a buffer is c->accum, whichever record holds it)
     int device = -1;
     hipStream_t own_stream = nullptr;
     // The stream the caller's work is ordered on. Everything but the split launches' join reaches it through
@@ -114,18 +200,12 @@ struct spt_ctx {
     uint32_t cu_count = 256;
     DerivedState derived;  // which of the results cached below are valid (spt_ctx_state.h: what each change drops)
 
-    // scene
-    float4* d_prims = nullptr;
-    float4* d_mats = nullptr;
-    float4* d_nodes = nullptr;
-    float4* d_env = nullptr;  // octahedral environment map (spt_set_env_map) or nullptr
-    float4* d_emit = nullptr;  // SPT_FLAG_NEE: the sampled emitters (scene.h DevEmitter), n_emit records
-    uint32_t n_emit = 0;
+    // scene (its device arrays: SceneMem)
+    uint32_t n_emit = 0;          // records in d_emit
     uint32_t n_emit_spheres = 0;  // ... of which spheres (NeeParams::spheres)
     uint32_t env_w = 0, env_h = 0;
     uint32_t n_prims = 0, n_nodes = 0, n_mats = 0;
     uint32_t n_dev_nodes = 0;  // records in d_nodes (4-wide, quantized): bounds the kernels' LDS top-node copies
-    void* bvh_stack = nullptr;  // the persistent kernels' traversal stacks (global memory)
     uint32_t bvh_stack_need = 0;  // the most stack entries a traversal of the 4-wide tree holds (bvh4_stack_need)
     uint32_t bvh_stack_stride = 0;  // entries per lane in bvh_stack (bvh_stack_stride(need)); 0: none allocated
     uint32_t bvh_stack_tb = 1;      // 4-B stack entries: bits of the entry-distance code (bvh_stack_t0_bits)
@@ -148,36 +228,14 @@ struct spt_ctx {
     uint32_t n_sub = 0;         // block-private sub-queues (= blocks of every extend/shade launch)
     uint32_t sub_cap = 0;       // capacity of one sub-queue
 
-    // device buffers
-    float4* q_o[2] = {nullptr, nullptr};
-    float4* q_d[2] = {nullptr, nullptr};
-    float4* q_t[2] = {nullptr, nullptr};
-    float2* hit = nullptr;
-    float4* radiance = nullptr;
-    float4* accum = nullptr;
-    float2* hit_cache = nullptr;  // k_frame: each shard pixel's camera-segment closest hit (configure-sized)
-    uint16_t* chunk_cost = nullptr;   // flat k_paths' first-tier chunk costs and order (PassParams)
-    uint32_t* chunk_order = nullptr;
-    // Flat k_paths' view lists (spt_kernels.h ViewPlan): every pixel's bounce 0, compacted into live-pixel
-    // records and constant pixels. Built behind the first persistent launch that finds them dropped; the
-    // persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
-    float4* view_live = nullptr;      // [3 * pixels] allocated by the first build
-    float4* view_const = nullptr;     // [pixels]
-    uint32_t* view_counts = nullptr;  // [2] live, constant; then the compaction's per-block scratch
+    // what goes with the device buffers (ConfigMem, OwnMem)
     uint32_t view_n[2] = {0, 0};      // view_counts[0..1], read back once per build
     int32_t view_cache = 0;           // spt_tuning: 0 = automatic, -1 = never (every launch computes bounce 0 itself)
     bool last_view_cached = false;    // the last persistent launch ran over the lists
-    uint4* live_rec = nullptr;     // hit_cache compacted: the live pixels' records (kFrameHitCache 2)
-    uint32_t* sky_pix = nullptr;   // ... the sky pixels' indices
-    uint32_t* list_counts = nullptr;  // [2] live, sky; then the compaction's per-block scratch
     uint32_t live_pixels = 0;         // list_counts[0], read back once per compaction
-    uint32_t* counts = nullptr;
-    unsigned long long* totals = nullptr;
-    uint32_t* work = nullptr;  // k_paths / k_frame work heads: 2 sets of kWorkWords, alternating per launch
-    uint32_t work_parity = 0;
+    uint32_t work_parity = 0;         // which of `work`'s two sets the next launch on the ctx stream takes
     uint32_t chunks_per_wave = 0;  // k_paths: chunks per resident wave in each small tail tier (spt_tuning; 0 = auto)
     uint32_t px_shift = 0;         // k_paths forced chunk size, log2 pixels (spt_tuning.px_shift = 2..5, clamped to the build)
-    uint32_t* resolved = nullptr;
     // spt_register_host_output: a caller's host image buffer, page-locked and mapped into the GPU's
     // address space, that the resolve kernel writes over PCIe directly (no device staging, no DMA copy)
     void* out_host = nullptr;
@@ -190,42 +248,16 @@ struct spt_ctx {
 
     uint32_t frame_count = 0;
 
-    // spt_render_features: the first-hit images of the current scene, camera and configuration
-    // (configure-sized, allocated by the first call), and the caller's material index behind each device
-    // material (h_dev_mat, uploaded with the scene)
-    float4* feat_a = nullptr;
-    float4* feat_b = nullptr;
-    float4* feat_albedo = nullptr;
-    uint32_t* d_mat_map = nullptr;
-    // spt_denoise: the filter's two ping-pong images (allocated by the first call)
-    float4* dn[2] = {nullptr, nullptr};
     int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
-    // Temporal reprojection, every buffer allocated by the first call that needs it (configure-sized).
-    // spt_history_capture: the captured view — image with lengths, feat_a, feat_b in 3 * pixels float4, laid
-    // out as hist_view_layout says (spt_reproject.h) — and its camera
-    float4* hist_view = nullptr;
+    // spt_history_capture: the captured view's (hist_view) layout and camera
     int hist_view_layout = 0;
     bool hist_view_has_camera = false;
     spt_camera hist_view_camera{};
-    float4* hist = nullptr;      // spt_reproject: the active history (rgb, length)
-    float4* blend = nullptr;     // spt_history_blend: the blended image
     int hist_layout = -1;        // spt_set_history_layout: -1 the layout measured faster
-    // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
-    // model is not DIFFUSE (bsdf)
-    uint32_t* d_reusable = nullptr;
-    // The luminance meter and the display transform: scratch only, nothing a change could make stale. The 256
-    // device words a metering sums into, the staging image of spt_resolve_display_device_image (grown on
-    // demand) and spt_set_meter_form's choice (-1: the form measured faster).
-    uint32_t* meter_counts = nullptr;
-    uint32_t* display_stage = nullptr;
-    uint64_t display_stage_pixels = 0;
-    int meter_form = -1;
-    // The noise estimate (spt_noise_update / spt_noise_meter): the per-pixel moments and the e2 image
-    // (configure-sized, each allocated by the first call that writes it), and the batches B and frames W folded
-    // since the accumulation last restarted (noise_frames: W as the caller counts it). spt_reset clears the
-    // counts; an update that finds B = 0 zeroes the moments first.
-    float4* noise_state = nullptr;
-    float* noise_e2 = nullptr;
+    int meter_form = -1;         // spt_set_meter_form: -1 the form measured faster
+    // The noise estimate (spt_noise_update / spt_noise_meter): the batches B and frames W folded into
+    // noise_state since the accumulation last restarted (noise_frames: W as the caller counts it). spt_reset
+    // clears the counts; an update that finds B = 0 zeroes the moments first.
     bool noise_metered = false;  // noise_e2 holds a metering of the current state's accumulation
     uint32_t noise_batches = 0, noise_frames = 0;
     float noise_W = 0.0f;
@@ -233,7 +265,6 @@ struct spt_ctx {
     // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
     bool has_camera = false;
     spt_camera camera{};
-    float4* d_camera = nullptr;  // its device record (PassParams::cam_pose), allocated by the first spt_set_camera
     // spt_set_camera_lens: the camera's thin lens, or none; kept across spt_configure and spt_set_camera(cam)
     bool has_lens = false;
     spt_lens lens{};
@@ -278,9 +309,8 @@ struct spt_ctx {
     uint32_t bvh_bins = 0;         // spt_tuning: 0 = the builder's default
     int32_t specialize = 0;        // spt_tuning: flat scenes' kernels compiled for their shape: 0 = in the
                                    // background (generic kernels until ready), 1 = inside the first launch, -1 = never
-    // sorted ray queues (SPT_FLAG_SORTED_RAYS): the binning grid over the BVH scene's bounds, buffers
+    // sorted ray queues (SPT_FLAG_SORTED_RAYS): the binning grid over the BVH scene's bounds
     float scene_lo[3] = {0.f, 0.f, 0.f}, scene_hi[3] = {1.f, 1.f, 1.f};
-    uint16_t* ray_keys = nullptr;
     // host copies of the current scene for spt_update_prims: the caller's arrays, and for a BVH scene
     // the device-order records and the binary tree (refitted, not rebuilt, on an edit)
     std::vector<spt_prim> h_prims;
@@ -288,10 +318,6 @@ struct spt_ctx {
     std::vector<DevPrim> h_dp;
     std::vector<BvhNode> h_nodes;
     std::vector<uint32_t> h_pos;  // original primitive index -> its record's position on the device
-    uint64_t node_alloc = 0;      // bytes allocated at d_nodes
-    uint32_t* ray_perm = nullptr;
-    uint32_t* ray_bins = nullptr;
-    uint32_t* ray_cursor = nullptr;
     bool last_specialized = false; // the last persistent / frame launch ran the specialized kernel
     uint32_t last_pairs = 0;       // ... whose key held this many wall pairs (flat_shape_pairs)
     bool last_ranges = false;      // ... a k_paths whose step loop ran its guard-free forms (flat_ranges_baked)
@@ -299,8 +325,6 @@ struct spt_ctx {
     // multi-GPU (spt_comm_init / spt_gather_image)
     ncclComm_t comm = nullptr;
     int comm_ranks = 0, comm_rank = -1;
-    float4* gather_buf = nullptr;  // rank 0: comm_ranks padded shards; other ranks: their padded shard
-    size_t gather_elems = 0;       // floats in gather_buf
     // spt_gather_image_overlapped: the gather runs on a stream of its own while the ctx stream renders on
     hipStream_t comm_stream = nullptr;
     hipEvent_t snap_ready = nullptr;   // ctx stream: the shard snapshot is in gather_buf
@@ -329,49 +353,15 @@ int fail(spt_ctx* c, int code, const std::string& msg) {
             return fail((ctx), SPT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
+// buf holds exactly n elements (kept if it does already), or SPT_ERR_HIP and "<who>: allocation failed"
+template <class T>
+int ensure_buf(spt_ctx* c, Dev<T>& buf, size_t n, const char* who) {
+    if (buf.ensure(n)) return SPT_OK;
+    return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
 }
 
 void free_buffers(spt_ctx* c) {
-    for (int k = 0; k < 2; ++k) {
-        free_dev(c->q_o[k]);
-        free_dev(c->q_d[k]);
-        free_dev(c->q_t[k]);
-    }
-    free_dev(c->hit);
-    free_dev(c->ray_keys);
-    free_dev(c->ray_perm);
-    free_dev(c->ray_bins);
-    free_dev(c->ray_cursor);
-    free_dev(c->radiance);
-    free_dev(c->accum);
-    free_dev(c->hit_cache);
-    free_dev(c->chunk_cost);
-    free_dev(c->chunk_order);
-    for (ViewHalf& h : c->half) {
-        free_dev(h.cost);
-        free_dev(h.order);
-    }
-    free_dev(c->view_live);
-    free_dev(c->view_const);
-    free_dev(c->view_counts);
-    free_dev(c->live_rec);
-    free_dev(c->sky_pix);
-    free_dev(c->list_counts);
-    free_dev(c->resolved);
-    free_dev(c->feat_a);
-    free_dev(c->feat_b);
-    free_dev(c->feat_albedo);
-    free_dev(c->dn[0]);
-    free_dev(c->dn[1]);
-    free_dev(c->hist_view);
-    free_dev(c->hist);
-    free_dev(c->blend);
-    free_dev(c->noise_state);
-    free_dev(c->noise_e2);
+    static_cast<ConfigMem&>(*c) = {};
     c->noise_metered = false;
     c->derived.drop(Change::Buffers);
 }
@@ -433,20 +423,13 @@ void free_comm(spt_ctx* c) {
     c->comm = nullptr;
     c->comm_ranks = 0;
     c->comm_rank = -1;
-    free_dev(c->gather_buf);
-    c->gather_elems = 0;
+    c->gather_buf.reset();
 }
 
 void free_scene(spt_ctx* c) {
     c->derived.drop(Change::Scene);
-    free_dev(c->bvh_stack);
+    static_cast<SceneMem&>(*c) = {};
     c->bvh_stack_stride = 0;
-    free_dev(c->d_prims);
-    free_dev(c->d_mats);
-    free_dev(c->d_nodes);
-    free_dev(c->d_emit);
-    free_dev(c->d_mat_map);
-    free_dev(c->d_reusable);
     c->n_prims = c->n_nodes = c->n_dev_nodes = c->n_emit = c->n_emit_spheres = 0;
     c->has_scene = false;
 }
@@ -633,7 +616,7 @@ static CameraLens lens_scalars(const spt_camera& cam, const spt_lens& lens) {
 static int write_camera_record(spt_ctx* c) {
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    if (!c->d_camera) SPT_HIP(c, hipMalloc(&c->d_camera, 4 * sizeof(float4)));
+    if (const int rc = ensure_buf(c, c->d_camera, 4, "spt_set_camera"); rc != SPT_OK) return rc;
     const spt_camera& cam = c->camera;
     const CameraLens l = c->has_lens ? lens_scalars(cam, c->lens) : CameraLens{0.0f, 0.0f, 0.0f};
     const uint32_t mode = camera_mode(c);
@@ -788,10 +771,9 @@ int spt_create(spt_ctx** out, int device_id) {
     // best on C2 among 4/6/8/12 per CU (scripts/gpu_sweep.sh).
     c->n_sub = c->cu_count * 12u;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->counts, sizeof(uint32_t) * 2 * (kMaxBounces + 1) * c->n_sub) != hipSuccess ||
-        hipMalloc(&c->totals, sizeof(unsigned long long) * kTotals) != hipSuccess ||
+        !c->counts.alloc((size_t)2 * (kMaxBounces + 1) * c->n_sub) || !c->totals.alloc(kTotals) ||
         // (work heads: the ctx stream's two sets, then two per view half)
-        hipMalloc(&c->work, sizeof(uint32_t) * 6 * kWorkWords) != hipSuccess ||
+        !c->work.alloc(6 * kWorkWords) ||
         hipMemset(c->work, 0, sizeof(uint32_t) * 6 * kWorkWords) != hipSuccess ||
         hipStreamCreateWithFlags(&c->half[0].stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->half[1].stream, hipStreamNonBlocking) != hipSuccess ||
@@ -826,13 +808,7 @@ void spt_destroy(spt_ctx* c) {
     free_buffers(c);
     free_scene(c);
     free_comm(c);
-    free_dev(c->counts);
-    free_dev(c->totals);
-    free_dev(c->d_env);
-    free_dev(c->d_camera);
-    free_dev(c->work);
-    free_dev(c->meter_counts);
-    free_dev(c->display_stage);
+    static_cast<OwnMem&>(*c) = {};  // (all device memory goes here, before the streams: `delete` finds the records empty)
     if (c->out_host) (void)hipHostUnregister(c->out_host);
     for (ViewHalf& h : c->half) {
         if (h.done) (void)hipEventDestroy(h.done);
@@ -922,33 +898,25 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
         flat_pairs = flat_wall_pairs(sorted, ends, flat_rect);  // (reorders the axis groups: pairs first)
         dp.insert(dp.end(), sorted.begin(), sorted.end());
     }
-    if (n_prims) {
-        SPT_HIP(c, hipMalloc(&c->d_prims, sizeof(DevPrim) * dp.size()));
-        SPT_HIP(c, hipMemcpy(c->d_prims, dp.data(), sizeof(DevPrim) * dp.size(), hipMemcpyHostToDevice));
-    }
-    SPT_HIP(c, hipMalloc(&c->d_mats, sizeof(DevMaterial) * n_mats));
-    SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * n_mats, hipMemcpyHostToDevice));
     if (dev_mat.empty())  // (a BVH scene keeps the caller's materials as they are)
         for (uint32_t i = 0; i < n_mats; ++i) dev_mat.push_back(i);
-    SPT_HIP(c, hipMalloc(&c->d_mat_map, sizeof(uint32_t) * dev_mat.size()));
-    SPT_HIP(c, hipMemcpy(c->d_mat_map, dev_mat.data(), sizeof(uint32_t) * dev_mat.size(), hipMemcpyHostToDevice));
-    if (!emit.empty()) {
-        SPT_HIP(c, hipMalloc(&c->d_emit, sizeof(DevEmitter) * emit.size()));
-        SPT_HIP(c, hipMemcpy(c->d_emit, emit.data(), sizeof(DevEmitter) * emit.size(), hipMemcpyHostToDevice));
-    }
     const void* node_data = tree.bytes.data();  // quantized (scene.h), exact decode on the device
     const uint64_t node_bytes = tree.bytes.size();
-    c->node_alloc = node_bytes;
-    if (node_bytes) {
-        SPT_HIP(c, hipMalloc(&c->d_nodes, node_bytes));
-        SPT_HIP(c, hipMemcpy(c->d_nodes, node_data, node_bytes, hipMemcpyHostToDevice));
-    }
-    if (!nodes.empty()) {  // every resident lane's traversal stack (8 waves x 4 SIMDs per CU), as deep as the tree needs
-        const uint32_t stride = bvh_stack_stride(stack_need);
-        const size_t bytes = (size_t)kBvhStackEntryBytes * stride * 64u * kMaxResidentWaves * c->cu_count;
-        SPT_HIP(c, hipMalloc(&c->bvh_stack, bytes));
-        c->bvh_stack_stride = stride;
-    }
+    // every resident lane's traversal stack (8 waves x 4 SIMDs per CU), as deep as the tree needs
+    const uint32_t stride = nodes.empty() ? 0u : bvh_stack_stride(stack_need);
+    // (a failure from here on leaves has_scene false, free_scene's: nothing reads a partly uploaded scene, and
+    // the next spt_set_scene frees it)
+    if (!c->d_prims.alloc(float4s<DevPrim>(dp.size())) || !c->d_mats.alloc(float4s<DevMaterial>(n_mats)) ||
+        !c->d_mat_map.alloc(dev_mat.size()) || !c->d_emit.alloc(float4s<DevEmitter>(emit.size())) ||
+        !c->d_nodes.alloc(node_bytes / sizeof(float4)) ||
+        !c->bvh_stack.alloc((size_t)kBvhStackEntryBytes * stride * 64u * kMaxResidentWaves * c->cu_count))
+        return fail(c, SPT_ERR_HIP, "spt_set_scene: allocation failed");
+    c->bvh_stack_stride = stride;
+    if (n_prims) SPT_HIP(c, hipMemcpy(c->d_prims, dp.data(), sizeof(DevPrim) * dp.size(), hipMemcpyHostToDevice));
+    SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * n_mats, hipMemcpyHostToDevice));
+    SPT_HIP(c, hipMemcpy(c->d_mat_map, dev_mat.data(), sizeof(uint32_t) * dev_mat.size(), hipMemcpyHostToDevice));
+    if (!emit.empty()) SPT_HIP(c, hipMemcpy(c->d_emit, emit.data(), sizeof(DevEmitter) * emit.size(), hipMemcpyHostToDevice));
+    if (node_bytes) SPT_HIP(c, hipMemcpy(c->d_nodes, node_data, node_bytes, hipMemcpyHostToDevice));
     c->n_prims = n_prims;
     c->n_mats = n_mats;
     c->n_emit = (uint32_t)emit.size();
@@ -1055,55 +1023,36 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     // failed call leaves the device scene, the stacks and their sizes exactly as they were.
     const uint32_t stride = bvh_stack_stride(stack_need);
     const size_t stack_bytes = (size_t)kBvhStackEntryBytes * stride * 64u * kMaxResidentWaves * c->cu_count;
-    float4* grown_nodes = nullptr;
-    float4* new_emit = nullptr;
-    void* grown_stack = nullptr;
-    auto release = [&]() {
-        free_dev(grown_nodes);
-        free_dev(new_emit);
-        free_dev(grown_stack);
-    };
-    hipError_t e = hipSuccess;
-    if (node_bytes > c->node_alloc) e = hipMalloc(&grown_nodes, node_bytes);
-    if (e == hipSuccess && emit.size() != c->n_emit && !emit.empty())  // (an edit can make an emitter degenerate, or not)
-        e = hipMalloc(&new_emit, sizeof(DevEmitter) * emit.size());
-    if (e == hipSuccess && stride > c->bvh_stack_stride) e = hipMalloc(&grown_stack, stack_bytes);  // deeper than allocated
-    if (e != hipSuccess) {
-        release();
-        (void)hipGetLastError();
-        return fail(c, SPT_ERR_HIP, std::string("spt_update_prims: allocation failed: ") + hipGetErrorString(e));
-    }
+    Dev<float4> grown_nodes, new_emit;  // (what is not swapped in goes when the call returns)
+    Dev<uint8_t> grown_stack;
+    const size_t node_elems = node_bytes / sizeof(float4);
+    const bool emit_changed = emit.size() != c->n_emit;  // (an edit can make an emitter degenerate, or not)
+    if ((node_elems > c->d_nodes.size() && !grown_nodes.alloc(node_elems)) ||
+        (emit_changed && !new_emit.alloc(float4s<DevEmitter>(emit.size()))) ||
+        (stride > c->bvh_stack_stride && !grown_stack.alloc(stack_bytes)))  // deeper than allocated
+        return fail(c, SPT_ERR_HIP, "spt_update_prims: allocation failed");
     // the copies into the buffers that stay (new buffers are swapped in only after theirs succeeded)
     float4* nodes_dst = grown_nodes ? grown_nodes : c->d_nodes;
-    float4* emit_dst = emit.size() != c->n_emit ? new_emit : c->d_emit;
-    e = hipMemcpy(nodes_dst, node_data, node_bytes, hipMemcpyHostToDevice);
+    float4* emit_dst = emit_changed ? new_emit : c->d_emit;
+    hipError_t e = hipMemcpy(nodes_dst, node_data, node_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && !emit.empty()) e = hipMemcpy(emit_dst, emit.data(), sizeof(DevEmitter) * emit.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && n)
         e = hipMemcpy(c->d_prims + 4u * lo, &dp[lo], sizeof(DevPrim) * (hi - lo + 1u), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         // a copy into the kept buffers may have landed partly: the device no longer matches the host
         // mirror, so the scene is dropped (the next render fails with SPT_ERR_NO_SCENE, not wrong bits)
-        release();
         (void)hipGetLastError();
         free_scene(c);
         c->has_scene = false;
         return fail(c, SPT_ERR_HIP, std::string("spt_update_prims: upload failed: ") + hipGetErrorString(e));
     }
-    if (grown_nodes) {
-        free_dev(c->d_nodes);
-        c->d_nodes = grown_nodes;
-        c->node_alloc = node_bytes;
-    }
-    if (emit.size() != c->n_emit) {
-        free_dev(c->d_emit);
-        c->d_emit = new_emit;
-    }
+    if (grown_nodes) c->d_nodes.swap(grown_nodes);
+    if (emit_changed) c->d_emit.swap(new_emit);
     c->n_emit = (uint32_t)emit.size();
     c->n_emit_spheres = sphere_emitters(emit);
     c->n_dev_nodes = (uint32_t)(node_bytes / kDevNodeBytes);
     if (grown_stack) {
-        free_dev(c->bvh_stack);
-        c->bvh_stack = grown_stack;
+        c->bvh_stack.swap(grown_stack);
         c->bvh_stack_stride = stride;
         c->stack_bytes = stack_bytes;
     }
@@ -1149,38 +1098,30 @@ int spt_configure(spt_ctx* c, const spt_config* cfg) {
     c->pixels = pixels;
     c->frames_per_pass = fpp;
     c->sub_cap = cap;
+    const size_t qn = (size_t)cap * c->n_sub;
+    bool ok = true;
     if (realloc) {
+        // not configured until every buffer of the new size exists: a failed allocation leaves a ctx that
+        // answers SPT_ERR_NOT_CONFIGURED, never one whose next launch runs over buffers that are not there
+        c->configured = false;
         free_buffers(c);
         c->sub_alloc = c->n_sub;
-        const size_t qn = (size_t)cap * c->n_sub;
-        if (qn) {
-            for (int k = 0; k < 2; ++k) {
-                SPT_HIP(c, hipMalloc(&c->q_o[k], sizeof(float4) * qn));
-                SPT_HIP(c, hipMalloc(&c->q_d[k], sizeof(float4) * qn));
-                SPT_HIP(c, hipMalloc(&c->q_t[k], sizeof(float4) * qn));
-            }
-            SPT_HIP(c, hipMalloc(&c->hit, sizeof(float2) * qn));
-            SPT_HIP(c, hipMalloc(&c->radiance, sizeof(float4) * (size_t)fpp * pixels));
-        }
-        SPT_HIP(c, hipMalloc(&c->accum, sizeof(float4) * std::max<size_t>(pixels, 1)));
-        SPT_HIP(c, hipMalloc(&c->hit_cache, sizeof(float2) * std::max<size_t>(pixels, 1)));
-        SPT_HIP(c, hipMalloc(&c->chunk_cost, sizeof(uint16_t) * std::max<size_t>(pixels, 1)));
-        SPT_HIP(c, hipMalloc(&c->chunk_order, sizeof(uint32_t) * std::max<size_t>(pixels, 1)));
-        if (kFrameHitCache >= 2) {
-            SPT_HIP(c, hipMalloc(&c->live_rec, sizeof(uint4) * std::max<size_t>(pixels, 1)));
-            SPT_HIP(c, hipMalloc(&c->sky_pix, sizeof(uint32_t) * std::max<size_t>(pixels, 1)));
-            SPT_HIP(c, hipMalloc(&c->list_counts, sizeof(uint32_t) * (2 + (pixels + kBlock - 1) / kBlock)));
-        }
-        SPT_HIP(c, hipMalloc(&c->resolved, sizeof(uint32_t) * std::max<size_t>(pixels, 1)));
+        const size_t px = std::max<size_t>(pixels, 1);
+        for (int k = 0; k < 2; ++k) ok = ok && c->q_o[k].alloc(qn) && c->q_d[k].alloc(qn) && c->q_t[k].alloc(qn);
+        ok = ok && c->hit.alloc(qn) && c->radiance.alloc(qn ? (size_t)fpp * pixels : 0u) && c->accum.alloc(px) &&
+             c->hit_cache.alloc(px) && c->chunk_cost.alloc(px) && c->chunk_order.alloc(px);
+        if (kFrameHitCache >= 2)
+            ok = ok && c->live_rec.alloc(px) && c->sky_pix.alloc(px) && c->list_counts.alloc(2 + (pixels + kBlock - 1) / kBlock);
+        ok = ok && c->resolved.alloc(px);
     }
     c->derived.drop(Change::Configuration);
-    const size_t qn = (size_t)cap * c->n_sub;
-    if ((cfg->flags & SPT_FLAG_SORTED_RAYS) && qn && !c->ray_perm) {  // the sorted schedule's buffers
-        SPT_HIP(c, hipMalloc(&c->ray_keys, sizeof(uint16_t) * qn));
-        SPT_HIP(c, hipMalloc(&c->ray_perm, sizeof(uint32_t) * qn));
-        SPT_HIP(c, hipMalloc(&c->ray_bins, sizeof(uint32_t) * 4096));
-        SPT_HIP(c, hipMalloc(&c->ray_cursor, sizeof(uint32_t) * 4097));
-        SPT_HIP(c, hipMemset(c->ray_bins, 0, sizeof(uint32_t) * 4096));
+    if ((cfg->flags & SPT_FLAG_SORTED_RAYS) && qn && !c->ray_perm)  // the sorted schedule's buffers
+        ok = ok && c->ray_keys.alloc(qn) && c->ray_perm.alloc(qn) && c->ray_bins.alloc(4096) && c->ray_cursor.alloc(4097) &&
+             hipMemset(c->ray_bins, 0, sizeof(uint32_t) * 4096) == hipSuccess;
+    if (!ok) {  // (whichever it was: nothing of a configuration is left)
+        c->configured = false;
+        free_buffers(c);
+        return fail(c, SPT_ERR_HIP, "spt_configure: allocation failed");
     }
     c->configured = true;
     prefetch_flat(c);  // (a flat scene's kernels are compiled for the configuration too)
@@ -1212,18 +1153,10 @@ int spt_get_frame_count(const spt_ctx* c, uint32_t* fc) {
 // allocation is no error: the launches keep computing bounce 0 themselves.
 static int build_view_lists(spt_ctx* c, const PassParams& p) {
     const size_t pixels = std::max<size_t>(c->pixels, 1);
-    if (!c->view_live) {
-        const size_t blocks = (pixels + kBlock - 1) / kBlock;
-        if (hipMalloc(&c->view_live, sizeof(float4) * 3 * pixels) != hipSuccess ||
-            hipMalloc(&c->view_const, sizeof(float4) * pixels) != hipSuccess ||
-            hipMalloc(&c->view_counts, sizeof(uint32_t) * (2 + blocks)) != hipSuccess) {
-            (void)hipGetLastError();
-            free_dev(c->view_live);
-            free_dev(c->view_const);
-            free_dev(c->view_counts);
-            c->derived.produced(kViewNoMemory);
-            return SPT_OK;
-        }
+    const size_t blocks = (pixels + kBlock - 1) / kBlock;
+    if (!c->view_live.ensure(3 * pixels) || !c->view_const.ensure(pixels) || !c->view_counts.ensure(2 + blocks)) {
+        c->derived.produced(kViewNoMemory);  // (the launches never take lists while it is set: a part of them may stay)
+        return SPT_OK;
     }
     launch_view_lists(p, c->view_live, c->view_const, c->view_counts, c->view_counts + 2, on_stream(c));
     SPT_HIP(c, hipGetLastError());
@@ -1253,15 +1186,8 @@ static int build_view_lists(spt_ctx* c, const PassParams& p) {
 // (the launch runs unsplit).
 static bool half_buffers(spt_ctx* c) {
     const size_t n = (size_t)c->pixels / 2u + 64u;
-    for (ViewHalf& h : c->half) {
-        if (h.cost && h.order) continue;
-        if (hipMalloc(&h.cost, sizeof(uint16_t) * n) != hipSuccess || hipMalloc(&h.order, sizeof(uint32_t) * n) != hipSuccess) {
-            (void)hipGetLastError();
-            free_dev(h.cost);
-            free_dev(h.order);
-            return false;
-        }
-    }
+    for (auto& h : c->half_mem)
+        if (!h.cost.ensure(n) || !h.order.ensure(n)) return false;
     return true;
 }
 
@@ -1293,8 +1219,8 @@ static int launch_paths_split(spt_ctx* c, PassParams p, const ViewPlan& whole, b
         p.work = vh.work + vh.work_parity * kWorkWords;
         p.work_next = vh.work + (vh.work_parity ^ 1u) * kWorkWords;
         vh.work_parity ^= 1u;
-        p.chunk_cost = vh.cost;
-        p.chunk_order = vh.order;
+        p.chunk_cost = c->half_mem[h].cost;
+        p.chunk_order = c->half_mem[h].order;
         p.chunk_order_key = &c->derived.half_order_key[h];
         if (timed) {
             if (take_events(c, ev[n_ev], 4) != SPT_OK) return SPT_ERR_HIP;
@@ -1675,12 +1601,12 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
         return fail(c, SPT_ERR_INVALID, "environment map: bad size");
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    free_dev(c->d_env);
+    c->d_env.reset();
     c->env_w = c->env_h = 0;
     if (rgba) {
-        const size_t bytes = sizeof(float4) * (size_t)width * height;
-        SPT_HIP(c, hipMalloc(&c->d_env, bytes));
-        SPT_HIP(c, hipMemcpy(c->d_env, rgba, bytes, hipMemcpyHostToDevice));
+        const size_t texels = (size_t)width * height;
+        if (!c->d_env.alloc(texels)) return fail(c, SPT_ERR_HIP, "spt_set_env_map: allocation failed");
+        SPT_HIP(c, hipMemcpy(c->d_env, rgba, sizeof(float4) * texels, hipMemcpyHostToDevice));
         c->env_w = width;
         c->env_h = height;
     }
@@ -1811,23 +1737,14 @@ const char* denoise_params_error(const spt_denoise_params& p) {
     if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_denoise_params: reserved must be 0";
     return nullptr;
 }
-int alloc_image(spt_ctx* c, float4*& img, size_t pixels, const char* who) {
-    if (img) return SPT_OK;
-    if (hipMalloc(&img, sizeof(float4) * pixels) != hipSuccess) {
-        img = nullptr;
-        (void)hipGetLastError();
-        return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
-    }
-    return SPT_OK;
-}
 // the images are those of the current scene, camera and configuration (rendered now if they are not)
 int ensure_features(spt_ctx* c) {
     if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
     if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "features before spt_configure");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->derived.valid(kFeatures) || c->pixels == 0) return SPT_OK;
-    for (float4** img : {&c->feat_a, &c->feat_b, &c->feat_albedo})
-        if (const int rc = alloc_image(c, *img, c->pixels, "spt_render_features"); rc != SPT_OK) return rc;
+    for (Dev<float4>* img : {&c->feat_a, &c->feat_b, &c->feat_albedo})
+        if (const int rc = ensure_buf(c, *img, c->pixels, "spt_render_features"); rc != SPT_OK) return rc;
     launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, on_stream(c));
     SPT_HIP(c, hipGetLastError());
     c->derived.produced(kFeatures);
@@ -1880,8 +1797,8 @@ static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt
     if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise: image taller than 262140 rows");
     const int rc = ensure_features(c);
     if (rc != SPT_OK || c->pixels == 0) return rc;
-    for (float4*& img : c->dn)
-        if (const int rc = alloc_image(c, img, c->pixels, "spt_denoise"); rc != SPT_OK) return rc;
+    for (Dev<float4>& img : c->dn)
+        if (const int rc = ensure_buf(c, img, c->pixels, "spt_denoise"); rc != SPT_OK) return rc;
     c->derived.begin(kDenoised);
     const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
     for (uint32_t l = 0; l < p.levels; ++l) {
@@ -2030,7 +1947,7 @@ int spt_history_capture(spt_ctx* c, uint32_t frame_count) {
     if (!c) return SPT_ERR_INVALID;
     if (const int rc = history_ready(c, "spt_history_capture", true); rc != SPT_OK) return rc;
     if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    if (const int rc = alloc_image(c, c->hist_view, 3 * (size_t)c->pixels, "spt_history_capture"); rc != SPT_OK) return rc;
+    if (const int rc = ensure_buf(c, c->hist_view, 3 * (size_t)c->pixels, "spt_history_capture"); rc != SPT_OK) return rc;
     c->derived.begin(kCapturedView);
     const int layout = c->hist_layout >= 0 ? c->hist_layout : kHistoryDefault;
     launch_history_capture(layout, c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->feat_a, c->feat_b,
@@ -2049,14 +1966,14 @@ int spt_reproject(spt_ctx* c, const spt_reproject_params* params) {
     if (const char* msg = reproject_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
     if (const int rc = history_ready(c, "spt_reproject", true); rc != SPT_OK) return rc;
     if (!c->derived.valid(kCapturedView)) return fail(c, SPT_ERR_INVALID, "no captured view: spt_history_capture first");
-    if (const int rc = alloc_image(c, c->hist, c->pixels, "spt_reproject"); rc != SPT_OK) return rc;
+    if (const int rc = ensure_buf(c, c->hist, c->pixels, "spt_reproject"); rc != SPT_OK) return rc;
     c->derived.begin(kHistory);
     const uint32_t n_mats = (uint32_t)c->h_mats.size();
     if (c->bsdf && !c->derived.valid(kReusable)) {
         // (spt_set_material_models drained the stream before it changed the models: nothing reads the old words)
         std::vector<uint32_t> words(n_mats);
         for (uint32_t m = 0; m < n_mats; ++m) words[m] = c->h_models[m].kind == SPT_MAT_DIFFUSE ? 1u : 0u;
-        if (!c->d_reusable) SPT_HIP(c, hipMalloc(&c->d_reusable, sizeof(uint32_t) * n_mats));
+        if (const int rc = ensure_buf(c, c->d_reusable, n_mats, "spt_reproject"); rc != SPT_OK) return rc;
         SPT_HIP(c, hipMemcpy(c->d_reusable, words.data(), sizeof(uint32_t) * n_mats, hipMemcpyHostToDevice));
         c->derived.produced(kReusable);
     }
@@ -2081,7 +1998,7 @@ int spt_history_blend(spt_ctx* c, uint32_t frame_count) {
     if (!c) return SPT_ERR_INVALID;
     if (const int rc = history_ready(c, "spt_history_blend", false); rc != SPT_OK) return rc;
     if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    if (const int rc = alloc_image(c, c->blend, c->pixels, "spt_history_blend"); rc != SPT_OK) return rc;
+    if (const int rc = ensure_buf(c, c->blend, c->pixels, "spt_history_blend"); rc != SPT_OK) return rc;
     c->derived.begin(kBlended);
     launch_history_blend(c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->blend, c->pixels, on_stream(c));
     SPT_HIP(c, hipGetLastError());
@@ -2192,9 +2109,9 @@ const float4* display_source(spt_ctx* c, uint32_t image, uint32_t frame_count, f
 }
 
 // counts = the histogram of img[0..n) / divisor, waited for
-int meter_image(spt_ctx* c, const float4* img, uint64_t n, float divisor, uint32_t* counts) {
+int meter_image(spt_ctx* c, const char* who, const float4* img, uint64_t n, float divisor, uint32_t* counts) {
     SPT_HIP(c, hipSetDevice(c->device));
-    if (!c->meter_counts) SPT_HIP(c, hipMalloc(&c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS));
+    if (const int rc = ensure_buf(c, c->meter_counts, SPT_METER_BINS, who); rc != SPT_OK) return rc;
     SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_METER_BINS, on_stream(c)));
     launch_meter(c->meter_form >= 0 ? c->meter_form : meter_default_form(), img, n, divisor, c->meter_counts, on_stream(c));
     SPT_HIP(c, hipGetLastError());
@@ -2218,7 +2135,7 @@ int spt_meter_luminance(spt_ctx* c, uint32_t image, uint32_t frame_count, uint32
     int rc = SPT_OK;
     const float4* img = display_source(c, image, frame_count, &divisor, &rc);
     if (!img) return rc;
-    return meter_image(c, img, c->pixels, divisor, counts);
+    return meter_image(c, "spt_meter_luminance", img, c->pixels, divisor, counts);
 }
 
 int spt_meter_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixels, float divisor,
@@ -2226,7 +2143,7 @@ int spt_meter_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixel
     if (!c || !device_rgba || !counts) return SPT_ERR_INVALID;
     if (n_pixels == 0) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: no pixels");
     if (!divisor_ok(divisor)) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: divisor must be finite and > 0");
-    return meter_image(c, (const float4*)device_rgba, n_pixels, divisor, counts);
+    return meter_image(c, "spt_meter_device_image", (const float4*)device_rgba, n_pixels, divisor, counts);
 }
 
 int spt_resolve_display_rgba8(spt_ctx* c, uint32_t image, uint32_t frame_count, const spt_display* display,
@@ -2252,16 +2169,10 @@ int spt_resolve_display_device_image(spt_ctx* c, const void* device_rgba, uint64
     const spt_display d = *display;
     if (const char* msg = display_error(d)) return fail(c, SPT_ERR_INVALID, msg);
     SPT_HIP(c, hipSetDevice(c->device));
-    if (c->display_stage_pixels < n_pixels) {
+    if (c->display_stage.size() < n_pixels) {
         SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (no earlier resolve may still read the old one)
-        free_dev(c->display_stage);
-        c->display_stage_pixels = 0;
-        if (hipMalloc(&c->display_stage, sizeof(uint32_t) * n_pixels) != hipSuccess) {
-            c->display_stage = nullptr;
-            (void)hipGetLastError();
+        if (!c->display_stage.ensure_at_least(n_pixels))
             return fail(c, SPT_ERR_HIP, "spt_resolve_display_device_image: allocation failed");
-        }
-        c->display_stage_pixels = n_pixels;
     }
     launch_display((const float4*)device_rgba, n_pixels, divisor, d, c->display_stage, on_stream(c));
     SPT_HIP(c, hipGetLastError());
@@ -2331,10 +2242,10 @@ int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const 
 
 namespace {
 // counts and the e2 image (may be nullptr) of width x height device moments, waited for
-int noise_meter_image(spt_ctx* c, const float4* state, uint32_t width, uint32_t height, uint32_t batches, float W,
-                      const spt_noise_params& p, uint32_t* counts, float* e2) {
+int noise_meter_image(spt_ctx* c, const char* who, const float4* state, uint32_t width, uint32_t height, uint32_t batches,
+                      float W, const spt_noise_params& p, uint32_t* counts, float* e2) {
     SPT_HIP(c, hipSetDevice(c->device));
-    if (!c->meter_counts) SPT_HIP(c, hipMalloc(&c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS));
+    if (const int rc = ensure_buf(c, c->meter_counts, SPT_METER_BINS, who); rc != SPT_OK) return rc;
     SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS, on_stream(c)));
     launch_noise_meter(state, width, height, (int)p.radius, noise_inv(batches, W), p.dark_floor, c->meter_counts, e2, on_stream(c));
     SPT_HIP(c, hipGetLastError());
@@ -2352,7 +2263,7 @@ int spt_noise_update(spt_ctx* c, uint32_t frame_count) {
     if (frame_count > (1u << 24)) return fail(c, SPT_ERR_INVALID, "spt_noise_update: more than 2^24 frames");
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t pixels = std::max<size_t>(c->pixels, 1);
-    if (!c->noise_state) SPT_HIP(c, hipMalloc(&c->noise_state, sizeof(float4) * pixels));
+    if (const int rc = ensure_buf(c, c->noise_state, pixels, "spt_noise_update"); rc != SPT_OK) return rc;
     if (c->noise_batches == 0) SPT_HIP(c, hipMemsetAsync(c->noise_state, 0, sizeof(float4) * pixels, on_stream(c)));
     const float w = (float)(frame_count - c->noise_frames);
     launch_noise_update(c->accum, c->noise_state, c->pixels, noise_batch(w, c->noise_W), on_stream(c));
@@ -2384,8 +2295,8 @@ int spt_noise_meter(spt_ctx* c, const spt_noise_params* params, uint32_t counts[
         std::memset(counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS);
         return SPT_OK;
     }
-    if (!c->noise_e2) SPT_HIP(c, hipMalloc(&c->noise_e2, sizeof(float) * c->pixels));
-    const int rc = noise_meter_image(c, c->noise_state, c->cfg.width, c->rows, c->noise_batches, c->noise_W, p, counts, c->noise_e2);
+    if (const int rc = ensure_buf(c, c->noise_e2, c->pixels, "spt_noise_meter"); rc != SPT_OK) return rc;
+    const int rc = noise_meter_image(c, "spt_noise_meter", c->noise_state,c->cfg.width, c->rows, c->noise_batches, c->noise_W, p, counts, c->noise_e2);
     c->noise_metered = rc == SPT_OK;
     return rc;
 }
@@ -2425,7 +2336,7 @@ int spt_noise_meter_device_image(spt_ctx* c, const void* device_moments, uint32_
     const spt_noise_params p = params ? *params : kNoiseDefaults;
     if (const char* msg = noise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
     if (const char* msg = noise_image_error(width, height, batches, frames)) return fail(c, SPT_ERR_INVALID, msg);
-    return noise_meter_image(c, (const float4*)device_moments, width, height, batches, frames, p, counts, (float*)device_e2);
+    return noise_meter_image(c, "spt_noise_meter_device_image", (const float4*)device_moments, width, height, batches, frames, p, counts, (float*)device_e2);
 }
 
 int spt_camera_look_at(const float eye[3], const float target[3], const float up[3], float vfov_degrees,
@@ -2708,15 +2619,11 @@ int spt_set_tuning(spt_ctx* c, const spt_tuning* t) {
     const uint32_t n_sub = t->subqueues ? t->subqueues : c->cu_count * 12u;
     if (n_sub != c->n_sub) {  // the wavefront schedule's per-sub-queue counters: the new buffer first,
         // swapped in only once it exists (a failed allocation leaves the ctx as it was)
-        uint32_t* counts = nullptr;
-        const size_t bytes = sizeof(uint32_t) * 2 * (kMaxBounces + 1) * n_sub;
-        SPT_HIP(c, hipMalloc(&counts, bytes));
-        if (hipMemset(counts, 0, bytes) != hipSuccess) {
-            (void)hipFree(counts);
+        Dev<uint32_t> counts;
+        if (!counts.alloc((size_t)2 * (kMaxBounces + 1) * n_sub)) return fail(c, SPT_ERR_HIP, "spt_set_tuning: allocation failed");
+        if (hipMemset(counts, 0, sizeof(uint32_t) * counts.size()) != hipSuccess)
             return fail(c, SPT_ERR_HIP, "spt_set_tuning: hipMemset of the sub-queue counters failed");
-        }
-        free_dev(c->counts);
-        c->counts = counts;
+        c->counts.swap(counts);
         c->n_sub = n_sub;
     }
     c->fused_override = t->fused;
@@ -2786,15 +2693,14 @@ int gather_check(spt_ctx* c, void* root_image, const char* what, uint32_t& rows_
 
 // gather_buf of `need` floats, its padding rows zeroed once (every copy into it writes the same rows)
 int gather_buffer(spt_ctx* c, size_t need) {
-    if (c->gather_elems == need) return SPT_OK;
+    const size_t texels = need / 4;  // (a shard is whole pixels)
+    if (c->gather_buf.size() == texels) return SPT_OK;
     if (c->gather_pending) SPT_HIP(c, hipStreamWaitEvent(on_stream(c), c->gather_done, 0));
     SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (an earlier gather may still read the old buffer)
-    free_dev(c->gather_buf);
-    if (need) {
-        SPT_HIP(c, hipMalloc(&c->gather_buf, sizeof(float) * need));
-        SPT_HIP(c, hipMemsetAsync(c->gather_buf, 0, sizeof(float) * need, on_stream(c)));
-    }
-    c->gather_elems = need;
+    // exactly the size, not the scratch's "at least": another size is another layout, whose padding rows are zero
+    // only in a buffer zeroed for it
+    if (!c->gather_buf.alloc(texels)) return fail(c, SPT_ERR_HIP, "spt_gather_image: allocation failed");
+    if (texels) SPT_HIP(c, hipMemsetAsync(c->gather_buf, 0, sizeof(float4) * texels, on_stream(c)));
     return SPT_OK;
 }
 }  // namespace

@@ -24,10 +24,10 @@ enum Derived : uint32_t {     // the cached results, a bit each
 };
 
 enum class Change {  // what changed: dropped by the entry point that changed it
-    Scene,           // free_scene: spt_set_scene, spt_destroy, a failed upload
+    Scene,           // with the scene's memory (spt_capi.hip SceneMem): spt_set_scene, spt_destroy, a failed upload
     Prims,           // spt_update_prims (a flat scene goes on through spt_set_scene: Scene too)
     Configuration,   // spt_configure, always
-    Buffers,         // free_buffers: a reallocating spt_configure, spt_destroy
+    Buffers,         // with the configuration's memory (ConfigMem): a reallocating spt_configure, spt_destroy
     Sky,             // spt_set_env_map
     Camera,          // spt_set_camera
     Lens,            // spt_set_camera_lens
