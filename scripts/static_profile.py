@@ -10,7 +10,11 @@ Compiles the C2 shape-specialized flat kernel and the two BVH k_paths instantiat
 prints, per section of the step loop, the VALU / SALU / LDS / scalar-memory / vector-memory
 instruction counts (the code the compiler placed after a marker, up to the next one in program
 order; the sections of divergent branches interleave, so read the counts as the code size of each
-part, not as executed instructions)."""
+part, not as executed instructions). Of the VALU count it also gives the fp64 instructions (any *_f64 operand
+or result, the conversions included) and the fp32 transcendentals (v_rcp / v_rsq / v_sqrt / v_exp / v_log / v_sin /
+v_cos), and an issue-cycle-weighted total `wt` = VALU + fp64 + transcendental: each of the two kinds counted
+twice, the rest once (the weights are the published MI355X figures' — fp64 vector at half the fp32
+rate, a transcendental's issue cost twice a plain instruction's — not measured on this kernel)."""
 import collections
 import os
 import re
@@ -59,6 +63,18 @@ def classify(op):
     return "other"
 
 
+TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_")
+
+
+def valu_kind(op):
+    """'f64', 'trans' or None (a plain VALU instruction); an fp64 transcendental counts as fp64."""
+    if "_f64" in op:
+        return "f64"
+    if op.startswith(TRANS):
+        return "trans"
+    return None
+
+
 def main():
     flags = sys.argv[1:]
     with tempfile.TemporaryDirectory() as td:
@@ -91,13 +107,19 @@ def main():
             if not s or s.startswith((";", ".")) or s.endswith(":"):
                 continue
             cnt[sec][classify(s.split()[0])] += 1
+            if classify(s.split()[0]) == "valu" and valu_kind(s.split()[0]):
+                cnt[sec][valu_kind(s.split()[0])] += 1
         if not cnt:
             continue
         print(kname)
         tot = sum(c["valu"] for c in cnt.values())
         for sec, c in cnt.items():
             print(f"  {sec:26s} valu {c['valu']:5d} ({100.0 * c['valu'] / max(tot, 1):4.1f} %)  salu {c['salu']:4d}  "
-                  f"lds {c['lds']:3d}  smem {c['smem']:3d}  vmem {c['vmem']:3d}  wait {c['wait']:3d}")
+                  f"lds {c['lds']:3d}  smem {c['smem']:3d}  vmem {c['vmem']:3d}  wait {c['wait']:3d}  "
+                  f"f64 {c['f64']:3d}  trans {c['trans']:3d}  wt {c['valu'] + c['f64'] + c['trans']:5d}")
+        loop = [c for sec, c in cnt.items() if sec != "prologue"]
+        v, f, t = (sum(c[k] for c in loop) for k in ("valu", "f64", "trans"))
+        print(f"  {'step loop (no prologue)':26s} valu {v:5d}  f64 {f:3d}  trans {t:3d}  wt {v + f + t:5d} ({(v + f + t) / max(v, 1):.3f} x)")
 
 
 if __name__ == "__main__":

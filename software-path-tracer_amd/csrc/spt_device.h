@@ -365,8 +365,11 @@ __device__ __forceinline__ double fma_sc(double a, double b, double c) {
 #endif
 }
 
+// The unselected form: sr = sin(r), cr = cos(r) of the reduced argument and the quadrant q = k & 3, so that
+// sin(phi), cos(phi) are (sr, cr), (cr, -sr), (-sr, -cr), (-cr, sr) for q = 0..3. sincos_2pi selects them as
+// doubles; bounce_dir_xy's kLateQuadrant form selects after its products and conversions.
 template <bool kSmemCoef = false>
-__host__ __device__ inline void sincos_2pi(double phi, double& s, double& c) {
+__host__ __device__ inline void sincos_2pi_reduced(double phi, double& sr_out, double& cr_out, int& q_out) {
     constexpr double kPio2Hi = 1.57079632679489655800e+00;
     constexpr double kPio2Lo = 6.12323399573676603587e-17;
     constexpr double k2OverPi = 6.36619772367581382433e-01;
@@ -409,12 +412,21 @@ __host__ __device__ inline void sincos_2pi(double phi, double& s, double& c) {
     pc = SPT_HORNER(pc, 14);
 #undef SPT_HORNER
     const double cr = __builtin_fma(w, pc, 1.0);
-    const int q = ((int)k) & 3;
+    sr_out = sr;
+    cr_out = cr;
+    q_out = ((int)k) & 3;
+#undef SPT_CF
+}
+
+template <bool kSmemCoef = false>
+__host__ __device__ inline void sincos_2pi(double phi, double& s, double& c) {
+    double sr, cr;
+    int q;
+    sincos_2pi_reduced<kSmemCoef>(phi, sr, cr, q);
     const double a = (q & 1) ? cr : sr;  // sin: sr, cr, -sr, -cr
     const double b = (q & 1) ? sr : cr;  // cos: cr, -sr, -cr, sr
     s = (q & 2) ? -a : a;
     c = ((q + 1) & 2) ? -b : b;
-#undef SPT_CF
 }
 
 // Correctly rounded sqrtf for x = 0 and finite x >= 2^-96: hipcc's sqrtf sequence (hardware
@@ -435,24 +447,54 @@ __host__ __device__ __forceinline__ float sqrt_unit(float x) {
 #endif
 }
 
-template <bool kSmemCoef = false>
+// The tail of bounce_dir_frame: x = (float)((double)sin_t * cos(phi)), y = (float)((double)sin_t * sin(phi)).
+// kLateQuadrant (k_paths' sampling site under the range bit): the quadrant's swap and signs are applied to the two
+// converted floats instead of to the doubles sin and cos. The same bits for every finite sin_t and phi in [0, 2 pi]:
+//   - The swap only chooses which of sr, cr a product takes, so it commutes with forming both products.
+//   - A double product's and a conversion's rounding is round-to-nearest-even on the magnitude, the sign carried
+//     apart: fl(s * (-a)) = -fl(s * a) and (float)(-v) = -(float)v for every finite s, a, v — zeros included
+//     (s * (-a) is -0 exactly when s * a is +0), subnormal results included (the flush or not of a result does
+//     not look at its sign). So (float)(sin_t * (-a)) and -(float)(sin_t * a) are the same word.
+//   - No NaN arises (sin_t in [0, 1], |sr|, |cr| <= 1: the products are finite), so no payload or sign of a NaN
+//     is in question.
+// tests/cpp/test_quadrant_select.cpp compares the two forms on the host build for every quadrant and the floats
+// around each multiple of pi / 2; the 32-bit select costs half the instructions of the 64-bit one.
+template <bool kSmemCoef = false, bool kLateQuadrant = false>
+__host__ __device__ __forceinline__ void bounce_dir_xy(float sin_t, float phi, float& x, float& y) {
+#ifdef SPT_EXPERIMENT_FP32_TRIG  // measurement-only build: prices the fp64 trig; NOT reference numerics
+    float spf, cpf;
+    sincosf(phi, &spf, &cpf);
+    x = sin_t * cpf;
+    y = sin_t * spf;
+#else
+    if constexpr (kLateQuadrant) {
+        double sr, cr;
+        int q;
+        sincos_2pi_reduced<kSmemCoef>((double)phi, sr, cr, q);
+        const float fs = (float)((double)sin_t * sr);
+        const float fc = (float)((double)sin_t * cr);
+        const float a = (q & 1) ? fc : fs;  // sin: sr, cr, -sr, -cr
+        const float b = (q & 1) ? fs : fc;  // cos: cr, -sr, -cr, sr
+        y = (q & 2) ? -a : a;
+        x = ((q + 1) & 2) ? -b : b;
+    } else {
+        double sp, cp;
+        sincos_2pi<kSmemCoef>((double)phi, sp, cp);
+        x = (float)((double)sin_t * cp);
+        y = (float)((double)sin_t * sp);
+    }
+#endif
+}
+
+template <bool kSmemCoef = false, bool kLateQuadrant = false>
 __host__ __device__ __forceinline__ F3 bounce_dir_frame(F3 n, F3 t, uint32_t& state) {
     const float u1 = random_float(state);
     const float u2 = random_float(state);
     const float cos_t = sqrt_unit(u1);
     const float sin_t = sqrt_unit(1.0f - u1);
     const float phi = 2.0f * kPiF * u2;
-#ifdef SPT_EXPERIMENT_FP32_TRIG  // measurement-only build: prices the fp64 trig; NOT reference numerics
-    float spf, cpf;
-    sincosf(phi, &spf, &cpf);
-    const float x = sin_t * cpf;
-    const float y = sin_t * spf;
-#else
-    double sp, cp;
-    sincos_2pi<kSmemCoef>((double)phi, sp, cp);
-    const float x = (float)((double)sin_t * cp);
-    const float y = (float)((double)sin_t * sp);
-#endif
+    float x, y;
+    bounce_dir_xy<kSmemCoef, kLateQuadrant>(sin_t, phi, x, y);
     const float z = cos_t;
     const F3 b = cross3(n, t);
     return F3{(x * t.x + y * b.x) + z * n.x, (x * t.y + y * b.y) + z * n.y, (x * t.z + y * b.z) + z * n.z};

@@ -1085,6 +1085,85 @@ __device__ __forceinline__ bool shade_hit(const float4* __restrict__ prims, cons
     return contributes;
 }
 
+// shade_hit's two cases as k_paths' step takes them under the range bit (flat scenes' records, no NEE, no
+// material models): each assigns the path's own T, L, o and n in place, so nothing — no `add`, `alive` or
+// `contributes` — is merged behind the branch on best_k. The same operations in the same order otherwise, with one
+// select dropped:
+//
+// L + T * emi instead of `emi.w != 0 ? L + T * emi : L`. Where the flag is set the two are the same expression.
+// Where it is not, the record's three emission words are +0 (prepare_materials writes them; flat_ranges_ok has
+// checked every emission component >= +0 with the sign bit clear, the hand-out relies on the same), and then:
+//   - T is finite: every component is 0 or in [2^-40, 1] (rr_divide_ranged's induction: products of albedos
+//     <= 1, divided by p >= the component), never NaN or inf. So T * (+0) = +0, not NaN.
+//   - L is never -0. It starts as a record's emission (>= +0, sign clear) and each term added to it is T * emi
+//     with T >= +0, emi >= +0 finite (the product <= emi: no overflow, and its sign bit is clear) or T * sky at
+//     a path's end. x + y of two values that are >= +0 with their sign bits clear is >= +0 with its sign bit
+//     clear (round to nearest gives -0 only for (-0) + (-0)). So L + (+0) = L bit for bit.
+// (`contributes` is still evaluated for the counting form's s_rmw; nothing else reads it.)
+//
+// rr_divide_ranged for a throughput divided in place: div_ref with its last step written as the three-address
+// v_fma_f32. Left to itself the compiler picks the two-address v_fmac_f32 (q1 += r1 * y), whose result lands in
+// q1's register, not in the loop-carried T's: three moves after every roulette. The same fused operation on the
+// same operands, so the same bits (as spt_device.h fma_sc).
+__device__ __forceinline__ float div_ref_to(float n, RcpRef r) {
+    const float q0 = n * r.y;
+    const float r0 = __builtin_fmaf(-r.s, q0, n);
+    const float q1 = __builtin_fmaf(r0, r.y, q0);
+    const float r1 = __builtin_fmaf(-r.s, q1, n);
+    float q;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(q) : "v"(r1), "v"(r.y), "v"(q1));
+    return q;
+}
+
+// The hit case: returns whether the path continues; n is the shading normal.
+template <bool kStats>
+__device__ __forceinline__ bool shade_hit_ranged(const float4* __restrict__ recs, const ShadeParams& sp,
+                                                 uint32_t bounce_count, float t, uint32_t k, F3& o, F3 d, F3& T, F3& L,
+                                                 uint32_t& rng, F3& n, bool& contributes) {
+    // current_origin += hit_t * current_direction (:238-241)
+    o = F3{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
+    const float4 g = recs[3 * k + 0];
+    const float4 alb = recs[3 * k + 1];
+    const float4 emi = recs[3 * k + 2];
+    F3 ng;
+    if (__float_as_uint(g.w) == 0u) {
+        ng = F3{o.x - g.x, o.y - g.y, o.z - g.z};  // sphere Ng = hit - center
+    } else {
+        ng = F3{g.x, g.y, g.z};
+        if (dot3(ng, d) > 0.0f) ng = F3{-ng.x, -ng.y, -ng.z};  // two-sided
+    }
+    // n = Ng / |Ng| (:244-250); |Ng|^2 is in inv_sqrt_ranged's window (the proof at shade_hit)
+    const float inv_len = inv_sqrt_ranged(ng.x * ng.x + ng.y * ng.y + ng.z * ng.z);
+    n = F3{ng.x * inv_len, ng.y * inv_len, ng.z * inv_len};
+    if (kStats) contributes = emi.w != 0.0f;
+    L = F3{L.x + T.x * emi.x, L.y + T.y * emi.y, L.z + T.z * emi.z};
+    // (opaque, no instruction: left visible, the compiler sinks these three multiply-adds and the miss case's into
+    // one copy behind the branch, and T's new value then travels to the join in temporaries — the nine moves per
+    // trip this split is there to remove)
+    asm volatile("" : "+v"(L.x), "+v"(L.y), "+v"(L.z));
+    // ray_throughput *= albedo (reference: 0.7f, :260)
+    T = F3{T.x * alb.x, T.y * alb.y, T.z * alb.z};
+    if (!(bounce_count < sp.max_bounces)) return false;
+    if (bounce_count > sp.rr_depth) {  // Russian roulette (:264-270)
+        const float cp = fmaxf(fmaxf(T.x, T.y), T.z);
+        if (random_float(rng) > cp) return false;
+        const RcpRef r = rcp_ref(cp);  // rr_divide_ranged, in place
+        T = F3{div_ref_to(T.x, r), div_ref_to(T.y, r), div_ref_to(T.z, r)};
+    }
+    o = F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};  // :277-280
+    return true;
+}
+
+// The miss case (:231-235): the path ends; T * sky where the configuration has the sky (whatever the map holds:
+// the term shade_hit adds), nothing otherwise. Returns whether it contributed.
+template <int kEnv>
+__device__ __forceinline__ bool shade_miss_ranged(const ShadeParams& sp, F3 d, F3 T, F3& L) {
+    if (!sp.sky_enabled) return false;
+    const F3 sky = sky_radiance<kEnv>(sp, d);
+    L = F3{L.x + T.x * sky.x, L.y + T.y * sky.y, L.z + T.z * sky.z};
+    return true;
+}
+
 // current_origin += normal * EPSILON (:277-280): the next ray's origin, and the shadow ray's
 __device__ __forceinline__ F3 offset_origin(F3 o, F3 n) {
     return F3{o.x + n.x * kOriginEps, o.y + n.y * kOriginEps, o.z + n.z * kOriginEps};
@@ -2129,6 +2208,13 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         // the wide form under the range bit keeps the frame a new direction is drawn around (dn, dt) across the
         // trips; in the other forms it measured more scratch (channel lanes, NEE, counting), so they keep theirs
         constexpr bool kCarry = kRanged && kWide;
+        // under the bit too, as kCarry and for its reason (a key without the bit keeps its machine code): the step's
+        // shading as a hit case and a miss case that assign the path's state in place (shade_hit_ranged,
+        // shade_miss_ranged), and the new direction's quadrant applied after its products (spt_device.h
+        // bounce_dir_xy). The split in the wide form only, again as kCarry: with it the channel-lane form went from
+        // no scratch to 12 B; the quadrant changes no form's registers or scratch
+        constexpr bool kSplitShade = kRanged && kWide && !kNee && !kBsdf;
+        constexpr bool kLateQuadrant = kRanged;
         [[maybe_unused]] F3 dn_loop{0.f, 0.f, 0.f}, dt_loop{0.f, 0.f, 0.f};
         uint32_t titer = 0;  // BVH NEE kernels: the chunk's traversal iterations (its cost, with the steps)
         while ((__ballot(have) != 0ull || next < n_slots || oldest_s < n_slots) && steps_left-- != 0u) {
@@ -2261,6 +2347,26 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                                 if (pend) dt = kTanRanged ? bounce_tangent_ranged(n, sp.flags) : bounce_tangent(n, sp.flags);
                             }
                         }
+                    } else if constexpr (kSplitShade) {
+                    // the range bit: the hit and the miss case each assign T, L, o, dn, have and fin themselves
+                    SPT_MARK(shade);
+                    [[maybe_unused]] bool contributes = false;
+                    if (best_k == kMiss) {
+                        contributes = shade_miss_ranged<kEnv>(sp, d, T, L);
+                        have = false;
+                        fin = true;
+                    } else if (shade_hit_ranged<kStats>(sh_prims, sp, bc + 1u, best_t, best_k, o, d, T, L, rng, dn, contributes)) {
+                        dt = kTanRanged ? bounce_tangent_ranged(dn, sp.flags) : bounce_tangent(dn, sp.flags);
+                        pend = true;
+                    } else {
+                        have = false;
+                        fin = true;
+                    }
+                    if (kStats) {
+                        atomicAdd(&s_seg[bc], 1u);
+                        if (contributes) atomicAdd(&s_rmw[bc], 1u);
+                    }
+                    ++bc;
                     } else {
                     bool alive;
                     F3 add;
@@ -2396,7 +2502,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             // one copy of the sampling code per step instead of one per branch ----
             if (pend) {
                 SPT_MARK(sample);
-                const F3 dir = bounce_dir_frame<true>(dn, dt, rng);
+                const F3 dir = bounce_dir_frame<true, kLateQuadrant>(dn, dt, rng);
                 if (kNee && !kInline && snew) {  // (a shadow ray is traced first: the continuation waits in nd)
                     nd = dir;
                 } else {
