@@ -315,7 +315,13 @@ typedef struct spt_camera {
 /* Set the camera of later spt_render calls (copied); NULL restores the reference's camera, bit for bit
  * what a ctx that never had one renders. SPT_ERR_INVALID for a non-finite value, a zero w, an unknown
  * flag or a non-zero reserved word. Resets the progressive accumulation like spt_set_env_map, and the
- * one-frame kernel's camera-hit cache. Valid before or after spt_configure; kept across spt_configure. */
+ * one-frame kernel's camera-hit cache. Valid before or after spt_configure; kept across spt_configure.
+ * The origin may lie anywhere: a BVH scene's boxes are padded for the larger of the scene's coordinate
+ * magnitude and the origin's, so a camera outside the scene's magnitude makes this call refit
+ * the tree and upload its nodes again (as does the next camera back inside); closest hits equal testing every
+ * primitive, which tests/test_gpu_bvh_brute.py checks up to an origin 1000 scene magnitudes away. At such
+ * distances the fp32 primitive tests themselves are coarse (a sphere's reports hits within 1e-3 of the
+ * distance): the image is what those tests give, on every schedule. */
 int spt_set_camera(spt_ctx* ctx, const spt_camera* camera);
 /* Host only: the camera at `eye` looking at `target`, computed in double and rounded once:
  * f = normalize(target - eye), r = normalize(cross(up, f)), t = cross(f, r), h = tan(vfov / 2);

@@ -45,6 +45,13 @@ void ref_bounce_dir(const float n[3], uint32_t* state, uint32_t flags, float out
 ref_scene* ref_scene_create(const spt_prim* prims, uint32_t n_prims, const spt_material* mats, uint32_t n_mats,
                             const spt_env* env);
 void ref_scene_destroy(ref_scene* s);
+/* Brute-force mode (off by default): with it on, every closest hit and every shadow test of this scene
+ * (ref_intersect, ref_visible, ref_light_sample's caller, ref_trace_ray, ref_render) tests every primitive
+ * in index order, a strict '<' keeping the lowest index on equal t, whatever the scene's size; off, scenes
+ * of more than 64 primitives walk the oracle's BVH for rays that start within 4 scene magnitudes of the
+ * origin (what its boxes are padded for; a ray from farther out tests every primitive in either mode).
+ * The check of that BVH (tests/test_oracle_brute.py). */
+void ref_scene_set_brute(ref_scene* s, int on);
 /* environment map (octahedral RGBA, as spt_set_env_map; NULL: the gradient sky) */
 void ref_set_env_map(ref_scene* s, const float* rgba, uint32_t w, uint32_t h);
 uint32_t ref_octa_texel(float dx, float dy, float dz, uint32_t w, uint32_t h);

@@ -59,6 +59,8 @@ def load() -> ctypes.CDLL:
     lib.ref_scene_create.restype = P
     lib.ref_scene_destroy.argtypes = [P]
     lib.ref_scene_destroy.restype = None
+    lib.ref_scene_set_brute.argtypes = [P, ctypes.c_int]
+    lib.ref_scene_set_brute.restype = None
     lib.ref_set_env_map.argtypes = [P, P, U32, U32]
     lib.ref_set_env_map.restype = None
     lib.ref_octa_texel.argtypes = [F, F, F, U32, U32]
@@ -129,13 +131,20 @@ def bounce_dir(n, state: int, flags: int = 0) -> Tuple[np.ndarray, int]:
 
 
 class RefScene:
-    def __init__(self, prims: np.ndarray, mats: np.ndarray, env):
+    def __init__(self, prims: np.ndarray, mats: np.ndarray, env, brute: bool = False):
+        """brute: test every primitive at every closest hit and shadow test (no BVH), see set_brute."""
         self.lib = load()
         self._prims = np.ascontiguousarray(prims)
         self._mats = np.ascontiguousarray(mats)
         self._env = _env(env)
         self.h = self.lib.ref_scene_create(self._prims.ctypes.data if len(prims) else None, len(prims),
                                            self._mats.ctypes.data, len(mats), ctypes.byref(self._env))
+        if brute:
+            self.set_brute(True)
+
+    def set_brute(self, on: bool = True) -> None:
+        """Brute-force mode: every primitive in index order, lowest index on equal t, whatever the size."""
+        self.lib.ref_scene_set_brute(self.h, 1 if on else 0)
 
     def __del__(self):
         if getattr(self, "h", None):

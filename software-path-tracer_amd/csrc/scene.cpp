@@ -369,16 +369,30 @@ Aabb prim_bounds(const spt_prim& p) {
     return b;
 }
 
-// Pad a box outward by an absolute epsilon = 1e-5 x the scene's coordinate magnitude, so the
-// few-ulp rounding of the slab test ((lo - o) * inv, error ~1e-7 of the ray-box distance, itself
-// bounded by the scene extent) and of the primitive tests can never cull a box whose primitives
-// the exact test would hit. A box-local epsilon is not enough: the error scales with the distance
-// from the ray origin, not with the box.
+// Pad a box outward by an absolute epsilon = 1e-5 x M (scene.h: the larger of the scene's coordinate
+// magnitude and the ray origins' reach), so the few-ulp rounding of the slab test ((lo - o) * inv, error
+// ~1e-7 of the ray-box distance, itself bounded by M) and of the quad and triangle tests can never cull a
+// box whose primitives the exact test would hit. A box-local epsilon is not enough: the error scales with
+// the distance from the ray origin, not with the box.
 void pad(Aabb& b, float eps) {
     for (int k = 0; k < 3; ++k) {
         b.lo[k] -= eps;
         b.hi[k] += eps;
     }
+}
+
+// What a sphere's box grows by on top of that (scene.h): sqrt(r^2 + 12 M^2 2^-20) - r, rounded up.
+float sphere_pad(float r, float m) {
+    const double rr = std::fabs((double)r);
+    const double p = std::sqrt(rr * rr + 12.0 * (double)m * (double)m * (1.0 / 1048576.0)) - rr;
+    return std::nextafter((float)p, std::numeric_limits<float>::infinity());
+}
+
+// A primitive's bounds as the tree's leaves hold them, before the common eps
+Aabb padded_prim_bounds(const spt_prim& p, float m) {
+    Aabb b = prim_bounds(p);
+    if (p.type == SPT_PRIM_SPHERE) pad(b, sphere_pad(p.p0[3], m));
+    return b;
 }
 
 struct Builder {
@@ -500,7 +514,7 @@ struct Builder {
 }  // namespace
 
 void build_bvh(const spt_prim* in, std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes,
-               uint32_t max_leaf, uint32_t bins) {
+               uint32_t max_leaf, uint32_t bins, float reach) {
     const uint32_t n = uint32_t(prims.size());
     nodes.clear();
     nodes.reserve(2 * size_t(n) + 1);
@@ -534,16 +548,25 @@ void build_bvh(const spt_prim* in, std::vector<DevPrim>& prims, std::vector<BvhN
     std::vector<DevPrim> reordered(n);
     for (uint32_t i = 0; i < n; ++i) reordered[i] = prims[b.idx[i]];
     prims.swap(reordered);
+    // the boxes, padded for `reach` (for a scene without spheres inside its own magnitude: the bits set above)
+    refit_bvh(in, n, prims, nodes, reach);
 }
 
-void refit_bvh(const spt_prim* in, uint32_t n, const std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes) {
-    if (n == 0 || nodes.empty()) return;
-    float mag = 1.0f;  // the padding of build_bvh, from the edited scene's coordinate magnitude
+float scene_magnitude(const spt_prim* in, uint32_t n) {
+    float mag = 1.0f;
     for (uint32_t i = 0; i < n; ++i) {
         const Aabb b = prim_bounds(in[i]);
         for (int k = 0; k < 3; ++k) mag = std::max({mag, std::fabs(b.lo[k]), std::fabs(b.hi[k])});
     }
-    const float eps = mag * 1e-5f;
+    return mag;
+}
+
+void refit_bvh(const spt_prim* in, uint32_t n, const std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes,
+               float reach) {
+    if (n == 0 || nodes.empty()) return;
+    // the padding of scene.h, from the edited scene's coordinate magnitude and the ray origins' reach
+    const float m = std::max(scene_magnitude(in, n), reach);
+    const float eps = m * 1e-5f;
     // children are allocated after their parent (build_bvh), so one reverse pass is bottom-up; node 1
     // is the alignment pad, never referenced
     for (size_t i = nodes.size(); i-- > 0;) {
@@ -552,7 +575,7 @@ void refit_bvh(const spt_prim* in, uint32_t n, const std::vector<DevPrim>& prims
         const uint32_t first = f2u(nd.lo[3]), count = f2u(nd.hi[3]);
         Aabb b;
         if (count > 0) {
-            for (uint32_t j = first; j < first + count; ++j) b.grow(prim_bounds(in[f2u(prims[j].b[3])]));
+            for (uint32_t j = first; j < first + count; ++j) b.grow(padded_prim_bounds(in[f2u(prims[j].b[3])], m));
             pad(b, eps);
         } else {  // union of the padded children = the padded union (the same eps on every side)
             for (uint32_t c = first; c < first + 2u; ++c) {

@@ -107,9 +107,20 @@ uint32_t flat_rect_bits(const std::vector<DevPrim>& sorted, const uint32_t ends[
 constexpr uint32_t kFlatMaxPairs = 3;
 uint32_t flat_wall_pairs(std::vector<DevPrim>& sorted, const uint32_t ends[kFlatKinds - 1], uint32_t rect_bits);
 
-// Binned-SAH BVH over the prepared primitives. Reorders `prims` into leaf order.
-// Boxes are padded outward by 1e-5 of the scene's coordinate magnitude, so the (rounded) slab test
-// never culls a primitive whose exact intersection test would accept the ray.
+// The padding of a tree's boxes, for rays that start within `reach` of the origin in every
+// coordinate: with M = max(the scene's coordinate magnitude, reach),
+//   - every box grows by eps = 1e-5 M on every side, far more than the few ulps of M by which a slab
+//     distance and a quad's or triangle's test round;
+//   - a sphere's box grows by sqrt(r^2 + 12 M^2 2^-20) - r more: its test is a quadratic whose discriminant
+//     4 (r^2 - p^2) (p: the ray's distance from the centre) is a difference of terms of size |o - c|^2
+//     <= 12 M^2, so it reports hits (at points of the ray) out to p^2 = r^2 + k |o - c|^2 with k a few dozen
+//     ulps — an error of sqrt(ulp), not of an ulp: 1e-3 |o - c| for a small sphere.
+// So the (rounded) slab test never culls a primitive whose own test would accept the ray. reach = 0 is a
+// tree for rays that start inside the scene's magnitude: every bounce ray, and a camera there.
+float scene_magnitude(const spt_prim* in, uint32_t n);  // max |coordinate| of the primitives' bounds, >= 1
+
+// Binned-SAH BVH over the prepared primitives. Reorders `prims` into leaf order. The splits are chosen on
+// the primitives' own bounds; the boxes are then padded as above (refit_bvh's pass).
 // `in` are the caller's records that `prims` was prepared from (bounds come from them).
 // SAH splits stop at depth kBvhMaxDepth; deeper subtrees are halved by index until their leaves hold
 // at most kBvhMaxLeaf primitives (the traversal packs (first, count) as first << 4 | count), so the
@@ -117,7 +128,7 @@ uint32_t flat_wall_pairs(std::vector<DevPrim>& sorted, const uint32_t ends[kFlat
 // pair starts at an even index (64-B aligned). Primitive and node indices must be < 2^28.
 // bins: SAH bins per axis (0 = the default 64; spt_tuning.bvh_bins, 2..64)
 void build_bvh(const spt_prim* in, std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes,
-               uint32_t max_leaf = 4, uint32_t bins = 0);
+               uint32_t max_leaf = 4, uint32_t bins = 0, float reach = 0.0f);
 
 // The leaf size the library builds with: SAH splits until a leaf holds at most this many
 // primitives. Single-primitive leaves are fastest for C4 (82 K primitives: 7.27 vs 5.75 Gsamples/s
@@ -157,8 +168,10 @@ inline uint32_t bvh4_max_ref(const std::vector<BvhNode4>& nodes) { return bvh_w_
 
 // Incremental edit (spt_update_prims): recompute every bound of `nodes` — a tree build_bvh made —
 // bottom-up for the edited primitives `in` (original order; `prims` are the device records in leaf
-// order, b.w = original index), keeping the topology. The padding follows build_bvh.
-void refit_bvh(const spt_prim* in, uint32_t n, const std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes);
+// order, b.w = original index), keeping the topology, padded for `reach` as above. Also how a tree is
+// re-padded when the camera leaves, or returns into, the magnitude it was padded for (spt_set_camera).
+void refit_bvh(const spt_prim* in, uint32_t n, const std::vector<DevPrim>& prims, std::vector<BvhNode>& nodes,
+               float reach = 0.0f);
 
 // Quantized 4-wide node, 64 B (half a cache line): the children's boxes as 8-bit offsets from a
 // per-node origin in units of a per-axis power of two. Decoding, origin + q * 2^e, is EXACT in

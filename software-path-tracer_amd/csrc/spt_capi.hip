@@ -268,6 +268,10 @@ struct spt_ctx : SceneMem, ConfigMem, OwnMem {  // (as bases: a buffer is c->acc
     // spt_set_camera_lens: the camera's thin lens, or none; kept across spt_configure and spt_set_camera(cam)
     bool has_lens = false;
     spt_lens lens{};
+    // BVH scenes: the reach of the ray origins the tree's boxes are padded for (scene.h; 0: the scene's own
+    // magnitude) and that magnitude: spt_set_camera re-pads the tree when the camera leaves it or returns
+    float pad_reach = 0.0f;
+    float scene_mag = 1.0f;
 
     // spt_set_material_models: one model per material of h_mats, or empty (all DIFFUSE). The device
     // materials carry each model as one word (DevMaterial::albedo[3], spt_device.h model_kind); h_dm is
@@ -597,6 +601,15 @@ static uint32_t sphere_emitters(const std::vector<DevEmitter>& emit) {
 }
 static bool nee_active(const spt_ctx* c) { return c->configured && (c->cfg.flags & SPT_FLAG_NEE) && c->n_emit != 0u; }
 
+// How far from the origin, per coordinate, the ctx's camera starts its rays (0 without one: the reference's
+// pinhole at the origin): |origin| and, with a lens, the aperture around it
+static float camera_reach(const spt_ctx* c) {
+    if (!c->has_camera) return 0.0f;
+    float r = 0.0f;
+    for (int k = 0; k < 3; ++k) r = std::max(r, std::fabs(c->camera.origin[k]));
+    return c->has_lens ? r + 2.0f * c->lens.radius : r;
+}
+
 // PassParams::cam_mode of the ctx's camera (has_camera)
 static uint32_t camera_mode(const spt_ctx* c) {
     return ((c->camera.flags & SPT_CAMERA_JITTER) ? kCamJitter : kCamPosed) | (c->has_lens ? kCamLens : 0u);
@@ -876,7 +889,7 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     if (n_prims > kFlatSceneMax) {
         uint32_t max_leaf = bvh_max_leaf(n_prims);  // scene.h
         if (c->bvh_max_leaf >= 1 && c->bvh_max_leaf <= kBvhMaxLeaf) max_leaf = c->bvh_max_leaf;  // spt_tuning
-        build_bvh(prims, dp, nodes, max_leaf, c->bvh_bins);
+        build_bvh(prims, dp, nodes, max_leaf, c->bvh_bins, camera_reach(c));
     }
     // the device traverses the W-wide collapse of the binary SAH tree (device_tree); a tree too deep for
     // the traversal stacks is refused before anything of the current scene is freed
@@ -923,6 +936,8 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     c->n_emit_spheres = sphere_emitters(emit);
     c->n_nodes = (uint32_t)nodes.size();
     c->n_dev_nodes = (uint32_t)(node_bytes / kDevNodeBytes);
+    c->pad_reach = camera_reach(c);
+    c->scene_mag = scene_magnitude(prims, n_prims);
     c->bvh_stack_need = stack_need;
     c->bvh_stack_tb = stack_tb;
     c->env = *env;
@@ -969,7 +984,9 @@ int spt_set_scene(spt_ctx* c, const spt_prim* prims, uint32_t n_prims, const spt
     return SPT_OK;
 }
 
-int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims, uint32_t n) {
+// spt_update_prims; edit false: no primitive changes (n == 0) and the caller invalidates and resets — a BVH
+// scene's boxes padded again for the ctx's camera (repad_for_camera)
+static int refit_scene(spt_ctx* c, const uint32_t* indices, const spt_prim* prims, uint32_t n, bool edit) {
     if (!c) return SPT_ERR_INVALID;
     if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "spt_update_prims before spt_set_scene");
     if (n && (!indices || !prims)) return fail(c, SPT_ERR_INVALID, "spt_update_prims: null array");
@@ -979,7 +996,7 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     if (!prepare_prims(prims, n, (uint32_t)c->h_mats.size(), upd, &msg)) return fail(c, SPT_ERR_INVALID, msg);
     for (uint32_t j = 0; j < n; ++j)
         if (indices[j] >= total) return fail(c, SPT_ERR_INVALID, "spt_update_prims: index out of range");
-    c->derived.drop(Change::Prims);
+    if (edit) c->derived.drop(Change::Prims);
     // the edits are staged and committed to the host mirror only once the device holds them, so a
     // failed call leaves the ctx's scene as it was
     std::vector<spt_prim> all = c->h_prims;
@@ -1005,7 +1022,8 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
         lo = std::min(lo, at);
         hi = std::max(hi, at);
     }
-    refit_bvh(all.data(), total, dp, tree);
+    const float reach = camera_reach(c);
+    refit_bvh(all.data(), total, dp, tree, reach);
     std::vector<DevEmitter> emit;  // moved emitters move their samples
     build_emitters(all.data(), total, c->h_mats.data(), emit);
     const DevTree dtree = device_tree(tree);
@@ -1058,6 +1076,8 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
     }
     c->bvh_stack_need = stack_need;
     c->bvh_stack_tb = dtree.stack_tb;  // (the collapse can add nodes)
+    c->pad_reach = reach;
+    c->scene_mag = scene_magnitude(all.data(), total);
     c->h_prims.swap(all);
     c->h_dp.swap(dp);
     c->h_nodes.swap(tree);
@@ -1066,8 +1086,12 @@ int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims,
         c->scene_hi[a] = c->h_nodes[0].hi[a];
     }
     // scene change -> m_frameCount = 0 (CPUPathTracer.cpp:122-131)
-    if (c->configured) return spt_reset(c);
+    if (edit && c->configured) return spt_reset(c);
     return SPT_OK;
+}
+
+int spt_update_prims(spt_ctx* c, const uint32_t* indices, const spt_prim* prims, uint32_t n) {
+    return refit_scene(c, indices, prims, n, true);
 }
 
 int spt_configure(spt_ctx* c, const spt_config* cfg) {
@@ -1630,6 +1654,17 @@ static const char* camera_error(const spt_camera& cam) {
     return nullptr;
 }
 
+// A BVH scene's boxes are padded for ray origins inside max(scene magnitude, reach) (scene.h). A camera
+// outside the scene's magnitude, or one that comes back into it, changes that: the tree is refitted with
+// the new padding and uploaded again (spt_update_prims' path with no edit: the node array, the stacks if the
+// collapse deepens; the caller drops what a camera change drops). A camera that stays inside the scene's
+// magnitude changes nothing and uploads nothing.
+static int repad_for_camera(spt_ctx* c) {
+    if (!c->has_scene || c->h_nodes.empty()) return SPT_OK;
+    if (std::max(c->scene_mag, camera_reach(c)) == std::max(c->scene_mag, c->pad_reach)) return SPT_OK;
+    return refit_scene(c, nullptr, nullptr, 0, false);
+}
+
 int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     if (!c) return SPT_ERR_INVALID;
     if (cam) {
@@ -1646,6 +1681,7 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     }
     c->has_camera = cam != nullptr;
     c->derived.drop(Change::Camera);
+    if (const int rc = repad_for_camera(c); rc != SPT_OK) return rc;
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
     return SPT_OK;
@@ -1674,6 +1710,7 @@ int spt_set_camera_lens(spt_ctx* c, const spt_lens* lens) {
         return rc;
     }
     c->derived.drop(Change::Lens);
+    if (const int rc = repad_for_camera(c); rc != SPT_OK) return rc;
     prefetch_flat(c);
     if (c->configured) return spt_reset(c);
     return SPT_OK;

@@ -515,15 +515,19 @@ __device__ __forceinline__ NodeBoxes node_boxes(float4 n0, float4 n1, float4 n2)
 }
 
 // The slab tests of a quantized node's children, against padded boxes: scene.cpp pads every BVH box
-// outward by 1e-5 of the scene's coordinate magnitude, far more than the few-ulp rounding of a slab
-// distance or of a primitive test, so the test never culls a box whose primitives the exact test would
-// hit — the traversal visits a (possibly different) superset of the boxes it must, and finds the same
-// hits (ties broken on the original index). (The FMA form lo*inv - o*inv is NOT usable: its error
-// scales with |o*inv|, measured 10x more node visits.)
+// outward by 1e-5 M, M the larger of the scene's coordinate magnitude and the camera origin's (scene.h;
+// spt_set_camera re-pads the tree when M changes), against <= 8 ulps of M by which a slab distance rounds
+// (origin - o, the fma, 1/d and the product: 2 ulps of 2M each, as a displacement of the bound) and about as
+// much for a quad's or triangle's test; a sphere's box grows further by what its quadratic's cancellation
+// reports as hits (sqrt(r^2 + 2^-20 |o - c|^2) - r). So the test never culls a box whose primitive's own
+// test would report a hit — the traversal visits a (possibly different) superset of the boxes it must, and
+// finds the hits that testing every primitive finds (ties broken on the original index). The count is in
+// DESIGN.md 3.3; the ulps are of the ORIGINS' magnitude, which is why M follows the camera. (The FMA form
+// lo*inv - o*inv is NOT usable: its error scales with |o*inv|, measured 10x more node visits.)
 // - Bounds are not decoded first: a bound's offset from the ray origin is (origin - o) + q * 2^e, the
 //   per-axis offset of the node's origin once per node, then one fma per bound (q * 2^e is exact),
-//   instead of (origin + q * 2^e) - o. The two round differently by an ulp or so of the scene's
-//   magnitude, far inside the padding.
+//   instead of (origin + q * 2^e) - o. The two round differently by an ulp or so of M, far inside the
+//   padding.
 // - Near and far bound per axis are picked by the sign of the inverse direction, once per node (one
 //   select of the packed byte words per bound): a child's entry is max(near slabs, tmin) and its exit
 //   min(far slabs, tmax), without a min/max pair per slab (C4 +6 %, C4 one frame +8 %, the App -6 % time).

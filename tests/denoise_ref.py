@@ -78,11 +78,12 @@ def atrous(c, feat_a, feat_b, levels=5, sigma_color=1.0, sigma_plane=0.05, norma
     return c
 
 
-def oracle_features(spt, ref, prims, mats, env, w, h, cam=None, jitter=False, rows=None):
+def oracle_features(spt, ref, prims, mats, env, w, h, cam=None, jitter=False, rows=None, scene=None):
     """(feat_a, feat_b, albedo), each (len(rows), w, 4) float32, from the oracle: the camera ray of every
     pixel (ref.primary_dir, or spt.camera_ray through the corner / the centre with jitter), RefScene.intersect's
-    closest hit, and the shading normal, position, material, albedo and primitive of include/spt.h."""
-    scene = ref.RefScene(prims, mats, env)
+    closest hit, and the shading normal, position, material, albedo and primitive of include/spt.h. `scene`: a
+    RefScene of (prims, mats, env) to use instead of a new one (one in brute-force mode, say)."""
+    scene = ref.RefScene(prims, mats, env) if scene is None else scene
     rows = list(range(h)) if rows is None else list(rows)
     a = np.zeros((len(rows), w, 4), dtype=F)
     b = np.zeros((len(rows), w, 4), dtype=F)

@@ -475,7 +475,7 @@ def test_chunk_order_changes_no_bits(spt, scene, w, h, nee):
     the launches after it (launch_paths, k_chunk_order): calls of 8 frames (ordered from the second),
     one call of 24 (recording only), a forced chunk size (no order) switched back mid-way, and a scene
     change (the order cleared) all give the same bits, with NEE too. BVH scenes: in cost order too since
-    round 6 (with NEE they keep the pixel order): same check."""
+    round 6 (with NEE as well, by a cost that counts the traversal's iterations): same check."""
     prims, mats, env = spt.build_scene(scene)
     other = spt.build_scene("app")
 
