@@ -3,7 +3,8 @@
 #   make            libspt_hip.so (C-ABI + gfx950 kernels) and libspt_render.so (C++ render::PathTracer backend)
 #   make oracle     the CPU oracle (test infrastructure, oracle/build/libcpu_ref.so), its restatement with
 #                   material models (tests/cpp/libref_materials.so), the lens's device check (tests/cpp/test_device_lens)
-#                   the sphere pass's (tests/cpp/test_sphere_cull) and the guard-free forms' (tests/cpp/test_device_ranges)
+#                   the sphere pass's (tests/cpp/test_sphere_cull), the guard-free forms' (tests/cpp/test_device_ranges)
+#                   and the key minimum's (tests/cpp/test_key_min)
 #   make cpp-tests  the C++ interface test driver (tests/cpp)
 #
 # Every float operation on the hot path is compiled with -ffp-contract=off, on the device and on the
@@ -63,7 +64,8 @@ REFMAT := tests/cpp/libref_materials.so
 DEVLENS := tests/cpp/test_device_lens
 SPHCULL := tests/cpp/test_sphere_cull
 DEVRANGES := tests/cpp/test_device_ranges
-oracle: $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES)
+KEYMIN := tests/cpp/test_key_min
+oracle: $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES) $(KEYMIN)
 
 oracle/build/libcpu_ref.so: oracle/cpu_ref.c oracle/cpu_ref.h include/spt.h oracle/Makefile
 	$(MAKE) -C oracle
@@ -92,11 +94,16 @@ $(SPHCULL): tests/cpp/test_sphere_cull.hip $(CSRC)/spt_device.h
 $(DEVRANGES): tests/cpp/test_device_ranges.hip $(CSRC)/spt_device.h
 	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
 
+# GPU program (run by tests/test_gpu_key_min_device.py): spt_device.h's key_min against the integer minimum of two
+# closest-hit keys; test infrastructure
+$(KEYMIN): tests/cpp/test_key_min.hip tests/cpp/key_min_words.h $(CSRC)/spt_device.h
+	$(HIPCC) -O3 $(FPFLAGS) -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
+
 cpp-tests: $(RLIB) oracle
 	$(MAKE) -C tests/cpp
 
 clean:
 	rm -rf $(OBJ) $(LIB) $(RLIB)
 	$(MAKE) -C oracle clean
-	rm -f $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES)
+	rm -f $(REFMAT) $(DEVLENS) $(SPHCULL) $(DEVRANGES) $(KEYMIN)
 	-$(MAKE) -C tests/cpp clean

@@ -16,7 +16,9 @@ C=software-path-tracer_amd/csrc
 python3 scripts/embed_sources.py build/var_$name/spt_jit_src.inc $C/spt_kernels.hip $C/spt_device.h $C/spt_kernels.h
 $H $flags "-DSPT_JIT_EXTRA_OPTS=\"$flags\"" -Ibuild/var_$name -c software-path-tracer_amd/csrc/spt_jit.hip -o build/var_$name/j.o
 # the host scene preparation (BVH build, collapse, node order) takes the variant's flags too
+# (the image-space kernels, reprojection, display and noise, are the in-tree build's objects: `make` first)
 g++ -O2 -ffp-contract=off -fno-fast-math -fPIC -std=c++17 -Iinclude -I$C $flags -c $C/scene.cpp -o build/var_$name/s.o
 /opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -fno-gpu-rdc -o build/libspt_exp_$name.so build/var_$name/k.o build/var_$name/c.o build/var_$name/d.o build/var_$name/j.o \
-  build/var_$name/s.o software-path-tracer_amd/build/scenes.o
+  build/var_$name/s.o software-path-tracer_amd/build/scenes.o \
+  software-path-tracer_amd/build/spt_reproject.o software-path-tracer_amd/build/spt_display.o software-path-tracer_amd/build/spt_noise.o
 echo build/libspt_exp_$name.so

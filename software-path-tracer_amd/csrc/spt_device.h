@@ -582,6 +582,34 @@ __device__ __forceinline__ float isect_sphere_fast(float4 s, float rr, F3 o, F3 
     return kInf;
 }
 
+// The minimum of two closest-hit keys, (t bits << 32) | original index, as unsigned integers: on the device ONE
+// v_min_f64 on the keys read as doubles (the integer form compiles to a 64-bit compare, a wait state for its mask
+// and two selects). kKeyMin = false: the integer form on the device too (spt_kernels.hip k_paths says for which
+// kernels). Measured on C2 (profiles/key_min_rates.txt).
+// Why the bits are the integer minimum's:
+//   - Domain. A key's high word is __float_as_uint(t) with t >= the test's tmin > 0 or t = +inf (every test ends in
+//     `cond ? t : kInf`, so a NaN t never reaches a key), or the caller's incoming best_t: kInf, or a shadow ray's
+//     smax > 0. So the high word is in [1, 0x7f800000]: read as doubles, both operands are positive.
+//   - Upper end. The high word is <= 0x7f800000 < 0x7ff00000: neither operand is a double NaN or infinity. Positive
+//     finite doubles order as their bit patterns do, the IEEE mode's quieting of a signalling NaN cannot occur, and
+//     v_min_f64 returns one operand's 64 bits unchanged.
+//   - Lower end. A high word below 0x00100000 (a tiny smax) is a denormal double. The kernels run with fp64
+//     denormals on (the AMDGPU default: .amdhsa_float_denorm_mode_16_64 3 in every kernel's descriptor), so a
+//     denormal operand is compared and returned as it is, not flushed. tests/cpp/test_key_min.hip covers such words.
+//   - Ties. Equal high words order by the low word, the original index; equal keys give the same bits either way.
+// (Not __builtin_fmin: the compiler puts a canonicalizing v_max_f64 in front of each operand.)
+template <bool kKeyMin = true>
+__host__ __device__ __forceinline__ uint64_t key_min(uint64_t a, uint64_t b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    if constexpr (kKeyMin) {
+        double r;
+        asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(__longlong_as_double((long long)a)), "v"(__longlong_as_double((long long)b)));
+        return (uint64_t)__double_as_longlong(r);
+    }
+#endif
+    return a < b ? a : b;
+}
+
 // kNS >= 2 spheres (kp: their records, two words of float4 read per sphere: a = (center, radius), b = (r^2, -, -,
 // original index)) against one ray, with ONE root stage per ray where that is enough; `best` is the running
 // (t bits, original index) key. The result is the minimum over isect_sphere_fast of every sphere, bit for bit.
@@ -597,7 +625,8 @@ __device__ __forceinline__ float isect_sphere_fast(float4 s, float rr, F3 o, F3 
 // candidate; with three or more spheres, a wave with a lane of three or more candidates then runs
 // isect_sphere_fast over every sphere (a sphere tested twice changes nothing: the key minimum is idempotent).
 // `second`: the counting kernels' counts in LDS (second[1] counts the second passes, one per wave), or null.
-template <uint32_t kNS>
+// kKeyMin: key_min's form of the minimum.
+template <uint32_t kNS, bool kKeyMin = true>
 __device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, F3 o, F3 d, float a, RcpRef r2a, float tmin,
                                                  bool& redo, uint64_t& best, uint32_t* second) {
     // One root stage on per-lane operands; `on`: the lane holds a candidate (another lane's operands are those of
@@ -614,7 +643,7 @@ __device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, 
         }
         t = (on & (t >= tmin)) ? t : kInf;
         const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | sidx;
-        best = key < best ? key : best;
+        best = key_min<kKeyMin>(key, best);
     };
     float bk[kNS], dk[kNS];
     uint32_t ik[kNS];
@@ -680,7 +709,7 @@ __device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, 
                     const float4 s = kp[4 * k + 0], pb = kp[4 * k + 1];
                     const float tk = isect_sphere_fast(s, pb.x, o, d, a, r2a, tmin, redo);
                     const uint64_t kk = ((uint64_t)__float_as_uint(tk) << 32) | __float_as_uint(pb.w);
-                    best = kk < best ? kk : best;
+                    best = key_min<kKeyMin>(kk, best);
                 }
             }
         }

@@ -60,6 +60,11 @@ __device__ __forceinline__ void closest_flat_exact(const float4* __restrict__ pr
 // key (t bits, original index): every t is +inf or >= kTNear > 0, so the integer order is the float
 // order, and equal t go to the lower original index, as in closest_flat_exact's index order. The
 // search starts from the caller's (best_t, best_k), as closest_flat_exact does.
+// Precondition on the incoming best_t: +inf or a finite value > 0, never NaN, zero or negative (the callers pass
+// kInf, or a shadow ray's tmax = 0.999 x a distance > 0). The key order has always needed it (a sign bit would
+// make the incoming key the largest), and with kKeyMin it is key_min's domain as well.
+// kKeyMin (the default): the keys' minimum is spt_device.h key_min's one v_min_f64; false: the integer compare.
+// The same bits either way; k_paths says which of its forms keep the compare.
 //
 // kShape != 0: a kernel compiled for one scene shape at run time (spt_jit.hip, flat_shape_key):
 // the group ends and the primitive count are compile-time constants, so every group loop unrolls
@@ -110,8 +115,8 @@ __device__ __forceinline__ void make_pair_table(const float4* __restrict__ prims
 
 // The kNP wall pairs at the head of axis group AX: kp = the group's first record, tab = the axis's
 // first table entry, `best` = closest_flat's running (t bits, original index) key. second: the counting
-// kernels' count of wave-level second passes (LDS), or null.
-template <int AX, uint32_t kNP>
+// kernels' count of wave-level second passes (LDS), or null. kKeyMin: key_min's form of the minimum.
+template <int AX, uint32_t kNP, bool kKeyMin = true>
 __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, const float4* tab, F3 o, F3 d, RcpRef r,
                                                 uint64_t& best, uint32_t* second) {
     if constexpr (kNP != 0u) {
@@ -138,7 +143,7 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
 #endif
                 const float t = isect_rect_axis_fast<AX>(e0.x, e0.y, e0.z, e0.w, e1.x, o, d, r, kTNear);
                 const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | __float_as_uint(e1.y);
-                best = key < best ? key : best;
+                best = key_min<kKeyMin>(key, best);
             };
             test(lane_tab, up);
             const bool inside = comp(la, AX) <= oa && oa <= comp(ha, AX);
@@ -155,14 +160,14 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
 #define SPT_NOHEAD(AX, RD)
 // an axis group's wall pairs (its first 2 x pairs records), before the loop over the rest of the group
 #define SPT_PAIR_HEAD(AX, RD)                                                                   \
-    flat_pair_tests<AX, flat_shape_pairs(kShape, AX)>(kp + 4 * k, pair_tab + 4 * pair0, o, d, RD, best, second); \
+    flat_pair_tests<AX, flat_shape_pairs(kShape, AX), kKeyMin>(kp + 4 * k, pair_tab + 4 * pair0, o, d, RD, best, second); \
     k += 2u * flat_shape_pairs(kShape, AX);                                                     \
     pair0 += flat_shape_pairs(kShape, AX);
 #define SPT_FLAT_GROUPS(UNROLL, PIN, HEAD)                                                      \
     {                                                                                           \
         uint32_t k = 0;                                                                         \
         if constexpr (kOnePass) { /* two or more spheres: one root stage per ray (flat_sphere_pass) */ \
-            flat_sphere_pass<(uint32_t)(kShape & 63u)>(kp, o, d, a, r2a, kTNear, redo, best, second); \
+            flat_sphere_pass<(uint32_t)(kShape & 63u), kKeyMin>(kp, o, d, a, r2a, kTNear, redo, best, second); \
             k = (uint32_t)(kShape & 63u);                                                       \
         } else {                                                                                \
             UNROLL for (const uint32_t e = flat_ends & 63u; k < e; ++k) { /* spheres */         \
@@ -198,7 +203,7 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
         take(TEST, pb);                                                                         \
     }
 
-template <uint64_t kShape = 0, bool kPaired = false>
+template <uint64_t kShape = 0, bool kPaired = false, bool kKeyMin = true>
 __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, uint32_t n_prims, F3 o, F3 d,
                                              float& best_t, uint32_t& best_k, bool fast_scene = false,
                                              uint32_t flat_ends = 0u, const float4* pair_tab = nullptr,
@@ -220,7 +225,7 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
             uint64_t best = ((uint64_t)__float_as_uint(in_t) << 32) | in_k;
             auto take = [&](float t, float4 pb) {
                 const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | __float_as_uint(pb.w);
-                best = key < best ? key : best;
+                best = key_min<kKeyMin>(key, best);
             };
             if constexpr (kShape != 0) {  // the fast path's counts as constants (the rare exact
                 // fallback below keeps the run-time loop: unrolled it would triple the kernel's code)
@@ -1540,7 +1545,7 @@ __device__ __forceinline__ void make_shade_recs(const float4* __restrict__ prims
 }
 
 // trace_ray's first iteration (CPUPathTracer.cpp:211-280) for a camera ray, without the RNG draws.
-template <bool kBvh, int kEnv, uint64_t kShape = 0, class Stk = StkP>
+template <bool kBvh, int kEnv, uint64_t kShape = 0, bool kKeyMin = true, class Stk = StkP>
 __device__ __forceinline__ PrimaryState primary_state(const float4* __restrict__ prims,
                                                       const float4* __restrict__ nodes, uint32_t n_prims,
                                                       const float4* sh_prims, const float4* sh_mats,
@@ -1555,7 +1560,7 @@ __device__ __forceinline__ PrimaryState primary_state(const float4* __restrict__
     float best_t = kInf;
     uint32_t best_k = kMiss;
     if (kBvh) closest_bvh4_on(nodes, prims, o, d, best_t, best_k, stk);
-    else closest_flat<kShape>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends);
+    else closest_flat<kShape, false, kKeyMin>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends);
     if (best_k == kMiss) {
         if (sp.sky_enabled) {  // L = 0 + T * sky with T = 1 (:231-235)
             const F3 sky = sky_radiance<kEnv>(sp, d);
@@ -1747,6 +1752,10 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     // the scene's range bit (spt_kernels.h kShapeRanges, scene.cpp flat_ranges_ok) with the configuration it holds
     // for: the step loop's guard-free forms (shade_hit's kRanged, bounce_tangent_ranged, the path start's emission)
     constexpr bool kRanged = !kBvh && !kStart0 && flat_ranges_baked(kShape);
+    // the closest hit's key minimum as one v_min_f64 (spt_device.h key_min), in the wide form only, as kCarry below:
+    // with it the plain and the channel-lane form went from no scratch to 8 and 12 B and the NEE forms gained 4 B (a
+    // form without it keeps its machine code); C2 +1.9 % (profiles/key_min_rates.txt)
+    constexpr bool kKeyMin = kRanged && kWide;
     constexpr bool kTanRanged = kRanged && flat_tangent_baked(kShape);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
@@ -1933,7 +1942,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 } else {
                     const CameraRay cr = camera_ray_xy<kShape, false>(cam, x, y, x + y * cam.width);
                     // (a BVH scene's camera ray borrows the lane's traversal stack: empty between chunks)
-                    ps = primary_state<kBvh, kEnv, kShape>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
+                    ps = primary_state<kBvh, kEnv, kShape, kKeyMin>(prims, nodes, n_prims, prims, mats, sp, cr.o, cr.d, cr.seed, stk);
                     live_px = (__float_as_uint(ps.r1.w) & kHitBit) != 0u && 1u < sp.max_bounces;
                 }
             }
@@ -2294,8 +2303,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         best_k = tv.best_k;
                     } else {
                         SPT_MARK(closest);
-                        closest_flat<kShape, true>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u,
-                                                   sp.flat_ends, pair_tab, pair_second);
+                        closest_flat<kShape, true, kKeyMin>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u,
+                                                            sp.flat_ends, pair_tab, pair_second);
                     }
                     if constexpr (kNee) {
                         if (!kInline && shadow) {  // the shadow ray: the estimate counts if nothing was hit before smax
@@ -2528,8 +2537,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                     shadow = false;
                     float bt = smax;
                     uint32_t bk = kMiss;
-                    closest_flat<kShape, true>(prims, n_prims, o, nd, bt, bk, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends,
-                                               pair_tab, pair_second);
+                    closest_flat<kShape, true, kKeyMin>(prims, n_prims, o, nd, bt, bk, (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends,
+                                                        pair_tab, pair_second);
                     if (!(bt < smax)) {
                         const uint32_t e = ring_entry(q);
                         L = F3{L.x + s_L[wave][0][e], L.y + s_L[wave][1][e], L.z + s_L[wave][2][e]};
