@@ -27,7 +27,7 @@ HIPFLAGS := -O3 -fno-slp-vectorize $(FPFLAGS) -fPIC -std=c++17 --offload-arch=$(
 CXXFLAGS := -O2 $(FPFLAGS) -fPIC -std=c++17 -Wall -Wextra -Iinclude -I$(CSRC)
 
 HIP_SRCS := $(CSRC)/spt_kernels.hip $(CSRC)/spt_capi.hip $(CSRC)/spt_jit.hip $(CSRC)/spt_denoise.hip \
-            $(CSRC)/spt_reproject.hip $(CSRC)/spt_display.hip $(CSRC)/spt_noise.hip
+            $(CSRC)/spt_reproject.hip $(CSRC)/spt_display.hip $(CSRC)/spt_noise.hip $(CSRC)/spt_denoise_guided.hip
 CPP_SRCS := $(CSRC)/scene.cpp $(CSRC)/scenes.cpp
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS))
 CPP_OBJS := $(patsubst $(CSRC)/%.cpp,$(OBJ)/%.o,$(CPP_SRCS))

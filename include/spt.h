@@ -485,7 +485,8 @@ int spt_denoise_params_default(spt_denoise_params* out);
 int spt_denoise(spt_ctx* ctx, uint32_t frame_count, const spt_denoise_params* params);
 /* Measurement and tests (the image never depends on it): the kernel form of every level of later
  * spt_denoise calls: 0 one thread per pixel with 25 global taps, 1 a residue class's tile staged in LDS,
- * -1 (the default) whichever measured faster at each step. SPT_ERR_INVALID otherwise. */
+ * -1 (the default) whichever measured faster at each step. SPT_ERR_INVALID otherwise. It
+ * governs the levels of spt_denoise_guided in the same way (their own table per step). */
 int spt_set_denoise_form(spt_ctx* ctx, int form);
 /* The last spt_denoise's image: copied to the host (n_pixels * 4 floats; waits for the stream), or its
  * device pointer and byte size (valid until the next spt_denoise or spt_configure). SPT_ERR_INVALID
@@ -502,6 +503,71 @@ int spt_resolve_denoised_rgba8(spt_ctx* ctx, float exposure, uint32_t* host_out)
  * params = NULL: the defaults. SPT_ERR_INVALID for a null array, a zero size or an invalid parameter. */
 int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
                     const spt_denoise_params* params, float* out);
+
+/* ---- variance-guided denoiser (superset) -------------------------------------------------------------
+ * The filter above smooths a converged pixel as hard as a noisy one: its colour weight has a fixed width. This
+ * one takes the width from the noise estimate's moments (below, "noise estimate"): a pixel's colour weight
+ * narrows as the variance of its mean luminance falls, so the image sharpens as frames accumulate. Each level
+ * also propagates the variance of what it wrote, which the next level reads.
+ *
+ * Definition (spt_atrous_guided_host computes it on the CPU from the functions the kernels compile,
+ * csrc/spt_atrous_guided.h: the same bits). Everything is fp32 without contraction, every '/' correctly
+ * rounded; only + - * / and fmaxf are used.
+ *
+ * Inputs: the mean colour c = accum / (float)frame_count on all four channels, as spt_denoise takes it; the
+ * ctx's noise moments, a float4 (mean, m2, prevL, 0) per pixel; the host's batch count B >= 2; feat_a and feat_b.
+ * Host constants, computed once:
+ *   inv = 1.0f / ((float)(B - 1) * (float)frame_count);   s2 = sigma_variance * sigma_variance;
+ *   per level l: step s = 1 << l, inv_z = 1.0f / (sigma_plane * (float)s).
+ * Variance of the mean luminance: v0 = fmaxf(m2 * inv, 0.0f), for every pixel, hit or miss.
+ * Prefilter (prefilter != 0, the default): G = {0.25f, 0.5f, 0.25f}; the 3 x 3 window's taps q = p + (i-1, j-1)
+ * inside the image, rows j = 0..2 outer, columns i = 0..2 inner, both sums starting at 0.0f:
+ *   g = G[j] * G[i];  s += g * v0_q;  sg += g;          then v = s / sg.     Prefilter off: v = v0.
+ * Level l reads the colour c and the variance v of the pass before; the first reads the mean and the
+ * (prefiltered) variance above. A pixel p whose camera ray missed keeps c_p and v_p. A pixel that hit computes
+ *   iv = 1.0f / (s2 * v_p + variance_floor)
+ * and visits the 25 taps in spt_denoise's order, with the same H and the same in-image rule:
+ *   L(x) = (0.2126f*x.r + 0.7152f*x.g) + 0.0722f*x.b      (linear, not compressed: v is its variance)
+ *   dl = L(c_q) - L(c_p);  x2 = (dl*dl) * iv;  r = 1.0f / (1.0f + x2);  wc = (H[j]*H[i]) * (r*r)
+ *   dn, pd, rz and geo exactly as in spt_denoise's definition
+ *   w = wc * geo, and w = 0 unless q has p's material
+ *   sum.c += w * c_q.c (c = r, g, b: multiply, then add);  sw += w;  sv += (w*w) * v_q
+ * and out.rgb = sum.rgb / sw, out.a = c_p.a, out_v = sv / (sw*sw). The centre tap has w = H[2]*H[2] > 0, so
+ * no division by zero occurs. The width does not shrink per level: the propagated variance does that.
+ * Not covered: a guided filter of the blended or reprojected image (its variance is not tracked), row shards
+ * (refused as spt_denoise refuses them), per-channel variance, variance-driven adaptive sampling. */
+typedef struct spt_guided_params {   /* 32 bytes */
+    uint32_t levels;             /* 1..6; default 5                                                      */
+    float    sigma_variance;     /* > 0, finite; default 4.0f: the colour weight's width in standard
+                                    deviations of the pixel's mean luminance                             */
+    float    sigma_plane;        /* > 0, finite, world units; default 0.05f                              */
+    uint32_t normal_power_log2;  /* 0..7; default 5                                                      */
+    float    variance_floor;     /* > 0, finite; default 1e-8f (0 would make 0 * inf a NaN)              */
+    uint32_t prefilter;          /* 0 or 1; default 1                                                    */
+    uint32_t reserved[2];        /* must be 0                                                            */
+} spt_guided_params;
+/* Host only: the defaults above. SPT_ERR_INVALID for NULL. */
+int spt_guided_params_default(spt_guided_params* out);
+/* Filter the frames accumulated so far (frame_count: the divisor) with the ctx's noise moments into the ctx's
+ * denoised image: spt_read_denoised, spt_denoised_device_ptr, spt_resolve_denoised_rgba8 and SPT_IMAGE_DENOISED
+ * serve it as they serve spt_denoise's. The features are rendered first if they are stale. params = NULL: the
+ * defaults. Asynchronous on the ctx stream; the accumulation, the frame count, the stats and the moments are
+ * untouched. The first call allocates two variance planes (4 bytes per pixel each) beside the filter's two
+ * images; a ctx that never calls it allocates nothing for it. Errors as spt_denoise, and SPT_ERR_INVALID while
+ * the ctx has folded fewer than two batches (spt_noise_update) since the accumulation last restarted. */
+int spt_denoise_guided(spt_ctx* ctx, uint32_t frame_count, const spt_guided_params* params);
+/* The variance the last spt_denoise_guided propagated, one float per pixel, copied to the host (waits for the
+ * stream): what noise the filter left. SPT_ERR_INVALID when the current denoised image did not come from
+ * spt_denoise_guided (none yet, or spt_denoise / spt_denoise_blended replaced it). */
+int spt_read_denoised_variance(spt_ctx* ctx, float* host_v);
+/* Host only, no device needed: the filter above on the caller's arrays by the functions the kernels compile:
+ * the same bits as spt_denoise_guided. rgba: the mean colour, moments: the noise moments, feat_a / feat_b: the
+ * features, out: the result; width * height * 4 floats each (out may be rgba). out_variance (may be NULL):
+ * width * height floats. params = NULL: the defaults. SPT_ERR_INVALID for a null array, a zero size,
+ * batches < 2, frame_count == 0 or an invalid parameter. */
+int spt_atrous_guided_host(const float* rgba, const float* moments, const float* feat_a, const float* feat_b,
+                           uint32_t width, uint32_t height, uint32_t batches, uint32_t frame_count,
+                           const spt_guided_params* params, float* out, float* out_variance);
 
 /* ---- temporal reprojection (superset: the reference restarts at 1 spp whenever anything changes) -------
  * After a camera move the image the old view accumulated is reused: nearly every surface is Lambertian, its
@@ -751,7 +817,7 @@ int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const 
  * reaches quantile * total. rel_error = sqrt(the lower edge of bin b + 1), the float whose bits are
  * (793 + b) << 20: the bin's upper edge, so it errs on the safe side. +inf for b = 255; 0 for b = 0 and for an
  * empty histogram.
- * Not covered: per-channel moments, variance-guided filter weights, adaptive sampling, a false-colour resolve
+ * Not covered: per-channel moments, adaptive sampling, a false-colour resolve
  * of the noise image, an estimate smoothed over time, pooling across row shards. */
 #define SPT_NOISE_BINS 256
 typedef struct spt_noise_params {      /* 16 bytes */

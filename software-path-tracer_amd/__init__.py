@@ -196,6 +196,7 @@ EXPORTED_SYMBOLS = (
     "spt_render_features", "spt_read_features", "spt_features_device_ptr",
     "spt_denoise_params_default", "spt_denoise", "spt_set_denoise_form", "spt_read_denoised", "spt_denoised_device_ptr",
     "spt_resolve_denoised_rgba8", "spt_atrous_host",
+    "spt_guided_params_default", "spt_denoise_guided", "spt_read_denoised_variance", "spt_atrous_guided_host",
     "spt_reproject_params_default", "spt_history_capture", "spt_reproject", "spt_history_clear", "spt_read_history",
     "spt_history_device_ptr", "spt_history_blend", "spt_read_blended", "spt_blended_device_ptr",
     "spt_resolve_blended_rgba8", "spt_denoise_blended", "spt_set_history_layout", "spt_reproject_basis",
@@ -256,6 +257,33 @@ class DenoiseParams(ctypes.Structure):
         for k, v in kw.items():
             if k not in dict(self._fields_):
                 raise TypeError(f"unknown spt_denoise_params field {k}")
+            setattr(self, k, v)
+
+
+class GuidedParams(ctypes.Structure):
+    """spt_guided_params (32 bytes): the variance-guided a-trous filter's levels (1..6), the colour weight's width
+    in standard deviations of a pixel's mean luminance (> 0), the plane-distance width (> 0), the normal weight's
+    exponent as log2 (0..7), the variance added under the colour weight's divisor (> 0) and whether the variance
+    goes through the 3 x 3 prefilter (0 or 1). GuidedParams() holds the library's defaults
+    (spt_guided_params_default); keyword arguments replace single fields."""
+    _fields_ = [
+        ("levels", ctypes.c_uint32),
+        ("sigma_variance", ctypes.c_float),
+        ("sigma_plane", ctypes.c_float),
+        ("normal_power_log2", ctypes.c_uint32),
+        ("variance_floor", ctypes.c_float),
+        ("prefilter", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        rc = load_library().spt_guided_params_default(ctypes.byref(self))
+        if rc != SPT_OK:
+            raise SptError(f"spt_guided_params_default -> {SPT_ERR.get(rc, rc)}")
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown spt_guided_params field {k}")
             setattr(self, k, v)
 
 
@@ -425,6 +453,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "spt_denoised_device_ptr": ([P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)], I),
         "spt_resolve_denoised_rgba8": ([P, ctypes.c_float, P], I),
         "spt_atrous_host": ([P, P, P, U32, U32, ctypes.POINTER(DenoiseParams), P], I),
+        "spt_guided_params_default": ([ctypes.POINTER(GuidedParams)], I),
+        "spt_denoise_guided": ([P, U32, ctypes.POINTER(GuidedParams)], I),
+        "spt_read_denoised_variance": ([P, P], I),
+        "spt_atrous_guided_host": ([P, P, P, P, U32, U32, U32, U32, ctypes.POINTER(GuidedParams), P, P], I),
         "spt_reproject_params_default": ([ctypes.POINTER(ReprojectParams)], I),
         "spt_history_capture": ([P, U32], I),
         "spt_reproject": ([P, ctypes.POINTER(ReprojectParams)], I),
@@ -618,6 +650,26 @@ def atrous_host(rgba: np.ndarray, feat_a: np.ndarray, feat_b: np.ndarray,
     if rc != SPT_OK:
         raise SptError(f"spt_atrous_host -> {SPT_ERR.get(rc, rc)}")
     return out
+
+
+def atrous_guided_host(rgba: np.ndarray, moments: np.ndarray, feat_a: np.ndarray, feat_b: np.ndarray, batches: int,
+                       frame_count: int, params: Optional[GuidedParams] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """spt_atrous_guided_host (host only): (colour (h, w, 4), variance (h, w)) of the variance-guided filter on
+    (h, w, 4) float32 arrays — the mean colour, the noise moments after `batches` batches and the two feature
+    images — by the functions the kernels compile: the same bits as Context.denoise_guided."""
+    c = np.ascontiguousarray(rgba, dtype=np.float32)
+    m = np.ascontiguousarray(moments, dtype=np.float32)
+    a = np.ascontiguousarray(feat_a, dtype=np.float32)
+    b = np.ascontiguousarray(feat_b, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 4 or m.shape != c.shape or a.shape != c.shape or b.shape != c.shape:
+        raise ValueError("atrous_guided_host: rgba, moments, feat_a and feat_b must be (height, width, 4) arrays of one shape")
+    out, var = np.zeros_like(c), np.zeros(c.shape[:2], dtype=np.float32)
+    rc = load_library().spt_atrous_guided_host(_ptr(c), _ptr(m), _ptr(a), _ptr(b), c.shape[1], c.shape[0], batches,
+                                               frame_count, ctypes.byref(params) if params is not None else None,
+                                               _ptr(out), _ptr(var))
+    if rc != SPT_OK:
+        raise SptError(f"spt_atrous_guided_host -> {SPT_ERR.get(rc, rc)}")
+    return out, var
 
 
 def reproject_basis(cam: Optional[SptCamera]):
@@ -1054,6 +1106,19 @@ class Context:
         self._check(self.lib.spt_denoise(self.h, frame_count, ctypes.byref(params) if params is not None else None),
                     "spt_denoise")
 
+    def denoise_guided(self, frame_count: int, params: Optional[GuidedParams] = None) -> None:
+        """spt_denoise_guided: the variance-guided filter of the mean of the frame_count frames accumulated so
+        far, with the noise moments folded so far (noise_update, at least two batches), into the ctx's denoised
+        image (asynchronous; read_denoised / resolve_denoised_rgba8 take it from there). params=None: the defaults."""
+        self._check(self.lib.spt_denoise_guided(self.h, frame_count, ctypes.byref(params) if params is not None else None),
+                    "spt_denoise_guided")
+
+    def read_denoised_variance(self) -> np.ndarray:
+        """spt_read_denoised_variance: the variance the last denoise_guided propagated, per pixel of the shard."""
+        out = np.zeros(self.shard_pixels, dtype=np.float32)
+        self._check(self.lib.spt_read_denoised_variance(self.h, _ptr(out)), "spt_read_denoised_variance")
+        return out
+
     def set_denoise_form(self, form: int) -> None:
         """spt_set_denoise_form (measurement and tests): 0 the straight kernel form at every level of later
         denoise calls, 1 the LDS-tiled one, -1 the library's choice per step. The image is the same."""
@@ -1459,6 +1524,7 @@ class HIPPathTracer(PathTracer):
         self._models = None
         self._models_dirty = False
         self._denoise: Optional[DenoiseParams] = None
+        self._guided: Optional[GuidedParams] = None
         self._reproject: Optional[ReprojectParams] = None
         self._tonemap = TONEMAP_CLAMP
         self._exposure_params: Optional[ExposureParams] = None
@@ -1468,6 +1534,8 @@ class HIPPathTracer(PathTracer):
     # HIPPathTracer::kNoiseUpdateEvery / kNoiseMeterEvery
     NOISE_UPDATE_EVERY = 8
     NOISE_METER_EVERY = 4
+    # HIPPathTracer::kGuidedMinBatches: below it the variance is too noisy to guide
+    GUIDED_MIN_BATCHES = 4
 
     def set_noise_target(self, rel_error: float, quantile: float = 0.95) -> None:
         """Not in the reference interface: a stop rule. While rel_error > 0, render() folds the frames since the
@@ -1497,6 +1565,8 @@ class HIPPathTracer(PathTracer):
         if self._frame_count - folded < self.NOISE_UPDATE_EVERY:
             return
         self._ctx.noise_update(self._frame_count)
+        if self._noise_target <= 0.0:  # (folded for set_denoise_guided alone: nothing to meter)
+            return
         self._noise_folds += 1
         if self._noise_folds < self.NOISE_METER_EVERY or batches + 1 < 2:
             return
@@ -1545,6 +1615,16 @@ class HIPPathTracer(PathTracer):
         image (Context.denoise with these parameters) of the frames accumulated so far; None (the default)
         returns the plain mean. render() and the accumulation are the same either way."""
         self._denoise = params
+
+    def set_denoise_guided(self, params: Optional[GuidedParams]) -> None:
+        """Not in the reference interface: while params is not None, render() folds a batch into the ctx's noise
+        estimate every NOISE_UPDATE_EVERY frames (with or without a noise target) and get_render_result() returns
+        the variance-guided denoised image (Context.denoise_guided with these parameters) once GUIDED_MIN_BATCHES
+        batches are folded; below that it returns the plain denoised image (Context.denoise with set_denoise's
+        parameters, or the defaults). Anything that restarts the accumulation restarts the sequence. With
+        set_reproject on, the blend is shown as without this call: the guided filter is not applied to it.
+        None (the default) switches it off."""
+        self._guided = params
 
     def set_scene(self, scene: Scene) -> None:
         self._scene = scene
@@ -1648,7 +1728,7 @@ class HIPPathTracer(PathTracer):
         n = max(1, self._settings.getSamplesPerPixel()) if self._settings_mode else 1
         self._ctx.render(self._frame_count, n)
         self._frame_count += n
-        if self._noise_target > 0.0:
+        if self._noise_target > 0.0 or self._guided is not None:
             self._noise_step()
 
     def get_render_result(self) -> RenderResult:
@@ -1666,8 +1746,11 @@ class HIPPathTracer(PathTracer):
                 self._result.image_buffer = (self._resolve_display(IMAGE_BLENDED, exposure) if display else
                                              self._ctx.resolve_blended_rgba8(exposure))
             return self._result
-        if self._denoise is not None:
-            self._ctx.denoise(self._frame_count, self._denoise)
+        if self._guided is not None or self._denoise is not None:
+            if self._guided is not None and self._ctx.noise_batches()[0] >= self.GUIDED_MIN_BATCHES:
+                self._ctx.denoise_guided(self._frame_count, self._guided)
+            else:
+                self._ctx.denoise(self._frame_count, self._denoise)
             self._result.image_buffer = (self._resolve_display(IMAGE_DENOISED, exposure) if display else
                                          self._ctx.resolve_denoised_rgba8(exposure))
             return self._result

@@ -79,7 +79,7 @@ namespace render
 		// (:61); settings mode: getSamplesPerPixel() such frames in one call (k_paths from 4)
 		const uint32_t n = m_settingsMode ? std::max<uint32_t>(1u, m_renderSettings->getSamplesPerPixel()) : 1u;
 		m_resolvedAt = 0;
-		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn && !m_reprojectOn && !display_on())
+		if (m_outputRegistered && n < SPT_PERSISTENT_MIN_FRAMES && !m_denoiseOn && !m_guidedOn && !m_reprojectOn && !display_on())
 		{
 			// the App reads the result after every render() (App.cpp:230-240): a one-frame call's resolve
 			// rides in the frame's own launch, its pixels stored into the registered result buffer as their
@@ -95,7 +95,7 @@ namespace render
 			SPT_CALL(m_ctx, spt_render(m_ctx, m_frameCount, n));
 		}
 		m_frameCount += n;
-		if (m_noiseTarget > 0.0)
+		if (m_noiseTarget > 0.0 || m_guidedOn)
 			noise_step();
 	}
 
@@ -124,6 +124,8 @@ namespace render
 		if (m_frameCount - folded < kNoiseUpdateEvery)
 			return;
 		SPT_CALL(m_ctx, spt_noise_update(m_ctx, m_frameCount));
+		if (!(m_noiseTarget > 0.0))
+			return; // (folded for set_denoise_guided alone: nothing to meter)
 		if (++m_noiseFolds < kNoiseMeterEvery || batches + 1u < 2u)
 			return;
 		m_noiseFolds = 0;
@@ -177,6 +179,14 @@ namespace render
 		m_denoiseOn = params != nullptr;
 		if (params)
 			m_denoise = *params;
+		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
+	}
+
+	void HIPPathTracer::set_denoise_guided(const spt_guided_params *params)
+	{
+		m_guidedOn = params != nullptr;
+		if (params)
+			m_guided = *params;
 		m_resolvedAt = 0; // (what render() resolved was the other kind of image)
 	}
 
@@ -251,10 +261,17 @@ namespace render
 				SPT_CALL(m_ctx, spt_resolve_blended_rgba8(m_ctx, exposure, m_render_result.image_buffer.data()));
 			return m_render_result;
 		}
-		if (m_denoiseOn)
+		if (m_denoiseOn || m_guidedOn)
 		{
-			// the filtered mean of the frames so far, resolved with divisor 1 (into the registered buffer)
-			SPT_CALL(m_ctx, spt_denoise(m_ctx, m_frameCount, &m_denoise));
+			// the filtered mean of the frames so far, resolved with divisor 1 (into the registered buffer): the
+			// variance-guided filter once its variance is worth reading, the plain one until then
+			uint32_t batches = 0;
+			if (m_guidedOn)
+				SPT_CALL(m_ctx, spt_noise_batches(m_ctx, &batches, nullptr));
+			if (m_guidedOn && batches >= kGuidedMinBatches)
+				SPT_CALL(m_ctx, spt_denoise_guided(m_ctx, m_frameCount, &m_guided));
+			else
+				SPT_CALL(m_ctx, spt_denoise(m_ctx, m_frameCount, m_denoiseOn ? &m_denoise : nullptr));
 			if (display)
 				resolve_display(SPT_IMAGE_DENOISED, exposure);
 			else

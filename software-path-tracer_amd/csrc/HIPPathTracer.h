@@ -75,6 +75,19 @@ namespace render
 		// way, except that a one-frame render() does not fuse the plain resolve into its launch while on.
 		void set_denoise(const spt_denoise_params *params);
 
+		// Not in the reference interface: the variance-guided denoiser (spt.h spt_denoise_guided with these
+		// parameters; copied). While on, render() folds a batch into the ctx's noise estimate every
+		// kNoiseUpdateEvery frames, with or without a noise target (it meters only with one), and
+		// get_render_result() returns the guided image once kGuidedMinBatches batches are folded; below that
+		// the variance is too noisy to guide and it returns the plain spt_denoise image
+		// (set_denoise's parameters if that is on too, else the defaults). A camera, scene or settings change
+		// restarts the sequence through the ctx's own invalidation. With set_reproject on the blend is shown
+		// as without this call: the guided filter is not applied to it (its variance is not tracked).
+		// nullptr switches it off, which is the default: the backend then makes exactly the calls it makes
+		// without this.
+		static constexpr uint32_t kGuidedMinBatches = 4;
+		void set_denoise_guided(const spt_guided_params *params);
+
 		// Not in the reference interface (it restarts at one sample after every change): temporal reprojection
 		// (spt.h spt_reproject with these parameters; copied). While on, a camera or lens change that arrives
 		// with frames accumulated captures the view before it is applied and reprojects it after, and
@@ -141,6 +154,8 @@ namespace render
 		bool m_modelsChanged = false;
 		spt_denoise_params m_denoise{};            // set_denoise's, while m_denoiseOn
 		bool m_denoiseOn = false;
+		spt_guided_params m_guided{};              // set_denoise_guided's, while m_guidedOn
+		bool m_guidedOn = false;
 		spt_reproject_params m_reproject{};        // set_reproject's, while m_reprojectOn
 		bool m_reprojectOn = false;
 		uint32_t m_tonemap = SPT_TONEMAP_CLAMP;    // set_tonemap's

@@ -20,6 +20,7 @@
 #include "spt.h"
 #include "spt_ctx_state.h"
 #include "spt_denoise.h"
+#include "spt_denoise_guided.h"
 #include "spt_dev_mem.h"
 #include "spt_device.h"
 #include "spt_display.h"
@@ -36,6 +37,7 @@ static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kM
               "spt.h spt_material_kind and spt_device.h model_kind");
 static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
 static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes");
+static_assert(sizeof(spt_guided_params) == 32, "spt_guided_params is 32 bytes");
 static_assert(sizeof(spt_reproject_params) == 32, "spt_reproject_params is 32 bytes");
 static_assert(sizeof(spt_exposure_params) == 32, "spt_exposure_params is 32 bytes");
 static_assert(sizeof(spt_display) == 16, "spt_display is 16 bytes");
@@ -150,6 +152,7 @@ struct ConfigMem {
     Dev<uint32_t> ray_perm, ray_bins, ray_cursor;
     Dev<float4> feat_a, feat_b, feat_albedo;  // spt_render_features: the first-hit images
     Dev<float4> dn[2];                        // spt_denoise: the filter's two ping-pong images
+    Dev<float> dn_var[2];                     // spt_denoise_guided: the variance planes that go with them
     // Temporal reprojection. spt_history_capture: the captured view — image with lengths, feat_a, feat_b in
     // 3 * pixels float4, laid out as hist_view_layout says (spt_reproject.h)
     Dev<float4> hist_view;
@@ -249,6 +252,7 @@ struct spt_ctx : SceneMem, ConfigMem, OwnMem {  // (as bases: a buffer is c->acc
     uint32_t frame_count = 0;
 
     int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
+    bool dn_guided = false;  // the denoised image is spt_denoise_guided's: dn_var[dn_result] is its variance
     // spt_history_capture: the captured view's (hist_view) layout and camera
     int hist_view_layout = 0;
     bool hist_view_has_camera = false;
@@ -1837,6 +1841,7 @@ static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt
     for (Dev<float4>& img : c->dn)
         if (const int rc = ensure_buf(c, img, c->pixels, "spt_denoise"); rc != SPT_OK) return rc;
     c->derived.begin(kDenoised);
+    c->dn_guided = false;
     const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
     for (uint32_t l = 0; l < p.levels; ++l) {
         const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
@@ -1854,6 +1859,53 @@ int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* para
     // (no scene or configuration is reported first, by denoise_image; a divisor of 0 would mean "already a mean")
     if (c->has_scene && c->configured && frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
     return denoise_image(c, c->accum, (float)frame_count, params);
+}
+
+int spt_denoise_guided(spt_ctx* c, uint32_t frame_count, const spt_guided_params* params) {
+    if (!c) return SPT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
+    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_denoise_guided before spt_configure");
+    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
+    const spt_guided_params p = params ? *params : kGuidedDefaults;
+    if (const char* msg = guided_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
+    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, "spt_denoise_guided needs the whole image (shard_count 1)");
+    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise_guided: image taller than 262140 rows");
+    if (c->noise_batches < 2 || !c->noise_state)
+        return fail(c, SPT_ERR_INVALID, "spt_denoise_guided: fewer than two spt_noise_update batches since the accumulation restarted");
+    const int rc = ensure_features(c);
+    if (rc != SPT_OK || c->pixels == 0) return rc;
+    for (Dev<float4>& img : c->dn)
+        if (const int rc = ensure_buf(c, img, c->pixels, "spt_denoise_guided"); rc != SPT_OK) return rc;
+    for (Dev<float>& plane : c->dn_var)
+        if (const int rc = ensure_buf(c, plane, c->pixels, "spt_denoise_guided"); rc != SPT_OK) return rc;
+    c->derived.begin(kDenoised);
+    c->dn_guided = false;
+    // the variance plane "the level before the first" wrote: slot 1, so that level l reads slot (l - 1) & 1
+    launch_guided_variance(c->noise_state, c->dn_var[1], c->cfg.width, c->cfg.height, guided_inv(c->noise_batches, frame_count),
+                           p.prefilter != 0u, on_stream(c));
+    SPT_HIP(c, hipGetLastError());
+    const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
+    for (uint32_t l = 0; l < p.levels; ++l) {
+        const GuidedLevel lv = guided_level(l, p);
+        const float4* in = l == 0 ? (const float4*)c->accum : (const float4*)c->dn[(l - 1u) & 1u];
+        launch_guided_level(forced >= 0 ? forced : guided_form_of_step(lv.step), in, l == 0 ? (float)frame_count : 0.0f,
+                            c->dn_var[(l + 1u) & 1u], c->feat_a, c->feat_b, c->dn[l & 1u], c->dn_var[l & 1u],
+                            c->cfg.width, c->cfg.height, lv, on_stream(c));
+        SPT_HIP(c, hipGetLastError());
+    }
+    c->derived.produced_denoised((int)((p.levels - 1u) & 1u));
+    c->dn_guided = true;
+    return SPT_OK;
+}
+
+int spt_read_denoised_variance(spt_ctx* c, float* host_v) {
+    if (!c || !host_v) return SPT_ERR_INVALID;
+    if (!c->derived.valid(kDenoised) || !c->dn_guided)
+        return fail(c, SPT_ERR_INVALID, "no guided denoised image: spt_denoise_guided first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipMemcpyAsync(host_v, c->dn_var[c->derived.dn_result], sizeof(float) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
+    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
+    return SPT_OK;
 }
 
 int spt_set_denoise_form(spt_ctx* c, int form) {
