@@ -11,10 +11,11 @@ prints, per section of the step loop, the VALU / SALU / LDS / scalar-memory / ve
 instruction counts (the code the compiler placed after a marker, up to the next one in program
 order; the sections of divergent branches interleave, so read the counts as the code size of each
 part, not as executed instructions). Of the VALU count it also gives the fp64 instructions (any *_f64 operand
-or result, the conversions included) and the fp32 transcendentals (v_rcp / v_rsq / v_sqrt / v_exp / v_log / v_sin /
-v_cos), and an issue-cycle-weighted total `wt` = VALU + fp64 + transcendental: each of the two kinds counted
-twice, the rest once (the weights are the published MI355X figures' — fp64 vector at half the fp32
-rate, a transcendental's issue cost twice a plain instruction's — not measured on this kernel)."""
+or result, the conversions included), the fp32 transcendentals (v_rcp / v_rsq / v_sqrt / v_exp / v_log / v_sin /
+v_cos) and the integer instructions measured above one issue slot (`int`: the 32-bit and 24-bit multiplies and
+multiply-adds, v_lshl_add_u32 / _u64, v_mad_u64_u32), and an issue-weighted total `wt`: each instruction at its
+measured cost in multiples of v_fma_f32's at 7 waves per SIMD (ISSUE_WEIGHTS below; scripts/valu_issue_cost.py,
+profiles/valu_issue_costs.txt), every other instruction at 1."""
 import collections
 import os
 import re
@@ -64,15 +65,31 @@ def classify(op):
 
 
 TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_")
+# the integer instructions measured at 1.5 issue slots (v_mad_u64_u32: 1.85, its own entry below)
+INT15 = ("v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u32_u24", "v_mul_u32_u24", "v_lshl_add_u64", "v_lshl_add_u32")
+# Issue cost by kind, in multiples of v_fma_f32's at 7 waves per SIMD on every CU (profiles/valu_issue_costs.txt,
+# rounded): v_fma_f64 1.52 and v_min_f64 1.50 stand for every *_f64; v_rcp_f32 2.97 and v_sqrt_f32 2.97 for the
+# fp32 transcendentals; the six of INT15 1.49-1.52; v_mad_u64_u32 1.84. v_add_f32, v_mul_f32 and v_add_u32 measured
+# 1.00, 0.96 and 1.04: the unit holds for the plain instructions.
+ISSUE_WEIGHTS = {"f64": 1.5, "trans": 3.0, "int": 1.5, "mad64": 1.85}
 
 
 def valu_kind(op):
-    """'f64', 'trans' or None (a plain VALU instruction); an fp64 transcendental counts as fp64."""
+    """'f64', 'trans', 'int', 'mad64' or None (a plain VALU instruction); an fp64 transcendental counts as fp64."""
     if "_f64" in op:
         return "f64"
     if op.startswith(TRANS):
         return "trans"
+    if op.startswith("v_mad_u64_u32"):
+        return "mad64"
+    if op.startswith(INT15):
+        return "int"
     return None
+
+
+def weighted(c):
+    """The issue-weighted VALU count of a section's counter."""
+    return c["valu"] + sum((w - 1.0) * c[k] for k, w in ISSUE_WEIGHTS.items())
 
 
 def main():
@@ -116,10 +133,12 @@ def main():
         for sec, c in cnt.items():
             print(f"  {sec:26s} valu {c['valu']:5d} ({100.0 * c['valu'] / max(tot, 1):4.1f} %)  salu {c['salu']:4d}  "
                   f"lds {c['lds']:3d}  smem {c['smem']:3d}  vmem {c['vmem']:3d}  wait {c['wait']:3d}  "
-                  f"f64 {c['f64']:3d}  trans {c['trans']:3d}  wt {c['valu'] + c['f64'] + c['trans']:5d}")
+                  f"f64 {c['f64']:3d}  trans {c['trans']:3d}  int {c['int'] + c['mad64']:3d}  wt {weighted(c):7.1f}")
         loop = [c for sec, c in cnt.items() if sec != "prologue"]
-        v, f, t = (sum(c[k] for c in loop) for k in ("valu", "f64", "trans"))
-        print(f"  {'step loop (no prologue)':26s} valu {v:5d}  f64 {f:3d}  trans {t:3d}  wt {v + f + t:5d} ({(v + f + t) / max(v, 1):.3f} x)")
+        v, f, t, i = (sum(c[k] for c in loop) for k in ("valu", "f64", "trans", "int"))
+        i += sum(c["mad64"] for c in loop)
+        wt = sum(weighted(c) for c in loop)
+        print(f"  {'step loop (no prologue)':26s} valu {v:5d}  f64 {f:3d}  trans {t:3d}  int {i:3d}  wt {wt:7.1f} ({wt / max(v, 1):.3f} x)")
 
 
 if __name__ == "__main__":

@@ -626,9 +626,14 @@ __host__ __device__ __forceinline__ uint64_t key_min(uint64_t a, uint64_t b) {
 // isect_sphere_fast over every sphere (a sphere tested twice changes nothing: the key minimum is idempotent).
 // `second`: the counting kernels' counts in LDS (second[1] counts the second passes, one per wave), or null.
 // kKeyMin: key_min's form of the minimum.
-template <uint32_t kNS, bool kKeyMin = true>
+// kRedoMask: *redo_w also gathers the wave's lanes that set `redo`, from stage 1's compares' own lane masks (scalar
+// instructions only, as `cm` below). Stage 1 evaluates the predicate for every sphere and the per-sphere loop of the
+// third pass only repeats it on the same operands, so with `redo` false on entry *redo_w is __ballot(redo) at the
+// end, which the compiler serves with a v_cndmask 0, 1 and a compare, `redo` being a value merged across the
+// passes' branches. false: redo_w is not read.
+template <uint32_t kNS, bool kKeyMin = true, bool kRedoMask = false>
 __device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, F3 o, F3 d, float a, RcpRef r2a, float tmin,
-                                                 bool& redo, uint64_t& best, uint32_t* second) {
+                                                 bool& redo, uint64_t& best, uint32_t* second, uint64_t* redo_w = nullptr) {
     // One root stage on per-lane operands; `on`: the lane holds a candidate (another lane's operands are those of
     // some sphere that is none of its candidates, its roots are not read: no exec-mask region). A candidate's
     // near root is kept if t >= tmin, else the far root replaces it (the wave then runs the far root) and is kept
@@ -657,6 +662,7 @@ __device__ __forceinline__ void flat_sphere_pass(const float4* __restrict__ kp, 
         const float c = ((lx * lx + ly * ly) + lz * lz) - pb.x;
         const float disc = b * b - 4.0f * a * c;
         redo = redo | ((disc > 0.0f) & (disc < 0x1p-96f));
+        if constexpr (kRedoMask) *redo_w |= __builtin_amdgcn_ballot_w64(disc > 0.0f) & __builtin_amdgcn_ballot_w64(disc < 0x1p-96f);
         cand[k] = ((disc >= 0x1p-96f) | (disc == 0.0f)) & (!(b > 0.0f) | !(c > 0.0f));
         bk[k] = b;
         dk[k] = disc;

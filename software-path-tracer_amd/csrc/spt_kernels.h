@@ -314,6 +314,17 @@ constexpr uint32_t kMinChunkShift = 0;
 constexpr uint32_t kWideShift = 6;
 constexpr uint32_t kWidePx = 1u << kWideShift;
 constexpr uint32_t kWideMaxFrames = 512;
+// k_paths hands out path slots: slot q of a chunk with n_live live pixels is frame f = q / n_live of live rank
+// r = q - f * n_live, in general by a high multiply (div_live there). A full chunk — n_live == px = 1 << pxs, which
+// every chunk of a view's list is but the list's last, partial one — splits by a shift and a mask instead: the wide
+// ranged form's hand-out tests n_live == px (wave-uniform) and takes this one. The same two numbers for every q:
+// tests/cpp/test_slot_split.cpp compares them with the multiply's for px = 16, 32, 64 and every q < 2^16.
+struct SlotSplit {
+    uint32_t f, r;
+};
+inline __host__ __device__ constexpr SlotSplit slot_split_shift(uint32_t q, uint32_t pxs) {
+    return SlotSplit{q >> pxs, q & ((1u << pxs) - 1u)};
+}
 
 // k_paths work plan: n[i] chunks of 1 << shift[i] pixels starting at pixel start[i] (start[0] = 0).
 // Flat scenes: the first tier's chunks are handed out in `order` (chunk indices, longest first) once a

@@ -167,7 +167,8 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
     {                                                                                           \
         uint32_t k = 0;                                                                         \
         if constexpr (kOnePass) { /* two or more spheres: one root stage per ray (flat_sphere_pass) */ \
-            flat_sphere_pass<(uint32_t)(kShape & 63u), kKeyMin>(kp, o, d, a, r2a, kTNear, redo, best, second); \
+            flat_sphere_pass<(uint32_t)(kShape & 63u), kKeyMin, kDirect>(kp, o, d, a, r2a, kTNear, redo, best, second, \
+                                                                         kDirect ? &redo_w : nullptr);             \
             k = (uint32_t)(kShape & 63u);                                                       \
         } else {                                                                                \
             UNROLL for (const uint32_t e = flat_ends & 63u; k < e; ++k) { /* spheres */         \
@@ -203,7 +204,9 @@ __device__ __forceinline__ void flat_pair_tests(const float4* __restrict__ kp, c
         take(TEST, pb);                                                                         \
     }
 
-template <uint64_t kShape = 0, bool kPaired = false, bool kKeyMin = true>
+// kDirect (k_paths' kStepInts), a one-pass shape: the wave-level `redo` test reads the lane mask flat_sphere_pass
+// gathers from its compares instead of taking a ballot of the merged bool.
+template <uint64_t kShape = 0, bool kPaired = false, bool kKeyMin = true, bool kDirect = false>
 __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, uint32_t n_prims, F3 o, F3 d,
                                              float& best_t, uint32_t& best_k, bool fast_scene = false,
                                              uint32_t flat_ends = 0u, const float4* pair_tab = nullptr,
@@ -222,6 +225,7 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
             const RcpRef r2a = rcp_ref(2.0f * a);
             const RcpRef rdx = rcp_ref(d.x), rdy = rcp_ref(d.y), rdz = rcp_ref(d.z);  // axis-aligned quads
             bool redo = false;
+            [[maybe_unused]] uint64_t redo_w = 0ull;  // kDirect, the one-pass sphere test: the wave's lanes with `redo` set
             uint64_t best = ((uint64_t)__float_as_uint(in_t) << 32) | in_k;
             auto take = [&](float t, float4 pb) {
                 const uint64_t key = ((uint64_t)__float_as_uint(t) << 32) | __float_as_uint(pb.w);
@@ -245,7 +249,8 @@ __device__ __forceinline__ void closest_flat(const float4* __restrict__ prims, u
                 const float4* __restrict__ kp = prims + 4 * n_prims;
                 SPT_FLAT_GROUPS(, SPT_PIN4, SPT_NOHEAD)
             }
-            if (__ballot(redo) == 0ull || !redo) {
+            // (every `redo` of a one-pass shape is set in flat_sphere_pass, which gathers the wave's mask itself)
+            if ((kDirect && kOnePass) ? (redo_w == 0ull || !redo) : (__ballot(redo) == 0ull || !redo)) {
                 best_t = __uint_as_float((uint32_t)(best >> 32));
                 best_k = best == (((uint64_t)__float_as_uint(in_t) << 32) | in_k) ? in_k
                          : (best_t < kInf ? (uint32_t)best : kMiss);
@@ -1124,16 +1129,34 @@ __device__ __forceinline__ float div_ref_to(float n, RcpRef r) {
     return q;
 }
 
-// The hit case: returns whether the path continues; n is the shading normal.
+// Word kWord (0: geometry, 1: albedo, 2: emission) of primitive k's LDS shading record (make_shade_recs: three
+// float4 per primitive from `scene`, the kernel's s_scene), at a 32-bit LDS address formed by ONE 24-bit
+// multiply-add: k * 48 + the array's base, the word's 16 * kWord in the read's offset field. Indexed through a
+// generic `const float4*` the same read cost a v_mad_u64_u32 (the pointer's 64-bit arithmetic, its high half
+// dropped at the ds_read). The 24-bit multiply is exact for k < 2^24 / 48; k is a primitive index of a flat scene,
+// below 64 by the shape key's 6-bit count (spt_kernels.h flat_shape_key), and the hit case and the hand-out only
+// call this with a hit's index (never kMiss). The same 16 bytes either way.
+template <uint32_t kWord>
+__device__ __forceinline__ float4 shade_rec_lds(const float4* scene, uint32_t k) {
+    using V4 = float __attribute__((ext_vector_type(4)));
+    using LdsBytes = const __attribute__((address_space(3))) char;
+    using LdsV4 = const __attribute__((address_space(3))) V4;
+    LdsBytes* const rec = (LdsBytes*)scene + __umul24(k, 48u);
+    const V4 v = *(LdsV4*)(rec + 16u * kWord);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// The hit case: returns whether the path continues; n is the shading normal. scene: the LDS shading records
+// (s_scene itself: read through shade_rec_lds).
 template <bool kStats>
-__device__ __forceinline__ bool shade_hit_ranged(const float4* __restrict__ recs, const ShadeParams& sp,
+__device__ __forceinline__ bool shade_hit_ranged(const float4* scene, const ShadeParams& sp,
                                                  uint32_t bounce_count, float t, uint32_t k, F3& o, F3 d, F3& T, F3& L,
                                                  uint32_t& rng, F3& n, bool& contributes) {
     // current_origin += hit_t * current_direction (:238-241)
     o = F3{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
-    const float4 g = recs[3 * k + 0];
-    const float4 alb = recs[3 * k + 1];
-    const float4 emi = recs[3 * k + 2];
+    const float4 g = shade_rec_lds<0>(scene, k);
+    const float4 alb = shade_rec_lds<1>(scene, k);
+    const float4 emi = shade_rec_lds<2>(scene, k);
     F3 ng;
     if (__float_as_uint(g.w) == 0u) {
         ng = F3{o.x - g.x, o.y - g.y, o.z - g.z};  // sphere Ng = hit - center
@@ -1756,6 +1779,13 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
     // with it the plain and the channel-lane form went from no scratch to 8 and 12 B and the NEE forms gained 4 B (a
     // form without it keeps its machine code); C2 +1.9 % (profiles/key_min_rates.txt)
     constexpr bool kKeyMin = kRanged && kWide;
+    // the step loop's integer and mask work in its short forms, in the wide form only and under the bit, as kKeyMin
+    // and for its reason (every other kernel keeps its machine code): LDS shading records at 32-bit addresses
+    // (shade_rec_lds), r2 of the live list at a 32-bit lane offset from the chunk's wave-uniform base, a full
+    // chunk's slot split by shift and mask (spt_kernels.h slot_split_shift), and two of the step's three ballots of a
+    // merged bool gone: the loop's condition needs none, and closest_flat's `redo` test reads the compares' own lane
+    // masks. None of it touches a float: DESIGN.md §3.1d, profiles/step_ints_rates.txt
+    constexpr bool kStepInts = kRanged && kWide;
     constexpr bool kTanRanged = kRanged && flat_tangent_baked(kShape);
     constexpr uint32_t kRingSlots = ring_slots<kBvh>();
     // flat scenes: launch-sized LDS shading records, 3 float4s per primitive (make_shade_recs)
@@ -2019,6 +2049,8 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         // tests/cpp/test_wide_plan.cpp checks every n_live <= 64 and s <= 2^16)
         const uint32_t m_live = __builtin_amdgcn_readfirstlane((0x80000000u + n_live - 1u) / n_live);
         auto div_live = [&](uint32_t s) { return __umulhi(s << 1, m_live); };
+        // a full chunk (every chunk of a list but its last, partial one): the hand-out splits a slot by shift and mask
+        [[maybe_unused]] const bool full_chunk = n_live == px;
         // kChan (small chunks, <= 16 live pixels): the ring's radiance entries are laid out per pixel —
         // pixel rank r owns the 2^sr_sh entries [r << sr_sh, (r + 1) << sr_sh), frame f at f mod 2^sr_sh
         // — so the accumulation of k frames reads each pixel's entries consecutively (unrolled, immediate
@@ -2230,7 +2262,11 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
         constexpr bool kLateQuadrant = kRanged;
         [[maybe_unused]] F3 dn_loop{0.f, 0.f, 0.f}, dt_loop{0.f, 0.f, 0.f};
         uint32_t titer = 0;  // BVH NEE kernels: the chunk's traversal iterations (its cost, with the steps)
-        while ((__ballot(have) != 0ull || next < n_slots || oldest_s < n_slots) && steps_left-- != 0u) {
+        // kStepInts: the condition without its ballot. A lane's live path holds a slot q < next that is not done, and a
+        // slot at or past `next` has not been handed out; accumulate() moves oldest_s only over done slots, so either
+        // leaves oldest_s < n_slots: the first two terms imply the third and the loop makes the same trips
+        while ((kStepInts ? oldest_s < n_slots : (__ballot(have) != 0ull || next < n_slots || oldest_s < n_slots)) &&
+               steps_left-- != 0u) {
             // ---- one segment (bounce >= 1) for every lane with a live path ----
             SPT_MARK(step);
             bool fin = false;
@@ -2289,7 +2325,9 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 }
             }
             const bool ready = kBvh ? (have && tdone) : have;
-            const unsigned long long tracing = __ballot(ready);
+            // (kStepInts, not counting: no wave-level test — `if (ready)` skips an empty step by its exec mask, `fin`
+            // stays false and finish() stores nothing)
+            const unsigned long long tracing = (kStepInts && !kStats) ? 1ull : __ballot(ready);
             if (tracing != 0ull) {
                 if (kStats && !kBvh) {
                     lane_slots += 64u;
@@ -2303,8 +2341,9 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         best_k = tv.best_k;
                     } else {
                         SPT_MARK(closest);
-                        closest_flat<kShape, true, kKeyMin>(prims, n_prims, o, d, best_t, best_k, (sp.flags & kFlagFastDiv) != 0u,
-                                                            sp.flat_ends, pair_tab, pair_second);
+                        closest_flat<kShape, true, kKeyMin, kStepInts>(prims, n_prims, o, d, best_t, best_k,
+                                                                       (sp.flags & kFlagFastDiv) != 0u, sp.flat_ends, pair_tab,
+                                                                       pair_second);
                     }
                     if constexpr (kNee) {
                         if (!kInline && shadow) {  // the shadow ray: the estimate counts if nothing was hit before smax
@@ -2368,7 +2407,7 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                         contributes = shade_miss_ranged<kEnv>(sp, d, T, L);
                         have = false;
                         fin = true;
-                    } else if (shade_hit_ranged<kStats>(sh_prims, sp, bc + 1u, best_t, best_k, o, d, T, L, rng, dn, contributes)) {
+                    } else if (shade_hit_ranged<kStats>(s_scene, sp, bc + 1u, best_t, best_k, o, d, T, L, rng, dn, contributes)) {
                         dt = kTanRanged ? bounce_tangent_ranged(dn, sp.flags) : bounce_tangent(dn, sp.flags);
                         pend = true;
                     } else {
@@ -2430,8 +2469,15 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
             const bool take = idle && next + rank < limit;
             if (take) {
                 q = next + rank;
-                const uint32_t f = div_live(q);  // the slot's frame and its pixel's live rank
-                const uint32_t r = q - f * n_live;
+                uint32_t f, r;  // the slot's frame and its pixel's live rank
+                if (kStepInts && full_chunk) {  // (wave-uniform: a scalar branch)
+                    const SlotSplit ss = slot_split_shift(q, pxs);
+                    f = ss.f;
+                    r = ss.r;
+                } else {
+                    f = div_live(q);
+                    r = q - f * n_live;
+                }
                 const uint32_t frame = cam.first_frame + f + 1u;
                 const float4 p0 = s_px[wave][0][r];
                 if constexpr (kStart0) {  // bounce 0 itself: the path's first two draws place its camera ray
@@ -2456,12 +2502,19 @@ __global__ __launch_bounds__(kBlock, kSimdWaves ? kSimdWaves : (kBvh ? kPathsWav
                 // kWide: r2 from the live list (L1/L2: the wave re-reads a record once per frame), issued
                 // here so that the draws below cover its latency
                 float4 p2w = make_float4(0.f, 0.f, 0.f, 0.f);
-                if constexpr (kWide) p2w = wrec[3u * r + 2u];
+                if constexpr (kStepInts) {
+                    // record r's third word at the 32-bit lane offset 48 r + 32 from the chunk's wave-uniform base (r <
+                    // 64: the 24-bit multiply is exact), so the load takes its scalar-base form instead of a 64-bit
+                    // address per lane; the same 16 bytes as wrec[3 r + 2]
+                    p2w = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(wrec) + 32u + (size_t)__umul24(r, 48u));
+                } else if constexpr (kWide) {
+                    p2w = wrec[3u * r + 2u];
+                }
                 bool alive = true;  // a live pixel: a hit, and bounce_count 1 < max_bounces
                 if (!kBvh) {  // ... from the hit primitive's LDS shading record (make_shade_recs)
                     const uint32_t k = __float_as_uint(p1.w) & ~kHitBit;
-                    const float4 alb = s_scene[3u * k + 1u];
-                    const float4 emi = s_scene[3u * k + 2u];
+                    const float4 alb = kStepInts ? shade_rec_lds<1>(s_scene, k) : s_scene[3u * k + 1u];
+                    const float4 emi = kStepInts ? shade_rec_lds<2>(s_scene, k) : s_scene[3u * k + 2u];
                     // kRanged: every emission component is >= +0 with the sign bit clear (flat_ranges_ok), so
                     // 1.0f * e = e and 0.0f + e = e bit for bit (only -0 would change), and a material
                     // without the flag (emi.w == 0: every component compares equal to 0) holds +0 itself: the
