@@ -26,9 +26,9 @@ FPFLAGS  := -ffp-contract=off -fno-fast-math
 HIPFLAGS := -O3 -fno-slp-vectorize $(FPFLAGS) -fPIC -std=c++17 --offload-arch=$(ARCH) -fno-gpu-rdc -Wall -Iinclude -I$(CSRC)
 CXXFLAGS := -O2 $(FPFLAGS) -fPIC -std=c++17 -Wall -Wextra -Iinclude -I$(CSRC)
 
-HIP_SRCS := $(CSRC)/spt_kernels.hip $(CSRC)/spt_capi.hip $(CSRC)/spt_jit.hip $(CSRC)/spt_denoise.hip \
+HIP_SRCS := $(CSRC)/spt_kernels.hip $(CSRC)/spt_capi.hip $(CSRC)/spt_capi_post.hip $(CSRC)/spt_jit.hip $(CSRC)/spt_denoise.hip \
             $(CSRC)/spt_reproject.hip $(CSRC)/spt_display.hip $(CSRC)/spt_noise.hip $(CSRC)/spt_denoise_guided.hip
-CPP_SRCS := $(CSRC)/scene.cpp $(CSRC)/scenes.cpp
+CPP_SRCS := $(CSRC)/scene.cpp $(CSRC)/scenes.cpp $(CSRC)/spt_host.cpp
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS))
 CPP_OBJS := $(patsubst $(CSRC)/%.cpp,$(OBJ)/%.o,$(CPP_SRCS))
 HDRS     := include/spt.h $(wildcard $(CSRC)/*.h)
@@ -51,6 +51,8 @@ $(OBJ)/spt_jit.o: $(CSRC)/spt_jit.hip $(OBJ)/spt_jit_src.inc $(HDRS) | $(OBJ)
 
 $(OBJ)/%.o: $(CSRC)/%.cpp $(HDRS) | $(OBJ)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
+# the host-only entry points: the kernels' per-pixel headers as plain C++ (HIP's headers for float4, no runtime)
+$(OBJ)/spt_host.o: CXXFLAGS += -D__HIP_PLATFORM_AMD__ -I$(dir $(HIPCC))../include
 
 $(LIB): $(HIP_OBJS) $(CPP_OBJS)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fno-gpu-rdc -o $@ $^

@@ -113,19 +113,4 @@ __host__ __device__ inline float4 guided_pixel(const GuidedTap& p, float alpha, 
     return make_float4(sr / sw, sg / sw, sb / sw, alpha);
 }
 
-// ---- the definition's host part, shared by the ctx's entry point (spt_capi.hip) and the host-only one ----
-constexpr spt_guided_params kGuidedDefaults = {5u, 4.0f, 0.05f, 5u, 1e-8f, 1u, {0u, 0u}};
-
-// nullptr: valid
-inline const char* guided_params_error(const spt_guided_params& p) {
-    if (p.levels < 1u || p.levels > kAtrousMaxLevels) return "spt_guided_params: levels outside 1..6";
-    if (!(p.sigma_variance > 0.0f) || !std::isfinite(p.sigma_variance)) return "spt_guided_params: sigma_variance must be > 0 and finite";
-    if (!(p.sigma_plane > 0.0f) || !std::isfinite(p.sigma_plane)) return "spt_guided_params: sigma_plane must be > 0 and finite";
-    if (p.normal_power_log2 > kAtrousMaxNormalPower) return "spt_guided_params: normal_power_log2 outside 0..7";
-    if (!(p.variance_floor > 0.0f) || !std::isfinite(p.variance_floor)) return "spt_guided_params: variance_floor must be > 0 and finite";
-    if (p.prefilter > 1u) return "spt_guided_params: prefilter must be 0 or 1";
-    if (p.reserved[0] | p.reserved[1]) return "spt_guided_params: reserved must be 0";
-    return nullptr;
-}
-
 }  // namespace spt

@@ -1,34 +1,20 @@
-// spt_capi.hip — the C-ABI of libspt_hip.so (declared in include/spt.h).
-//
+// spt_capi.hip — the C-ABI of libspt_hip.so (declared in include/spt.h): the context (spt_ctx.h). Its
+// post-processing entry points are in spt_capi_post.hip, the entry points that take no context in spt_host.cpp.
 // Owns one HIP device's state for the integrator: scene records, ray queues, accumulation, and
 // the pass driver that replaces CPUPathTracer::render()'s serial pixel loop
 // (libs/render/src/engines/pathtracer/backends/cpu/CPUPathTracer.cpp:43-85) with wavefront
 // launches. Never aborts: every failure is a negative spt_status + spt_last_error().
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "scene.h"
-#include "spt.h"
-#include "spt_ctx_state.h"
-#include "spt_denoise.h"
-#include "spt_denoise_guided.h"
-#include "spt_dev_mem.h"
+#include "spt_ctx.h"
 #include "spt_device.h"
-#include "spt_display.h"
 #include "spt_jit.h"
-#include "spt_kernels.h"
 #include "spt_launch_plan.h"
-#include "spt_noise.h"
-#include "spt_reproject.h"
+#include "spt_params.h"
 
 using namespace spt;
 
@@ -36,12 +22,6 @@ static_assert(kBvhStackMax == kBvhStackEntries, "scene.h and spt_kernels.h stack
 static_assert(kMatDiffuse == SPT_MAT_DIFFUSE && kMatMetal == SPT_MAT_METAL && kMatDielectric == SPT_MAT_DIELECTRIC,
               "spt.h spt_material_kind and spt_device.h model_kind");
 static_assert(sizeof(spt_material_model) == 16, "spt_material_model is 16 bytes");
-static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params is 32 bytes");
-static_assert(sizeof(spt_guided_params) == 32, "spt_guided_params is 32 bytes");
-static_assert(sizeof(spt_reproject_params) == 32, "spt_reproject_params is 32 bytes");
-static_assert(sizeof(spt_exposure_params) == 32, "spt_exposure_params is 32 bytes");
-static_assert(sizeof(spt_display) == 16, "spt_display is 16 bytes");
-static_assert(sizeof(spt_noise_params) == 16, "spt_noise_params is 16 bytes");
 
 namespace {
 
@@ -69,38 +49,6 @@ DevTree make_dev_tree(const std::vector<BvhNode>& bin, QuantFn quantize) {
 }
 DevTree device_tree(const std::vector<BvhNode>& bin) { return make_dev_tree<4, BvhNodeQ>(bin, quantize_bvh4); }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    int kind = 0;  // 0 extend, 1 shade, 2 other, 3 tail, 4 persistent
-    uint32_t bounce = 0;
-    uint32_t launches = 1;  // kind 4: the launches between a and b (> 1 for a SPT_PROFILE_SPAN pair)
-    // kind 4, a split launch (ViewHalf): the second half's pair, on its stream; the launch's time is
-    // (latest end - earliest start) of the two pairs
-    hipEvent_t a2 = nullptr, b2 = nullptr;
-};
-
-// One half of a split view (spt_launch_plan.h make_view_split): the k_paths launches over it run on a
-// stream of their own, with everything a launch writes besides its pixels' sums kept per half.
-struct ViewHalf {
-    hipStream_t stream = nullptr;  // non-blocking, created with the ctx
-    hipEvent_t done = nullptr;     // behind the half's last launch of a call: the ctx stream waits on it (the join)
-    uint32_t* work = nullptr;      // 2 sets of kWorkWords of its own, inside the ctx's `work` (k_paths zeroes work_next
-    uint32_t work_parity = 0;      // in stream order: a set is never shared across streams)
-};
-
-// ---- device memory: every allocation has an owner (spt_dev_mem.h), in the record of what frees it ----
-struct HipAlloc {
-    static void* alloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) == hipSuccess) return p;
-        (void)hipGetLastError();  // (the caller reports the failure: no sticky error is left for a later check)
-        return nullptr;
-    }
-    static void free(void* p) { (void)hipFree(p); }
-};
-template <class T>
-using Dev = DevBuf<T, HipAlloc>;
-
 // float4s in n records of a device array the kernels address as float4 (scene.h DevPrim, DevMaterial, DevEmitter)
 template <class Rec>
 size_t float4s(size_t n) {
@@ -108,265 +56,6 @@ size_t float4s(size_t n) {
     return n * (sizeof(Rec) / sizeof(float4));
 }
 static_assert(kDevNodeBytes % sizeof(float4) == 0, "a device node is whole float4s");
-
-// The scene's: freed by free_scene (spt_set_scene, a failed upload, spt_destroy).
-struct SceneMem {
-    Dev<float4> d_prims;
-    Dev<float4> d_mats;
-    Dev<float4> d_nodes;
-    Dev<float4> d_emit;  // SPT_FLAG_NEE: the sampled emitters (scene.h DevEmitter), n_emit records
-    Dev<uint32_t> d_mat_map;  // the caller's material index behind each device material (h_dev_mat)
-    // one word per material of h_mats, 0 for a METAL or DIELECTRIC one; uploaded by spt_reproject while some
-    // model is not DIFFUSE (bsdf)
-    Dev<uint32_t> d_reusable;
-    Dev<uint8_t> bvh_stack;  // the persistent kernels' traversal stacks (global memory)
-};
-
-// The configuration's, each sized by it: freed by free_buffers (a reallocating spt_configure, spt_destroy), so
-// none outlives the size it was allocated for. What spt_configure does not allocate, the first call that
-// writes it does.
-struct ConfigMem {
-    Dev<float4> q_o[2], q_d[2], q_t[2];
-    Dev<float2> hit;
-    Dev<float4> radiance;
-    Dev<float4> accum;
-    Dev<float2> hit_cache;  // k_frame: each shard pixel's camera-segment closest hit
-    Dev<uint16_t> chunk_cost;  // flat k_paths' first-tier chunk costs and order (PassParams)
-    Dev<uint32_t> chunk_order;
-    struct {  // ... and each half's of a split view, [pixels / 2 + 64] (its key: DerivedState::half_order_key)
-        Dev<uint16_t> cost;
-        Dev<uint32_t> order;
-    } half_mem[2];
-    // Flat k_paths' view lists (spt_kernels.h ViewPlan): every pixel's bounce 0, compacted into live-pixel
-    // records and constant pixels. Built behind the first persistent launch that finds them dropped; the
-    // persistent launches that follow run over them. spt_reset keeps them: it only zeroes the sums.
-    Dev<float4> view_live;      // [3 * pixels]
-    Dev<float4> view_const;     // [pixels]
-    Dev<uint32_t> view_counts;  // [2] live, constant; then the compaction's per-block scratch
-    Dev<uint4> live_rec;        // hit_cache compacted: the live pixels' records (kFrameHitCache 2)
-    Dev<uint32_t> sky_pix;      // ... the sky pixels' indices
-    Dev<uint32_t> list_counts;  // [2] live, sky; then the compaction's per-block scratch
-    Dev<uint32_t> resolved;
-    // sorted ray queues (SPT_FLAG_SORTED_RAYS)
-    Dev<uint16_t> ray_keys;
-    Dev<uint32_t> ray_perm, ray_bins, ray_cursor;
-    Dev<float4> feat_a, feat_b, feat_albedo;  // spt_render_features: the first-hit images
-    Dev<float4> dn[2];                        // spt_denoise: the filter's two ping-pong images
-    Dev<float> dn_var[2];                     // spt_denoise_guided: the variance planes that go with them
-    // Temporal reprojection. spt_history_capture: the captured view — image with lengths, feat_a, feat_b in
-    // 3 * pixels float4, laid out as hist_view_layout says (spt_reproject.h)
-    Dev<float4> hist_view;
-    Dev<float4> hist;         // spt_reproject: the active history (rgb, length)
-    Dev<float4> blend;        // spt_history_blend: the blended image
-    Dev<float4> noise_state;  // spt_noise_update: the per-pixel moments
-    Dev<float> noise_e2;      // spt_noise_meter: the e2 image
-};
-
-// The context's own: freed by spt_destroy (gather_buf by free_comm as well).
-struct OwnMem {
-    Dev<uint32_t> counts;
-    Dev<unsigned long long> totals;
-    Dev<uint32_t> work;  // k_paths / k_frame work heads: 2 sets of kWorkWords, alternating per launch; then two per view half
-    Dev<float4> d_env;   // octahedral environment map (spt_set_env_map) or empty
-    Dev<float4> d_camera;  // the camera's device record (PassParams::cam_pose), allocated by the first spt_set_camera
-    // The luminance meter and the display transform: scratch only, nothing a change could make stale. The 256
-    // device words a metering sums into and the staging image of spt_resolve_display_device_image (grown on demand)
-    Dev<uint32_t> meter_counts;
-    Dev<uint32_t> display_stage;
-    Dev<float4> gather_buf;  // rank 0: comm_ranks padded shards; other ranks: their padded shard
-};
-
-}  // namespace
-
-struct spt_ctx : SceneMem, ConfigMem, OwnMem {  // (as bases: a buffer is c->accum, whichever record holds it)
-    int device = -1;
-    hipStream_t own_stream = nullptr;
-    // The stream the caller's work is ordered on. Everything but the split launches' join reaches it through
-    // on_stream(), which marks it dirty for the next split launch's fork (stream_dirty below).
-    hipStream_t user_stream = nullptr;
-    // Split k_paths launches (spt_tuning.split_streams): a view's lists in two halves on two streams.
-    ViewHalf half[2];
-    hipEvent_t fork_ev = nullptr;   // on the ctx stream: what the half streams wait on after anything else ran there
-    // Set by every use of the ctx stream (on_stream) — every entry point that enqueues on it, drains it before
-    // changing what a launch reads, or replaces it — and cleared by a split launch's fork: two split renders
-    // with nothing between them fork without a wait, so call k+1's halves overlap call k's.
-    bool stream_dirty = true;
-    int32_t split_streams = 0;      // spt_tuning: -1 never, 0 automatic, 1 always when a view is valid
-    bool last_view_split = false;   // the last persistent launch was split
-    bool last_view_wide = false;    // ... ran the wide kernel (64-pixel chunks)
-    int32_t wide_chunks = 0;        // spt_tuning: 0 = automatic, 1 = every eligible launch over a view, -1 = never
-    // spt_accum_device_ptr handed the sums' address out (until the next spt_configure frees it): the caller may
-    // read them with work of its own on its stream that no ctx call sees, so every split launch forks, as if
-    // the stream were always dirty (it then waits for that work; the overlap across calls is given up)
-    bool accum_shared = false;
-    std::string err;
-    uint32_t cu_count = 256;
-    DerivedState derived;  // which of the results cached below are valid (spt_ctx_state.h: what each change drops)
-
-    // scene (its device arrays: SceneMem)
-    uint32_t n_emit = 0;          // records in d_emit
-    uint32_t n_emit_spheres = 0;  // ... of which spheres (NeeParams::spheres)
-    uint32_t env_w = 0, env_h = 0;
-    uint32_t n_prims = 0, n_nodes = 0, n_mats = 0;
-    uint32_t n_dev_nodes = 0;  // records in d_nodes (4-wide, quantized): bounds the kernels' LDS top-node copies
-    uint32_t bvh_stack_need = 0;  // the most stack entries a traversal of the 4-wide tree holds (bvh4_stack_need)
-    uint32_t bvh_stack_stride = 0;  // entries per lane in bvh_stack (bvh_stack_stride(need)); 0: none allocated
-    uint32_t bvh_stack_tb = 1;      // 4-B stack entries: bits of the entry-distance code (bvh_stack_t0_bits)
-    spt_env env{};
-    bool has_scene = false;
-    uint32_t flat_ends = 0;  // PassParams::flat_ends
-    uint32_t flat_rect = 0;  // flat_rect_bits of the kind-major copy (part of the shape key)
-    uint32_t flat_pairs = 0; // flat_wall_pairs of the kind-major copy (part of the shape key)
-    bool fast_div = false;  // scene.cpp fast_division_ok: the flat loop's unscaled divisions apply
-    bool flat_ranges = false;  // scene.cpp flat_ranges_ok: the shape key's range bit (spt_kernels.h kShapeRanges)
-    uint64_t scene_bytes = 0;
-    uint64_t stack_bytes = 0;  // the persistent kernels' global traversal stacks (BVH scenes)
-
-    // configuration
-    spt_config cfg{};
-    bool configured = false;
-    uint32_t rows = 0;          // rows owned by this shard
-    uint32_t pixels = 0;        // rows * width
-    uint32_t frames_per_pass = 1;
-    uint32_t n_sub = 0;         // block-private sub-queues (= blocks of every extend/shade launch)
-    uint32_t sub_cap = 0;       // capacity of one sub-queue
-
-    // what goes with the device buffers (ConfigMem, OwnMem)
-    uint32_t view_n[2] = {0, 0};      // view_counts[0..1], read back once per build
-    int32_t view_cache = 0;           // spt_tuning: 0 = automatic, -1 = never (every launch computes bounce 0 itself)
-    bool last_view_cached = false;    // the last persistent launch ran over the lists
-    uint32_t live_pixels = 0;         // list_counts[0], read back once per compaction
-    uint32_t work_parity = 0;         // which of `work`'s two sets the next launch on the ctx stream takes
-    uint32_t chunks_per_wave = 0;  // k_paths: chunks per resident wave in each small tail tier (spt_tuning; 0 = auto)
-    uint32_t px_shift = 0;         // k_paths forced chunk size, log2 pixels (spt_tuning.px_shift = 2..5, clamped to the build)
-    // spt_register_host_output: a caller's host image buffer, page-locked and mapped into the GPU's
-    // address space, that the resolve kernel writes over PCIe directly (no device staging, no DMA copy)
-    void* out_host = nullptr;
-    void* out_dev = nullptr;
-    size_t out_bytes = 0;
-    // spt_render_resolve_rgba8: the resolve the next k_frame launch of spt_render fuses (fuse_frames != 0),
-    // and whether a launch took it
-    float fuse_frames = 0.0f, fuse_exposure = 1.0f;
-    bool fused = false;
-
-    uint32_t frame_count = 0;
-
-    int dn_form = -1;  // spt_set_denoise_form: -1 the form measured faster at each step
-    bool dn_guided = false;  // the denoised image is spt_denoise_guided's: dn_var[dn_result] is its variance
-    // spt_history_capture: the captured view's (hist_view) layout and camera
-    int hist_view_layout = 0;
-    bool hist_view_has_camera = false;
-    spt_camera hist_view_camera{};
-    int hist_layout = -1;        // spt_set_history_layout: -1 the layout measured faster
-    int meter_form = -1;         // spt_set_meter_form: -1 the form measured faster
-    // The noise estimate (spt_noise_update / spt_noise_meter): the batches B and frames W folded into
-    // noise_state since the accumulation last restarted (noise_frames: W as the caller counts it). spt_reset
-    // clears the counts; an update that finds B = 0 zeroes the moments first.
-    bool noise_metered = false;  // noise_e2 holds a metering of the current state's accumulation
-    uint32_t noise_batches = 0, noise_frames = 0;
-    float noise_W = 0.0f;
-
-    // spt_set_camera: the posed camera, or none (the reference's pinhole at the origin); kept across spt_configure
-    bool has_camera = false;
-    spt_camera camera{};
-    // spt_set_camera_lens: the camera's thin lens, or none; kept across spt_configure and spt_set_camera(cam)
-    bool has_lens = false;
-    spt_lens lens{};
-    // BVH scenes: the reach of the ray origins the tree's boxes are padded for (scene.h; 0: the scene's own
-    // magnitude) and that magnitude: spt_set_camera re-pads the tree when the camera leaves it or returns
-    float pad_reach = 0.0f;
-    float scene_mag = 1.0f;
-
-    // spt_set_material_models: one model per material of h_mats, or empty (all DIFFUSE). The device
-    // materials carry each model as one word (DevMaterial::albedo[3], spt_device.h model_kind); h_dm is
-    // the uploaded array without them and h_dev_mat[i] the caller's material behind device material i
-    // (a flat scene's materials are compacted). bsdf: some model is not DIFFUSE (PassParams::bsdf).
-    std::vector<spt_material_model> h_models;
-    std::vector<DevMaterial> h_dm;
-    std::vector<uint32_t> h_dev_mat;
-    bool bsdf = false;
-
-    // stats
-    uint64_t frames = 0, paths = 0, passes = 0;
-    bool profiling = false;
-    bool span = false;        // SPT_PROFILE_SPAN: one event pair around the persistent launches
-    bool span_open = false;   // its begin event is recorded
-    EventPair span_ev;
-    std::vector<EventPair> pending;
-    std::vector<EventPair> free_events;
-    uint64_t ext_launches = 0, shade_launches = 0, ext_segments = 0;
-    double ext_ms = 0.0, shade_ms = 0.0, other_ms = 0.0, tail_ms = 0.0;
-    uint64_t tail_launches = 0;
-    // Schedule (measured): flat scenes run one fused extend+shade launch per bounce
-    // and finish paths from bounce 3 in k_trace_tail; BVH scenes run split extend/shade launches
-    // for every bounce (traversal divergence makes the fused and tail kernels slower there).
-    // Overrides: spt_tuning.fused / .tail_bounce (spt_set_tuning), or SPT_FLAG_SPLIT_KERNELS.
-    int fused_override = -1;       // -1: automatic
-    uint32_t tail_override = 0;    // 0: automatic
-    double ext_ms_b[kMaxBounces] = {}, shade_ms_b[kMaxBounces] = {};
-    // Calls of >= SPT_PERSISTENT_MIN_FRAMES frames run the persistent k_paths schedule instead
-    // (SPT_FLAG_WAVEFRONT or spt_tuning.persistent = 0 keep the wavefront one).
-    int persistent_override = -1;  // -1: automatic
-    int frame_override = -1;       // spt_tuning.frame_kernel for calls of < SPT_PERSISTENT_MIN_FRAMES frames
-    bool counters = false;         // SPT_PROFILE_COUNTERS: k_paths tallies segments per bounce
-    double persist_ms = 0.0;
-    uint64_t persist_launches = 0;
-    uint32_t last_schedule = SPT_SCHEDULE_FUSED;
-    uint32_t sub_alloc = 0;        // n_sub the queue buffers were sized for (spt_configure)
-    uint32_t bvh_max_leaf = 0;     // spt_tuning: 0 = bvh_max_leaf(n)
-    uint32_t bvh_bins = 0;         // spt_tuning: 0 = the builder's default
-    int32_t specialize = 0;        // spt_tuning: flat scenes' kernels compiled for their shape: 0 = in the
-                                   // background (generic kernels until ready), 1 = inside the first launch, -1 = never
-    // sorted ray queues (SPT_FLAG_SORTED_RAYS): the binning grid over the BVH scene's bounds
-    float scene_lo[3] = {0.f, 0.f, 0.f}, scene_hi[3] = {1.f, 1.f, 1.f};
-    // host copies of the current scene for spt_update_prims: the caller's arrays, and for a BVH scene
-    // the device-order records and the binary tree (refitted, not rebuilt, on an edit)
-    std::vector<spt_prim> h_prims;
-    std::vector<spt_material> h_mats;
-    std::vector<DevPrim> h_dp;
-    std::vector<BvhNode> h_nodes;
-    std::vector<uint32_t> h_pos;  // original primitive index -> its record's position on the device
-    bool last_specialized = false; // the last persistent / frame launch ran the specialized kernel
-    uint32_t last_pairs = 0;       // ... whose key held this many wall pairs (flat_shape_pairs)
-    bool last_ranges = false;      // ... a k_paths whose step loop ran its guard-free forms (flat_ranges_baked)
-
-    // multi-GPU (spt_comm_init / spt_gather_image)
-    ncclComm_t comm = nullptr;
-    int comm_ranks = 0, comm_rank = -1;
-    // spt_gather_image_overlapped: the gather runs on a stream of its own while the ctx stream renders on
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t snap_ready = nullptr;   // ctx stream: the shard snapshot is in gather_buf
-    hipEvent_t gather_done = nullptr;  // comm stream: the last overlapped gather (and assembly) finished
-    bool gather_pending = false;       // an overlapped gather was enqueued since the last wait
-};
-
-namespace {
-
-// The ctx stream, for anything that is about to enqueue on it, wait for it or replace it: the one place
-// that marks it dirty (spt_ctx::stream_dirty). Only the split launches' join takes user_stream directly.
-hipStream_t& on_stream(spt_ctx* c) {
-    c->stream_dirty = true;
-    return c->user_stream;
-}
-
-int fail(spt_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-
-#define SPT_HIP(ctx, call)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail((ctx), SPT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// buf holds exactly n elements (kept if it does already), or SPT_ERR_HIP and "<who>: allocation failed"
-template <class T>
-int ensure_buf(spt_ctx* c, Dev<T>& buf, size_t n, const char* who) {
-    if (buf.ensure(n)) return SPT_OK;
-    return fail(c, SPT_ERR_HIP, std::string(who) + ": allocation failed");
-}
 
 void free_buffers(spt_ctx* c) {
     static_cast<ConfigMem&>(*c) = {};
@@ -659,7 +348,31 @@ static void prefetch_flat(const spt_ctx* c) {
     for (int i = 0; i < forms.n; ++i) jit_prefetch(forms.f[i], key);
 }
 
-PassParams base_params(spt_ctx* c) {
+
+// The model word of a material (spt_device.h model_kind): +0.0f DIFFUSE, -fuzz METAL, ior DIELECTRIC.
+float model_word(const spt_material_model& m) {
+    if (m.kind == SPT_MAT_METAL) return -std::fabs(m.param);  // (a fuzz of -0.0f is a mirror too, not word 0)
+    return m.kind == SPT_MAT_DIELECTRIC ? m.param : 0.0f;
+}
+// Upload the scene's device materials with the models' words (c->h_models; empty: none) and set c->bsdf.
+// The caller has synchronized the stream.
+int upload_materials(spt_ctx* c) {
+    std::vector<DevMaterial> dm = c->h_dm;
+    bool bsdf = false;
+    if (!c->h_models.empty())
+        for (size_t i = 0; i < dm.size(); ++i) {
+            const spt_material_model& m = c->h_models[c->h_dev_mat[i]];
+            dm[i].albedo[3] = model_word(m);
+            bsdf = bsdf || m.kind != SPT_MAT_DIFFUSE;
+        }
+    SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * dm.size(), hipMemcpyHostToDevice));
+    c->bsdf = bsdf;
+    return SPT_OK;
+}
+
+}  // namespace
+
+PassParams spt::base_params(spt_ctx* c) {
     PassParams p{};
     p.prims = c->d_prims;
     p.mats = c->d_mats;
@@ -726,39 +439,6 @@ PassParams base_params(spt_ctx* c) {
     p.bsdf = c->bsdf ? 1u : 0u;
     return p;
 }
-
-// The model word of a material (spt_device.h model_kind): +0.0f DIFFUSE, -fuzz METAL, ior DIELECTRIC.
-float model_word(const spt_material_model& m) {
-    if (m.kind == SPT_MAT_METAL) return -std::fabs(m.param);  // (a fuzz of -0.0f is a mirror too, not word 0)
-    return m.kind == SPT_MAT_DIELECTRIC ? m.param : 0.0f;
-}
-// nullptr: valid
-const char* model_error(const spt_material_model& m) {
-    if (m.reserved[0] | m.reserved[1]) return "material model: reserved must be 0";
-    if (!std::isfinite(m.param)) return "material model: non-finite parameter";
-    if (m.kind == SPT_MAT_DIFFUSE) return m.param == 0.0f ? nullptr : "material model: a DIFFUSE parameter must be 0";
-    if (m.kind == SPT_MAT_METAL) return m.param >= 0.0f && m.param <= 1.0f ? nullptr : "material model: fuzz outside [0, 1]";
-    if (m.kind == SPT_MAT_DIELECTRIC) return m.param > 0.0f ? nullptr : "material model: index of refraction not > 0";
-    return "material model: unknown kind";
-}
-// Upload the scene's device materials with the models' words (c->h_models; empty: none) and set c->bsdf.
-// The caller has synchronized the stream.
-int upload_materials(spt_ctx* c) {
-    std::vector<DevMaterial> dm = c->h_dm;
-    bool bsdf = false;
-    if (!c->h_models.empty())
-        for (size_t i = 0; i < dm.size(); ++i) {
-            const spt_material_model& m = c->h_models[c->h_dev_mat[i]];
-            dm[i].albedo[3] = model_word(m);
-            bsdf = bsdf || m.kind != SPT_MAT_DIFFUSE;
-        }
-    SPT_HIP(c, hipMemcpy(c->d_mats, dm.data(), sizeof(DevMaterial) * dm.size(), hipMemcpyHostToDevice));
-    c->bsdf = bsdf;
-    return SPT_OK;
-}
-
-
-}  // namespace
 
 extern "C" {
 
@@ -1483,8 +1163,6 @@ int spt_render(spt_ctx* c, uint32_t first_frame, uint32_t n_frames) {
 
 // The caller waits for the frame (spt_synchronize, the resolves)
 // (polling an event recorded after the frame instead measured the same)
-static hipError_t wait_frame(spt_ctx* c) { return hipStreamSynchronize(on_stream(c)); }
-
 int spt_synchronize(spt_ctx* c) {
     if (!c) return SPT_ERR_INVALID;
     SPT_HIP(c, hipSetDevice(c->device));
@@ -1529,33 +1207,6 @@ int spt_copy_accum_device(spt_ctx* c, void* dst) {
 
 int spt_resolve_rgba8(spt_ctx* c, uint32_t frame_count, uint32_t* host_out) {
     return spt_resolve_rgba8_exposure(c, frame_count, 1.0f, host_out);
-}
-
-// The ctx's image as RGBA8 in host_out, waited for; launch(out, stream) enqueues the kernel that writes it.
-extern "C++" {  // (a template inside the C-ABI's linkage block)
-template <class Launch>
-static int resolve_image_by(spt_ctx* c, uint32_t* host_out, Launch&& launch) {
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (c->pixels == 0) return SPT_OK;
-    if (host_out == c->out_host && sizeof(uint32_t) * (size_t)c->pixels <= c->out_bytes) {
-        // the registered buffer: the kernel's stores go straight to host memory over PCIe
-        launch((uint32_t*)c->out_dev, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-    } else {
-        launch(c->resolved, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-        SPT_HIP(c, hipMemcpyAsync(host_out, c->resolved, sizeof(uint32_t) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    }
-    SPT_HIP(c, wait_frame(c));
-    return SPT_OK;
-}
-}  // extern "C++"
-
-// img / divisor as RGBA8 in host_out, waited for (the sums and a frame count, or a mean and 1)
-static int resolve_image(spt_ctx* c, const float4* img, float divisor, float exposure, uint32_t* host_out) {
-    return resolve_image_by(c, host_out, [&](uint32_t* out, hipStream_t s) {
-        launch_resolve(img, c->pixels, divisor, exposure, out, s);
-    });
 }
 
 int spt_resolve_rgba8_exposure(spt_ctx* c, uint32_t frame_count, float exposure, uint32_t* host_out) {
@@ -1643,21 +1294,6 @@ int spt_set_env_map(spt_ctx* c, const float* rgba, uint32_t width, uint32_t heig
     return SPT_OK;
 }
 
-// nullptr: valid
-static const char* camera_error(const spt_camera& cam) {
-    double w2 = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(cam.origin[a]) || !std::isfinite(cam.u[a]) || !std::isfinite(cam.v[a]) ||
-            !std::isfinite(cam.w[a]))
-            return "camera: non-finite value";
-        w2 += (double)cam.w[a] * cam.w[a];
-    }
-    if (!(w2 > 0.0)) return "camera: w (forward) is zero";
-    if (cam.flags & ~(uint32_t)SPT_CAMERA_JITTER) return "camera: unknown flags";
-    if (cam.reserved[0] | cam.reserved[1] | cam.reserved[2]) return "camera: reserved must be 0";
-    return nullptr;
-}
-
 // A BVH scene's boxes are padded for ray origins inside max(scene magnitude, reach) (scene.h). A camera
 // outside the scene's magnitude, or one that comes back into it, changes that: the tree is refitted with
 // the new padding and uploaded again (spt_update_prims' path with no edit: the node array, the stacks if the
@@ -1689,14 +1325,6 @@ int spt_set_camera(spt_ctx* c, const spt_camera* cam) {
     prefetch_flat(c);  // (a flat scene's kernels are compiled for having a camera or none, too)
     if (c->configured) return spt_reset(c);  // another view: the accumulation restarts
     return SPT_OK;
-}
-
-// nullptr: valid
-static const char* lens_error(const spt_lens& l) {
-    if (!std::isfinite(l.radius) || l.radius < 0.0f) return "lens: radius must be finite and >= 0";
-    if (!std::isfinite(l.focus_distance) || !(l.focus_distance > 0.0f)) return "lens: focus_distance must be finite and > 0";
-    if (l.reserved[0] | l.reserved[1]) return "lens: reserved must be 0";
-    return nullptr;
 }
 
 int spt_set_camera_lens(spt_ctx* c, const spt_lens* lens) {
@@ -1743,6 +1371,8 @@ int spt_set_material_models(spt_ctx* c, const spt_material_model* models, uint32
     return SPT_OK;
 }
 
+// No context and no device call, but through spt_device.h (its host build needs the HIP compiler), so not in
+// spt_host.cpp: spt_bsdf_sample, and below spt_camera_ray, spt_camera_lens_ray and spt_camera_focus_at_hit.
 int spt_bsdf_sample(const spt_material_model* model, const float d[3], const float n[3], int entering, uint32_t flags,
                     uint32_t* rng, float dir_out[3], int* transmitted, int* absorbed) {
     if (!model || !d || !n || !rng || !dir_out || !transmitted || !absorbed) return SPT_ERR_INVALID;
@@ -1762,707 +1392,6 @@ int spt_bsdf_sample(const spt_material_model* model, const float d[3], const flo
     dir_out[2] = s.dir.z;
     *transmitted = s.transmitted ? 1 : 0;
     *absorbed = s.absorbed ? 1 : 0;
-    return SPT_OK;
-}
-
-// ---- first-hit features and the denoiser ---------------------------------------------------------
-
-namespace {
-const spt_denoise_params kDenoiseDefaults = {5u, 1.0f, 0.05f, 5u, {0u, 0u, 0u, 0u}};
-// nullptr: valid
-const char* denoise_params_error(const spt_denoise_params& p) {
-    if (p.levels < 1u || p.levels > kAtrousMaxLevels) return "spt_denoise_params: levels outside 1..6";
-    if (!(p.sigma_color > 0.0f) || !std::isfinite(p.sigma_color)) return "spt_denoise_params: sigma_color must be > 0 and finite";
-    if (!(p.sigma_plane > 0.0f) || !std::isfinite(p.sigma_plane)) return "spt_denoise_params: sigma_plane must be > 0 and finite";
-    if (p.normal_power_log2 > kAtrousMaxNormalPower) return "spt_denoise_params: normal_power_log2 outside 0..7";
-    if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_denoise_params: reserved must be 0";
-    return nullptr;
-}
-// the images are those of the current scene, camera and configuration (rendered now if they are not)
-int ensure_features(spt_ctx* c) {
-    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "features before spt_configure");
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (c->derived.valid(kFeatures) || c->pixels == 0) return SPT_OK;
-    for (Dev<float4>* img : {&c->feat_a, &c->feat_b, &c->feat_albedo})
-        if (const int rc = ensure_buf(c, *img, c->pixels, "spt_render_features"); rc != SPT_OK) return rc;
-    launch_features(base_params(c), c->d_mat_map, c->feat_a, c->feat_b, c->feat_albedo, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    c->derived.produced(kFeatures);
-    return SPT_OK;
-}
-}  // namespace
-
-int spt_render_features(spt_ctx* c) {
-    if (!c) return SPT_ERR_INVALID;
-    return ensure_features(c);
-}
-
-int spt_read_features(spt_ctx* c, float* feat_a, float* feat_b, float* albedo) {
-    if (!c) return SPT_ERR_INVALID;
-    const int rc = ensure_features(c);
-    if (rc != SPT_OK || c->pixels == 0) return rc;
-    const size_t bytes = sizeof(float4) * c->pixels;
-    if (feat_a) SPT_HIP(c, hipMemcpyAsync(feat_a, c->feat_a, bytes, hipMemcpyDeviceToHost, on_stream(c)));
-    if (feat_b) SPT_HIP(c, hipMemcpyAsync(feat_b, c->feat_b, bytes, hipMemcpyDeviceToHost, on_stream(c)));
-    if (albedo) SPT_HIP(c, hipMemcpyAsync(albedo, c->feat_albedo, bytes, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-int spt_features_device_ptr(spt_ctx* c, void** feat_a, void** feat_b, void** albedo, size_t* bytes) {
-    if (!c || !bytes) return SPT_ERR_INVALID;
-    const int rc = ensure_features(c);
-    if (rc != SPT_OK) return rc;
-    if (feat_a) *feat_a = c->feat_a;
-    if (feat_b) *feat_b = c->feat_b;
-    if (albedo) *albedo = c->feat_albedo;
-    *bytes = sizeof(float4) * (size_t)c->pixels;
-    return SPT_OK;
-}
-
-int spt_denoise_params_default(spt_denoise_params* out) {
-    if (!out) return SPT_ERR_INVALID;
-    *out = kDenoiseDefaults;
-    return SPT_OK;
-}
-
-// the filter over `in` / divisor (divisor 0: `in` is already the mean), into the ctx's denoised image
-static int denoise_image(spt_ctx* c, const float4* in0, float divisor, const spt_denoise_params* params) {
-    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_denoise before spt_configure");
-    const spt_denoise_params p = params ? *params : kDenoiseDefaults;
-    if (const char* msg = denoise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
-    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, "spt_denoise needs the whole image (shard_count 1)");
-    // (the straight form's grid has a block row per 4 image rows)
-    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise: image taller than 262140 rows");
-    const int rc = ensure_features(c);
-    if (rc != SPT_OK || c->pixels == 0) return rc;
-    for (Dev<float4>& img : c->dn)
-        if (const int rc = ensure_buf(c, img, c->pixels, "spt_denoise"); rc != SPT_OK) return rc;
-    c->derived.begin(kDenoised);
-    c->dn_guided = false;
-    const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
-    for (uint32_t l = 0; l < p.levels; ++l) {
-        const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
-        const float4* in = l == 0 ? in0 : c->dn[(l - 1u) & 1u];
-        launch_atrous(forced >= 0 ? forced : atrous_form_of_step(lv.step), in, l == 0 ? divisor : 0.0f,
-                      c->feat_a, c->feat_b, c->dn[l & 1u], c->cfg.width, c->cfg.height, lv, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-    }
-    c->derived.produced_denoised((int)((p.levels - 1u) & 1u));
-    return SPT_OK;
-}
-
-int spt_denoise(spt_ctx* c, uint32_t frame_count, const spt_denoise_params* params) {
-    if (!c) return SPT_ERR_INVALID;
-    // (no scene or configuration is reported first, by denoise_image; a divisor of 0 would mean "already a mean")
-    if (c->has_scene && c->configured && frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    return denoise_image(c, c->accum, (float)frame_count, params);
-}
-
-int spt_denoise_guided(spt_ctx* c, uint32_t frame_count, const spt_guided_params* params) {
-    if (!c) return SPT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_denoise_guided before spt_configure");
-    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    const spt_guided_params p = params ? *params : kGuidedDefaults;
-    if (const char* msg = guided_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
-    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, "spt_denoise_guided needs the whole image (shard_count 1)");
-    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, "spt_denoise_guided: image taller than 262140 rows");
-    if (c->noise_batches < 2 || !c->noise_state)
-        return fail(c, SPT_ERR_INVALID, "spt_denoise_guided: fewer than two spt_noise_update batches since the accumulation restarted");
-    const int rc = ensure_features(c);
-    if (rc != SPT_OK || c->pixels == 0) return rc;
-    for (Dev<float4>& img : c->dn)
-        if (const int rc = ensure_buf(c, img, c->pixels, "spt_denoise_guided"); rc != SPT_OK) return rc;
-    for (Dev<float>& plane : c->dn_var)
-        if (const int rc = ensure_buf(c, plane, c->pixels, "spt_denoise_guided"); rc != SPT_OK) return rc;
-    c->derived.begin(kDenoised);
-    c->dn_guided = false;
-    // the variance plane "the level before the first" wrote: slot 1, so that level l reads slot (l - 1) & 1
-    launch_guided_variance(c->noise_state, c->dn_var[1], c->cfg.width, c->cfg.height, guided_inv(c->noise_batches, frame_count),
-                           p.prefilter != 0u, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    const int forced = c->dn_form;  // spt_set_denoise_form: one form for every level (measurement), or -1
-    for (uint32_t l = 0; l < p.levels; ++l) {
-        const GuidedLevel lv = guided_level(l, p);
-        const float4* in = l == 0 ? (const float4*)c->accum : (const float4*)c->dn[(l - 1u) & 1u];
-        launch_guided_level(forced >= 0 ? forced : guided_form_of_step(lv.step), in, l == 0 ? (float)frame_count : 0.0f,
-                            c->dn_var[(l + 1u) & 1u], c->feat_a, c->feat_b, c->dn[l & 1u], c->dn_var[l & 1u],
-                            c->cfg.width, c->cfg.height, lv, on_stream(c));
-        SPT_HIP(c, hipGetLastError());
-    }
-    c->derived.produced_denoised((int)((p.levels - 1u) & 1u));
-    c->dn_guided = true;
-    return SPT_OK;
-}
-
-int spt_read_denoised_variance(spt_ctx* c, float* host_v) {
-    if (!c || !host_v) return SPT_ERR_INVALID;
-    if (!c->derived.valid(kDenoised) || !c->dn_guided)
-        return fail(c, SPT_ERR_INVALID, "no guided denoised image: spt_denoise_guided first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_v, c->dn_var[c->derived.dn_result], sizeof(float) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-int spt_set_denoise_form(spt_ctx* c, int form) {
-    if (!c) return SPT_ERR_INVALID;
-    if (form != -1 && form != kAtrousStraight && form != kAtrousTiled)
-        return fail(c, SPT_ERR_INVALID, "spt_set_denoise_form: -1 (automatic), 0 (straight) or 1 (tiled)");
-    c->dn_form = form;
-    return SPT_OK;
-}
-
-// ---- the post-processed images: denoised, active history, blended ---------------------------------
-// Each is described once: a pointer, whether it is valid (spt_ctx_state.h) and what to say when it is not.
-// Reading one back, handing out its address and resolving it to RGBA8 are one body each, for all of them.
-enum PostImage { kImgDenoised, kImgHistory, kImgBlended };
-// the image, or nullptr with the ctx's error set: there is none
-static float4* post_image(spt_ctx* c, PostImage which) {
-    const DerivedState& d = c->derived;
-    const struct {
-        float4* img;  // (a valid one was allocated: never nullptr)
-        const char* missing;
-    } images[] = {{d.valid(kDenoised) ? c->dn[d.dn_result] : nullptr, "no denoised image: spt_denoise first"},
-                  {d.valid(kHistory) ? c->hist : nullptr, "no active history: spt_reproject first"},
-                  {d.valid(kBlended) ? c->blend : nullptr, "no blended image: spt_history_blend first"}};
-    if (!images[which].img) fail(c, SPT_ERR_INVALID, images[which].missing);
-    return images[which].img;
-}
-
-static int read_image(spt_ctx* c, PostImage which, float* host_rgba) {
-    if (!c || !host_rgba) return SPT_ERR_INVALID;
-    const float4* img = post_image(c, which);
-    if (!img) return SPT_ERR_INVALID;
-    SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_rgba, img, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-static int image_device_ptr(spt_ctx* c, PostImage which, void** dptr, size_t* bytes) {
-    if (!c || !dptr || !bytes) return SPT_ERR_INVALID;
-    float4* img = post_image(c, which);
-    if (!img) return SPT_ERR_INVALID;
-    *dptr = img;
-    *bytes = sizeof(float4) * (size_t)c->pixels;
-    return SPT_OK;
-}
-
-// spt_resolve_rgba8_exposure of an image that is already a mean (divisor 1)
-static int resolve_mean_rgba8(spt_ctx* c, PostImage which, float exposure, uint32_t* host_out) {
-    if (!c || !host_out) return SPT_ERR_INVALID;
-    const float4* img = post_image(c, which);
-    return img ? resolve_image(c, img, 1.0f, exposure, host_out) : SPT_ERR_INVALID;
-}
-
-int spt_read_denoised(spt_ctx* c, float* host_rgba) { return read_image(c, kImgDenoised, host_rgba); }
-int spt_denoised_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgDenoised, dptr, bytes); }
-int spt_resolve_denoised_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
-    return resolve_mean_rgba8(c, kImgDenoised, exposure, host_out);
-}
-
-int spt_atrous_host(const float* rgba, const float* feat_a, const float* feat_b, uint32_t width, uint32_t height,
-                    const spt_denoise_params* params, float* out) {
-    if (!rgba || !feat_a || !feat_b || !out || width == 0 || height == 0) return SPT_ERR_INVALID;
-    if ((uint64_t)width * height >= (1ull << 31)) return SPT_ERR_INVALID;
-    const spt_denoise_params p = params ? *params : kDenoiseDefaults;
-    if (denoise_params_error(p)) return SPT_ERR_INVALID;
-    const size_t n = (size_t)width * height;
-    const int w = (int)width, h = (int)height;
-    auto px = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
-    std::vector<float> buf[2] = {std::vector<float>(4 * n), std::vector<float>(4 * n)};
-    const float* in = rgba;
-    for (uint32_t l = 0; l < p.levels; ++l) {
-        const AtrousLevel lv = atrous_level(l, p.sigma_color, p.sigma_plane, p.normal_power_log2);
-        float* dst = buf[l & 1u].data();
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x) {
-                const size_t at = (size_t)y * width + (size_t)x;
-                const float4 cp = px(in, at);
-                const float4 o = atrous_pixel(atrous_tap(cp, px(feat_a, at), px(feat_b, at)), cp.w, x, y, w, h, lv,
-                                              [&](int, int, int qx, int qy) {
-                                                  const size_t q = (size_t)qy * width + (size_t)qx;
-                                                  return atrous_tap(px(in, q), px(feat_a, q), px(feat_b, q));
-                                              });
-                dst[4 * at + 0] = o.x;
-                dst[4 * at + 1] = o.y;
-                dst[4 * at + 2] = o.z;
-                dst[4 * at + 3] = o.w;
-            }
-        in = dst;
-    }
-    std::memcpy(out, in, sizeof(float) * 4 * n);
-    return SPT_OK;
-}
-
-// ---- temporal reprojection ------------------------------------------------------------------------
-
-namespace {
-const spt_reproject_params kReprojectDefaults = {32.0f, 0.9f, 0.01f, 0.01f, {0u, 0u, 0u, 0u}};
-// nullptr: valid
-const char* reproject_params_error(const spt_reproject_params& p) {
-    if (!std::isfinite(p.max_history) || !(p.max_history >= 1.0f)) return "spt_reproject_params: max_history must be finite and >= 1";
-    if (!std::isfinite(p.normal_min)) return "spt_reproject_params: normal_min must be finite";
-    if (!std::isfinite(p.plane_tolerance) || !(p.plane_tolerance >= 0.0f)) return "spt_reproject_params: plane_tolerance must be finite and >= 0";
-    if (!std::isfinite(p.min_weight) || !(p.min_weight > 0.0f)) return "spt_reproject_params: min_weight must be finite and > 0";
-    if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3]) return "spt_reproject_params: reserved must be 0";
-    return nullptr;
-}
-// what spt_history_capture, spt_reproject and spt_history_blend share: a whole image, and for the first two
-// (features) its current feature images
-int history_ready(spt_ctx* c, const char* who, bool features) {
-    if (!c->has_scene) return fail(c, SPT_ERR_NO_SCENE, "Scene not set before rendering");
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, std::string(who) + " before spt_configure");
-    if (c->cfg.shard_count != 1u) return fail(c, SPT_ERR_INVALID, std::string(who) + " needs the whole image (shard_count 1)");
-    // (k_reproject's grid has a block row per 4 image rows)
-    if (c->cfg.height > 4u * 65535u) return fail(c, SPT_ERR_INVALID, std::string(who) + ": image taller than 262140 rows");
-    if (features) return ensure_features(c);
-    SPT_HIP(c, hipSetDevice(c->device));
-    return SPT_OK;
-}
-}  // namespace
-
-int spt_reproject_params_default(spt_reproject_params* out) {
-    if (!out) return SPT_ERR_INVALID;
-    *out = kReprojectDefaults;
-    return SPT_OK;
-}
-
-int spt_history_capture(spt_ctx* c, uint32_t frame_count) {
-    if (!c) return SPT_ERR_INVALID;
-    if (const int rc = history_ready(c, "spt_history_capture", true); rc != SPT_OK) return rc;
-    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    if (const int rc = ensure_buf(c, c->hist_view, 3 * (size_t)c->pixels, "spt_history_capture"); rc != SPT_OK) return rc;
-    c->derived.begin(kCapturedView);
-    const int layout = c->hist_layout >= 0 ? c->hist_layout : kHistoryDefault;
-    launch_history_capture(layout, c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->feat_a, c->feat_b,
-                           c->hist_view, c->pixels, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    c->hist_view_layout = layout;
-    c->hist_view_has_camera = c->has_camera;
-    c->hist_view_camera = c->camera;
-    c->derived.produced(kCapturedView);
-    return SPT_OK;
-}
-
-int spt_reproject(spt_ctx* c, const spt_reproject_params* params) {
-    if (!c) return SPT_ERR_INVALID;
-    const spt_reproject_params p = params ? *params : kReprojectDefaults;
-    if (const char* msg = reproject_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
-    if (const int rc = history_ready(c, "spt_reproject", true); rc != SPT_OK) return rc;
-    if (!c->derived.valid(kCapturedView)) return fail(c, SPT_ERR_INVALID, "no captured view: spt_history_capture first");
-    if (const int rc = ensure_buf(c, c->hist, c->pixels, "spt_reproject"); rc != SPT_OK) return rc;
-    c->derived.begin(kHistory);
-    const uint32_t n_mats = (uint32_t)c->h_mats.size();
-    if (c->bsdf && !c->derived.valid(kReusable)) {
-        // (spt_set_material_models drained the stream before it changed the models: nothing reads the old words)
-        std::vector<uint32_t> words(n_mats);
-        for (uint32_t m = 0; m < n_mats; ++m) words[m] = c->h_models[m].kind == SPT_MAT_DIFFUSE ? 1u : 0u;
-        if (const int rc = ensure_buf(c, c->d_reusable, n_mats, "spt_reproject"); rc != SPT_OK) return rc;
-        SPT_HIP(c, hipMemcpy(c->d_reusable, words.data(), sizeof(uint32_t) * n_mats, hipMemcpyHostToDevice));
-        c->derived.produced(kReusable);
-    }
-    const ReprojectView v = reproject_view(c->hist_view_has_camera ? &c->hist_view_camera : nullptr);
-    launch_reproject(c->hist_view_layout, c->feat_a, c->feat_b, c->hist_view, c->hist, c->cfg.width, c->cfg.height, v, p,
-                     c->bsdf ? c->d_reusable : nullptr, n_mats, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    c->derived.produced(kHistory);
-    return SPT_OK;
-}
-
-int spt_history_clear(spt_ctx* c) {
-    if (!c) return SPT_ERR_INVALID;
-    c->derived.drop(Change::HistoryClear);
-    return SPT_OK;
-}
-
-int spt_read_history(spt_ctx* c, float* host_rgba) { return read_image(c, kImgHistory, host_rgba); }
-int spt_history_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgHistory, dptr, bytes); }
-
-int spt_history_blend(spt_ctx* c, uint32_t frame_count) {
-    if (!c) return SPT_ERR_INVALID;
-    if (const int rc = history_ready(c, "spt_history_blend", false); rc != SPT_OK) return rc;
-    if (frame_count == 0) return fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-    if (const int rc = ensure_buf(c, c->blend, c->pixels, "spt_history_blend"); rc != SPT_OK) return rc;
-    c->derived.begin(kBlended);
-    launch_history_blend(c->accum, (float)frame_count, c->derived.valid(kHistory) ? c->hist : nullptr, c->blend, c->pixels, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    c->derived.produced(kBlended);
-    return SPT_OK;
-}
-
-int spt_read_blended(spt_ctx* c, float* host_rgba) { return read_image(c, kImgBlended, host_rgba); }
-int spt_blended_device_ptr(spt_ctx* c, void** dptr, size_t* bytes) { return image_device_ptr(c, kImgBlended, dptr, bytes); }
-int spt_resolve_blended_rgba8(spt_ctx* c, float exposure, uint32_t* host_out) {
-    return resolve_mean_rgba8(c, kImgBlended, exposure, host_out);
-}
-
-int spt_denoise_blended(spt_ctx* c, const spt_denoise_params* params) {
-    if (!c) return SPT_ERR_INVALID;
-    const float4* img = post_image(c, kImgBlended);
-    return img ? denoise_image(c, img, 0.0f, params) : SPT_ERR_INVALID;
-}
-
-int spt_set_history_layout(spt_ctx* c, int layout) {
-    if (!c) return SPT_ERR_INVALID;
-    if (layout != -1 && layout != kHistoryPlanes && layout != kHistoryRecords)
-        return fail(c, SPT_ERR_INVALID, "spt_set_history_layout: -1 (automatic), 0 (three images) or 1 (48-byte records)");
-    c->hist_layout = layout;
-    return SPT_OK;
-}
-
-int spt_reproject_basis(const spt_camera* cam, float rows[9], float origin[3], float* j) {
-    if (!rows || !origin || !j) return SPT_ERR_INVALID;
-    if (cam && camera_error(*cam)) return SPT_ERR_INVALID;
-    const ReprojectView v = reproject_view(cam);
-    for (int a = 0; a < 3; ++a) {
-        rows[a] = v.ru[a];
-        rows[3 + a] = v.rv[a];
-        rows[6 + a] = v.rw[a];
-        origin[a] = v.o[a];
-    }
-    *j = v.j;
-    return SPT_OK;
-}
-
-int spt_reproject_host(const spt_reproject_params* params, const spt_camera* prev_camera, uint32_t width, uint32_t height,
-                       const float* cur_a, const float* cur_b, const float* hist_rgba, const float* hist_a,
-                       const float* hist_b, const uint32_t* material_reusable, uint32_t n_materials, float* out) {
-    if (!cur_a || !cur_b || !hist_rgba || !hist_a || !hist_b || !out || width == 0 || height == 0) return SPT_ERR_INVALID;
-    if ((uint64_t)width * height >= (1ull << 31)) return SPT_ERR_INVALID;
-    const spt_reproject_params p = params ? *params : kReprojectDefaults;
-    if (reproject_params_error(p)) return SPT_ERR_INVALID;
-    if (prev_camera && camera_error(*prev_camera)) return SPT_ERR_INVALID;
-    const ReprojectView v = reproject_view(prev_camera);
-    auto px = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
-    const size_t n = (size_t)width * height;
-    for (size_t at = 0; at < n; ++at) {
-        const float4 o = reproject_pixel(
-            px(cur_a, at), px(cur_b, at), (int)width, (int)height, v, p, material_reusable, n_materials,
-            [&](size_t q) { return px(hist_a, q); }, [&](size_t q) { return px(hist_b, q); },
-            [&](size_t q) { return px(hist_rgba, q); });
-        out[4 * at + 0] = o.x;
-        out[4 * at + 1] = o.y;
-        out[4 * at + 2] = o.z;
-        out[4 * at + 3] = o.w;
-    }
-    return SPT_OK;
-}
-
-// ---- exposure and tone mapping: the luminance meter and the display resolve -------------------------
-
-namespace {
-const spt_exposure_params kExposureDefaults = {0.18f, 0.1f, 0.02f, 0.015625f, 64.0f, {0u, 0u, 0u}};
-bool exposure_params_ok(const spt_exposure_params& p) {
-    for (const float v : {p.target_luminance, p.low_fraction, p.high_fraction, p.min_exposure, p.max_exposure})
-        if (!std::isfinite(v)) return false;
-    if (!(p.target_luminance > 0.0f) || !(p.min_exposure > 0.0f) || !(p.max_exposure > 0.0f)) return false;
-    if (p.min_exposure > p.max_exposure) return false;
-    if (p.low_fraction < 0.0f || p.high_fraction < 0.0f) return false;
-    if ((double)p.low_fraction + (double)p.high_fraction >= 1.0) return false;
-    return !(p.reserved[0] | p.reserved[1] | p.reserved[2]);
-}
-// nullptr: valid
-const char* display_error(const spt_display& d) {
-    if (d.tonemap > SPT_TONEMAP_ACES) return "spt_display: unknown tonemap operator";
-    if (!std::isfinite(d.exposure) || d.exposure < 0.0f) return "spt_display: exposure must be finite and >= 0";
-    if (d.reserved[0] | d.reserved[1]) return "spt_display: reserved must be 0";
-    return nullptr;
-}
-bool divisor_ok(float divisor) { return std::isfinite(divisor) && divisor > 0.0f; }
-
-// The ctx image `image` with its divisor (the frame count for the sums, 1 for a mean), or nullptr with the
-// status to return in *rc.
-const float4* display_source(spt_ctx* c, uint32_t image, uint32_t frame_count, float* divisor, int* rc) {
-    *rc = SPT_ERR_INVALID;
-    if (image > SPT_IMAGE_BLENDED) {
-        fail(c, SPT_ERR_INVALID, "unknown image: SPT_IMAGE_ACCUM, SPT_IMAGE_DENOISED or SPT_IMAGE_BLENDED");
-        return nullptr;
-    }
-    if (!c->configured) {
-        *rc = fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
-        return nullptr;
-    }
-    *divisor = 1.0f;
-    if (image != SPT_IMAGE_ACCUM) return post_image(c, image == SPT_IMAGE_DENOISED ? kImgDenoised : kImgBlended);
-    if (frame_count == 0) {
-        fail(c, SPT_ERR_INVALID, "No frames rendered yet");
-        return nullptr;
-    }
-    *divisor = (float)frame_count;
-    return c->accum;
-}
-
-// counts = the histogram of img[0..n) / divisor, waited for
-int meter_image(spt_ctx* c, const char* who, const float4* img, uint64_t n, float divisor, uint32_t* counts) {
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (const int rc = ensure_buf(c, c->meter_counts, SPT_METER_BINS, who); rc != SPT_OK) return rc;
-    SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_METER_BINS, on_stream(c)));
-    launch_meter(c->meter_form >= 0 ? c->meter_form : meter_default_form(), img, n, divisor, c->meter_counts, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    SPT_HIP(c, hipMemcpyAsync(counts, c->meter_counts, sizeof(uint32_t) * SPT_METER_BINS, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-float4 pixel_of(const float* a, uint64_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); }
-}  // namespace
-
-int spt_exposure_params_default(spt_exposure_params* out) {
-    if (!out) return SPT_ERR_INVALID;
-    *out = kExposureDefaults;
-    return SPT_OK;
-}
-
-int spt_meter_luminance(spt_ctx* c, uint32_t image, uint32_t frame_count, uint32_t counts[SPT_METER_BINS]) {
-    if (!c || !counts) return SPT_ERR_INVALID;
-    float divisor = 1.0f;
-    int rc = SPT_OK;
-    const float4* img = display_source(c, image, frame_count, &divisor, &rc);
-    if (!img) return rc;
-    return meter_image(c, "spt_meter_luminance", img, c->pixels, divisor, counts);
-}
-
-int spt_meter_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixels, float divisor,
-                           uint32_t counts[SPT_METER_BINS]) {
-    if (!c || !device_rgba || !counts) return SPT_ERR_INVALID;
-    if (n_pixels == 0) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: no pixels");
-    if (!divisor_ok(divisor)) return fail(c, SPT_ERR_INVALID, "spt_meter_device_image: divisor must be finite and > 0");
-    return meter_image(c, "spt_meter_device_image", (const float4*)device_rgba, n_pixels, divisor, counts);
-}
-
-int spt_resolve_display_rgba8(spt_ctx* c, uint32_t image, uint32_t frame_count, const spt_display* display,
-                              uint32_t* host_out) {
-    if (!c || !display || !host_out) return SPT_ERR_INVALID;
-    const spt_display d = *display;
-    if (const char* msg = display_error(d)) return fail(c, SPT_ERR_INVALID, msg);
-    float divisor = 1.0f;
-    int rc = SPT_OK;
-    const float4* img = display_source(c, image, frame_count, &divisor, &rc);
-    if (!img) return rc;
-    return resolve_image_by(c, host_out, [&](uint32_t* out, hipStream_t s) {
-        launch_display(img, c->pixels, divisor, d, out, s);
-    });
-}
-
-int spt_resolve_display_device_image(spt_ctx* c, const void* device_rgba, uint64_t n_pixels, float divisor,
-                                     const spt_display* display, uint32_t* host_out) {
-    if (!c || !device_rgba || !display || !host_out) return SPT_ERR_INVALID;
-    if (n_pixels == 0) return fail(c, SPT_ERR_INVALID, "spt_resolve_display_device_image: no pixels");
-    if (!divisor_ok(divisor))
-        return fail(c, SPT_ERR_INVALID, "spt_resolve_display_device_image: divisor must be finite and > 0");
-    const spt_display d = *display;
-    if (const char* msg = display_error(d)) return fail(c, SPT_ERR_INVALID, msg);
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (c->display_stage.size() < n_pixels) {
-        SPT_HIP(c, hipStreamSynchronize(on_stream(c)));  // (no earlier resolve may still read the old one)
-        if (!c->display_stage.ensure_at_least(n_pixels))
-            return fail(c, SPT_ERR_HIP, "spt_resolve_display_device_image: allocation failed");
-    }
-    launch_display((const float4*)device_rgba, n_pixels, divisor, d, c->display_stage, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    SPT_HIP(c, hipMemcpyAsync(host_out, c->display_stage, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-int spt_set_meter_form(spt_ctx* c, int form) {
-    if (!c) return SPT_ERR_INVALID;
-    if (form != -1 && form != kMeterLanes && form != kMeterPeel)
-        return fail(c, SPT_ERR_INVALID, "spt_set_meter_form: -1 (automatic), 0 (an add per lane) or 1 (an add per distinct bin)");
-    c->meter_form = form;
-    return SPT_OK;
-}
-
-int spt_meter_bin(float luminance, uint32_t* bin) {
-    if (!bin) return SPT_ERR_INVALID;
-    *bin = meter_bin(luminance);
-    return SPT_OK;
-}
-
-int spt_luminance_histogram_host(const float* rgba, uint64_t n_pixels, float divisor, uint32_t counts[SPT_METER_BINS]) {
-    if (!rgba || !counts || n_pixels == 0 || !divisor_ok(divisor)) return SPT_ERR_INVALID;
-    std::memset(counts, 0, sizeof(uint32_t) * SPT_METER_BINS);
-    for (uint64_t i = 0; i < n_pixels; ++i) counts[meter_bin(pixel_luminance(pixel_of(rgba, i), divisor))] += 1u;
-    return SPT_OK;
-}
-
-int spt_exposure_from_histogram(const uint32_t counts[SPT_METER_BINS], const spt_exposure_params* params, float* exposure) {
-    if (!counts || !exposure) return SPT_ERR_INVALID;
-    const spt_exposure_params p = params ? *params : kExposureDefaults;
-    if (!exposure_params_ok(p)) return SPT_ERR_INVALID;
-    uint64_t total = 0;
-    for (int b = 1; b < SPT_METER_BINS; ++b) total += counts[b];
-    if (total == 0) {
-        *exposure = 1.0f;
-        return SPT_OK;
-    }
-    const double n = (double)total;
-    const double lo = (double)p.low_fraction * n, hi = (1.0 - (double)p.high_fraction) * n;
-    double c0 = 0.0, sw = 0.0, sl = 0.0;
-    for (int b = 1; b < SPT_METER_BINS; ++b) {
-        const double c1 = c0 + (double)counts[b];
-        const double w = std::max(0.0, std::min(c1, hi) - std::max(c0, lo));
-        const int key = kMeterKeyBase + b, e = (key >> 3) - 127, k = key & 7;
-        const double centre = (double)e + std::log2(1.0 + ((double)k + 0.5) / 8.0);
-        sw += w;
-        sl += w * centre;
-        c0 = c1;
-    }
-    double x = (double)p.target_luminance / std::exp2(sl / sw);
-    x = std::min(std::max(x, (double)p.min_exposure), (double)p.max_exposure);
-    *exposure = (float)x;
-    return SPT_OK;
-}
-
-int spt_display_host(const float* rgba, uint64_t n_pixels, float divisor, const spt_display* display, uint32_t* out) {
-    if (!rgba || !display || !out || n_pixels == 0 || !divisor_ok(divisor)) return SPT_ERR_INVALID;
-    const spt_display d = *display;
-    if (display_error(d)) return SPT_ERR_INVALID;
-    for (uint64_t i = 0; i < n_pixels; ++i) out[i] = display_rgba8(pixel_of(rgba, i), divisor, d);
-    return SPT_OK;
-}
-
-// ---- noise estimate: batch moments, the meter, the stop rule ------------------------------------------
-
-namespace {
-// counts and the e2 image (may be nullptr) of width x height device moments, waited for
-int noise_meter_image(spt_ctx* c, const char* who, const float4* state, uint32_t width, uint32_t height, uint32_t batches,
-                      float W, const spt_noise_params& p, uint32_t* counts, float* e2) {
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (const int rc = ensure_buf(c, c->meter_counts, SPT_METER_BINS, who); rc != SPT_OK) return rc;
-    SPT_HIP(c, hipMemsetAsync(c->meter_counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS, on_stream(c)));
-    launch_noise_meter(state, width, height, (int)p.radius, noise_inv(batches, W), p.dark_floor, c->meter_counts, e2, on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    SPT_HIP(c, hipMemcpyAsync(counts, c->meter_counts, sizeof(uint32_t) * SPT_NOISE_BINS, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-static_assert(SPT_NOISE_BINS == SPT_METER_BINS, "the two meters share the ctx's 256 device words");
-}  // namespace
-
-int spt_noise_update(spt_ctx* c, uint32_t frame_count) {
-    if (!c) return SPT_ERR_INVALID;
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_noise_update before spt_configure");
-    if (frame_count <= c->noise_frames) return fail(c, SPT_ERR_INVALID, "spt_noise_update: no frames since the last update");
-    if (frame_count > (1u << 24)) return fail(c, SPT_ERR_INVALID, "spt_noise_update: more than 2^24 frames");
-    SPT_HIP(c, hipSetDevice(c->device));
-    const size_t pixels = std::max<size_t>(c->pixels, 1);
-    if (const int rc = ensure_buf(c, c->noise_state, pixels, "spt_noise_update"); rc != SPT_OK) return rc;
-    if (c->noise_batches == 0) SPT_HIP(c, hipMemsetAsync(c->noise_state, 0, sizeof(float4) * pixels, on_stream(c)));
-    const float w = (float)(frame_count - c->noise_frames);
-    launch_noise_update(c->accum, c->noise_state, c->pixels, noise_batch(w, c->noise_W), on_stream(c));
-    SPT_HIP(c, hipGetLastError());
-    c->noise_W = c->noise_W + w;
-    c->noise_frames = frame_count;
-    c->noise_batches += 1u;
-    c->noise_metered = false;
-    return SPT_OK;
-}
-
-int spt_noise_batches(const spt_ctx* c, uint32_t* batches, uint32_t* frames) {
-    if (!c) return SPT_ERR_INVALID;
-    if (batches) *batches = c->noise_batches;
-    if (frames) *frames = c->noise_frames;
-    return SPT_OK;
-}
-
-int spt_noise_meter(spt_ctx* c, const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS]) {
-    if (!c || !counts) return SPT_ERR_INVALID;
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "spt_noise_meter before spt_configure");
-    const spt_noise_params p = params ? *params : kNoiseDefaults;
-    if (const char* msg = noise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
-    if (c->noise_batches < 2) return fail(c, SPT_ERR_INVALID, "spt_noise_meter: fewer than two updates since the accumulation restarted");
-    if (p.radius > 0 && c->cfg.shard_count != 1u)
-        return fail(c, SPT_ERR_INVALID, "spt_noise_meter: pooling (radius > 0) needs the whole image (shard_count 1)");
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (c->pixels == 0) {
-        std::memset(counts, 0, sizeof(uint32_t) * SPT_NOISE_BINS);
-        return SPT_OK;
-    }
-    if (const int rc = ensure_buf(c, c->noise_e2, c->pixels, "spt_noise_meter"); rc != SPT_OK) return rc;
-    const int rc = noise_meter_image(c, "spt_noise_meter", c->noise_state,c->cfg.width, c->rows, c->noise_batches, c->noise_W, p, counts, c->noise_e2);
-    c->noise_metered = rc == SPT_OK;
-    return rc;
-}
-
-int spt_read_noise_moments(spt_ctx* c, float* host_moments) {
-    if (!c || !host_moments) return SPT_ERR_INVALID;
-    if (!c->noise_state || c->noise_batches == 0) return fail(c, SPT_ERR_INVALID, "no noise moments: spt_noise_update first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    if (c->pixels == 0) return SPT_OK;
-    SPT_HIP(c, hipMemcpyAsync(host_moments, c->noise_state, sizeof(float4) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-int spt_read_noise(spt_ctx* c, float* host_e2) {
-    if (!c || !host_e2) return SPT_ERR_INVALID;
-    if (!c->noise_e2 || !c->noise_metered) return fail(c, SPT_ERR_INVALID, "no noise image: spt_noise_meter first");
-    SPT_HIP(c, hipSetDevice(c->device));
-    SPT_HIP(c, hipMemcpyAsync(host_e2, c->noise_e2, sizeof(float) * c->pixels, hipMemcpyDeviceToHost, on_stream(c)));
-    SPT_HIP(c, hipStreamSynchronize(on_stream(c)));
-    return SPT_OK;
-}
-
-int spt_noise_device_ptr(spt_ctx* c, void** moments, void** e2, uint64_t* pixels) {
-    if (!c) return SPT_ERR_INVALID;
-    if (!c->configured) return fail(c, SPT_ERR_NOT_CONFIGURED, "not configured");
-    if (moments) *moments = c->noise_state;
-    if (e2) *e2 = c->noise_e2;
-    if (pixels) *pixels = c->pixels;
-    return SPT_OK;
-}
-
-int spt_noise_meter_device_image(spt_ctx* c, const void* device_moments, uint32_t width, uint32_t height, uint32_t batches,
-                                 float frames, const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS],
-                                 void* device_e2) {
-    if (!c || !device_moments || !counts) return SPT_ERR_INVALID;
-    const spt_noise_params p = params ? *params : kNoiseDefaults;
-    if (const char* msg = noise_params_error(p)) return fail(c, SPT_ERR_INVALID, msg);
-    if (const char* msg = noise_image_error(width, height, batches, frames)) return fail(c, SPT_ERR_INVALID, msg);
-    return noise_meter_image(c, "spt_noise_meter_device_image", (const float4*)device_moments, width, height, batches, frames, p, counts, (float*)device_e2);
-}
-
-int spt_camera_look_at(const float eye[3], const float target[3], const float up[3], float vfov_degrees,
-                       spt_camera* out) {
-    if (!eye || !target || !up || !out) return SPT_ERR_INVALID;
-    if (!(vfov_degrees > 0.0f && vfov_degrees < 180.0f)) return SPT_ERR_INVALID;
-    auto norm = [](double v[3]) {
-        const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        if (!(l > 0.0) || !std::isfinite(l)) return false;
-        for (int a = 0; a < 3; ++a) v[a] /= l;
-        return true;
-    };
-    double f[3], r[3], t[3];
-    for (int a = 0; a < 3; ++a) f[a] = (double)target[a] - (double)eye[a];
-    if (!norm(f)) return SPT_ERR_INVALID;  // eye == target
-    const double upd[3] = {up[0], up[1], up[2]};
-    r[0] = upd[1] * f[2] - upd[2] * f[1];  // cross(up, f)
-    r[1] = upd[2] * f[0] - upd[0] * f[2];
-    r[2] = upd[0] * f[1] - upd[1] * f[0];
-    // up parallel to the view direction: |cross| vanishes against |up| (|f| = 1)
-    const double ul = std::sqrt(upd[0] * upd[0] + upd[1] * upd[1] + upd[2] * upd[2]);
-    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (!(ul > 0.0) || !std::isfinite(ul) || !(rl > 1e-12 * ul)) return SPT_ERR_INVALID;
-    if (!norm(r)) return SPT_ERR_INVALID;
-    t[0] = f[1] * r[2] - f[2] * r[1];  // cross(f, r)
-    t[1] = f[2] * r[0] - f[0] * r[2];
-    t[2] = f[0] * r[1] - f[1] * r[0];
-    // tan(vfov / 2); 90 degrees is exactly 1 (tan(pi / 4) in double is 1 - 1 ulp)
-    const double h = vfov_degrees == 90.0f ? 1.0 : std::tan((double)vfov_degrees * (3.14159265358979323846 / 360.0));
-    spt_camera cam{};
-    for (int a = 0; a < 3; ++a) {
-        cam.origin[a] = eye[a];
-        cam.u[a] = (float)(r[a] * h);
-        cam.v[a] = (float)(t[a] * h);
-        cam.w[a] = (float)f[a];
-    }
-    *out = cam;
     return SPT_OK;
 }
 
@@ -2517,38 +1446,6 @@ int spt_camera_focus_at_hit(const spt_camera* cam, uint32_t width, uint32_t heig
     const double len = std::sqrt(q);
     if (!(len > 0.0) || !std::isfinite(len)) return SPT_ERR_INVALID;
     *focus_distance = (float)((double)t / len);
-    return SPT_OK;
-}
-
-int spt_env_octa_from_equirect(const float* src, uint32_t sw, uint32_t sh, float* dst, uint32_t dw, uint32_t dh) {
-    if (!src || !dst || sw == 0 || sh == 0 || dw == 0 || dh == 0) return SPT_ERR_INVALID;
-    const double kPi = 3.14159265358979323846;
-    for (uint32_t iy = 0; iy < dh; ++iy) {
-        for (uint32_t ix = 0; ix < dw; ++ix) {
-            // octahedral decode of the texel centre (the inverse of octa_texel's projection)
-            double px = 2.0 * (ix + 0.5) / dw - 1.0, pz = 2.0 * (iy + 0.5) / dh - 1.0;
-            double y = 1.0 - std::fabs(px) - std::fabs(pz);
-            if (y < 0.0) {
-                const double fx = (1.0 - std::fabs(pz)) * (px >= 0.0 ? 1.0 : -1.0);
-                const double fz = (1.0 - std::fabs(px)) * (pz >= 0.0 ? 1.0 : -1.0);
-                px = fx;
-                pz = fz;
-            }
-            const double len = std::sqrt(px * px + y * y + pz * pz);
-            const double x = px / len, yy = y / len, z = pz / len;
-            const double phi = std::atan2(x, -z);                              // [-pi, pi]
-            const double theta = std::acos(std::max(-1.0, std::min(1.0, yy)));  // 0 at +y
-            uint32_t sx = (uint32_t)((phi + kPi) / (2.0 * kPi) * sw), sy = (uint32_t)(theta / kPi * sh);
-            sx = std::min(sx, sw - 1u);
-            sy = std::min(sy, sh - 1u);
-            const float* t = src + 3ull * ((size_t)sy * sw + sx);
-            float* o = dst + 4ull * ((size_t)iy * dw + ix);
-            o[0] = t[0];
-            o[1] = t[1];
-            o[2] = t[2];
-            o[3] = 1.0f;
-        }
-    }
     return SPT_OK;
 }
 

@@ -17,11 +17,7 @@
 //             luminance is computed once per staged record.
 // guided_form_of_step picks the form per step from the measurement in profiles/guided_rates.txt: tiled at
 // step 1, straight from step 2 on.
-// Below the kernels: the host-only entry points, the same functions over the caller's arrays.
 #include "spt_denoise_guided.h"
-
-#include <cstring>
-#include <vector>
 
 namespace spt {
 
@@ -183,69 +179,3 @@ void launch_guided_level(int form, const float4* color, float divisor, const flo
 }
 
 }  // namespace spt
-
-// ---- the host-only entry points (include/spt.h): the same functions over the caller's arrays; no device call ----
-using namespace spt;
-
-int spt_guided_params_default(spt_guided_params* out) {
-    if (!out) return SPT_ERR_INVALID;
-    *out = kGuidedDefaults;
-    return SPT_OK;
-}
-
-int spt_atrous_guided_host(const float* rgba, const float* moments, const float* feat_a, const float* feat_b,
-                           uint32_t width, uint32_t height, uint32_t batches, uint32_t frame_count,
-                           const spt_guided_params* params, float* out, float* out_variance) {
-    if (!rgba || !moments || !feat_a || !feat_b || !out || width == 0 || height == 0) return SPT_ERR_INVALID;
-    if ((uint64_t)width * height >= (1ull << 31)) return SPT_ERR_INVALID;
-    if (batches < 2 || frame_count == 0) return SPT_ERR_INVALID;
-    const spt_guided_params p = params ? *params : kGuidedDefaults;
-    if (guided_params_error(p)) return SPT_ERR_INVALID;
-    const size_t n = (size_t)width * height;
-    const int w = (int)width, h = (int)height;
-    const float inv = guided_inv(batches, frame_count);
-    auto px = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
-    std::vector<float> v0(n);
-    for (size_t i = 0; i < n; ++i) v0[i] = guided_variance0(moments[4 * i + 1], inv);
-    std::vector<float> vbuf[2] = {std::vector<float>(n), std::vector<float>(n)};
-    std::vector<float> cbuf[2] = {std::vector<float>(4 * n), std::vector<float>(4 * n)};
-    // (the level before level 0 "wrote" slot 1: the colour is the caller's, the variance the prefilter's)
-    if (p.prefilter) {
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x)
-                vbuf[1][(size_t)y * width + (size_t)x] = guided_prefilter_pixel(
-                    x, y, w, h, [&](int qx, int qy) { return v0[(size_t)qy * width + (size_t)qx]; });
-    } else {
-        vbuf[1] = v0;
-    }
-    const float* in = rgba;
-    const float* vin = vbuf[1].data();
-    for (uint32_t l = 0; l < p.levels; ++l) {
-        const GuidedLevel lv = guided_level(l, p);
-        float* dst = cbuf[l & 1u].data();
-        float* vdst = vbuf[l & 1u].data();
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x) {
-                const size_t at = (size_t)y * width + (size_t)x;
-                const float4 cp = px(in, at);
-                float pv;
-                const float4 o = guided_pixel(
-                    guided_tap(cp, px(feat_a, at), px(feat_b, at), vin[at]), cp.w, x, y, w, h, lv,
-                    [&](int, int, int qx, int qy) {
-                        const size_t q = (size_t)qy * width + (size_t)qx;
-                        return guided_tap(px(in, q), px(feat_a, q), px(feat_b, q), vin[q]);
-                    },
-                    &pv);
-                dst[4 * at + 0] = o.x;
-                dst[4 * at + 1] = o.y;
-                dst[4 * at + 2] = o.z;
-                dst[4 * at + 3] = o.w;
-                vdst[at] = pv;
-            }
-        in = dst;
-        vin = vdst;
-    }
-    std::memcpy(out, in, sizeof(float) * 4 * n);
-    if (out_variance) std::memcpy(out_variance, vin, sizeof(float) * n);
-    return SPT_OK;
-}

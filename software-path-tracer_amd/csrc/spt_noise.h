@@ -82,17 +82,9 @@ __host__ __device__ inline float noise_pooled_e2(int x, int y, int width, int he
     return noise_e2(s_mean / n, s_m2 / n, inv, dark_floor);
 }
 
-// ---- the definition's host part, shared by the ctx's entry points (spt_capi.hip) and the host-only ones ----
-constexpr spt_noise_params kNoiseDefaults = {1u, 0.01f, {0u, 0u}};
+// ---- the definition's host part, shared by spt_capi_post.hip and spt_host.cpp (the parameters': spt_params.h) ----
 constexpr float kNoiseMaxFrames = 16777216.0f;  // 2^24: W stays an exact integer in a float
 
-// nullptr: valid
-inline const char* noise_params_error(const spt_noise_params& p) {
-    if (p.radius > (uint32_t)kNoiseMaxRadius) return "spt_noise_params: radius must be 0, 1 or 2";
-    if (!std::isfinite(p.dark_floor) || p.dark_floor < 0.0f) return "spt_noise_params: dark_floor must be finite and >= 0";
-    if (p.reserved[0] | p.reserved[1]) return "spt_noise_params: reserved must be 0";
-    return nullptr;
-}
 // a frame count held in a float: an integer in [1, 2^24]
 inline bool noise_count_ok(float frames) {
     return frames >= 1.0f && frames <= kNoiseMaxFrames && frames == (float)(uint32_t)frames;

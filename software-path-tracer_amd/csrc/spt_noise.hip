@@ -1,5 +1,5 @@
 // spt_noise.hip — the noise estimate's kernels for MI355X (gfx950), every pixel by spt_noise.h's functions (the
-// ones spt_noise_update_host and spt_noise_meter_host run on the CPU: the same bits). A translation unit of its
+// ones spt_host.cpp's spt_noise_update_host and spt_noise_meter_host run on the CPU: the same bits). A translation unit of its
 // own: spt_kernels.hip is the run-time compiler's source and stays free of it.
 //
 // k_noise_update: a streaming pass, 16 B of accumulation and 16 B of state read and 16 B written per pixel. A
@@ -12,7 +12,6 @@
 // wave, wave + 4, ..., a lane one column. The block first stages the tile's (mean, m2) pairs with their halo in
 // LDS (8 B per record, rows of 64 + 2 * radius records filled by consecutive lanes), then taps LDS, so every
 // global and LDS access of a wave is one contiguous run.
-// Below the kernels: the host-only entry points, the same functions over the caller's arrays.
 #include "spt_noise.h"
 
 namespace spt {
@@ -167,80 +166,3 @@ void launch_noise_meter(const float4* state, uint32_t width, uint32_t height, in
 }
 
 }  // namespace spt
-
-// ---- the host-only entry points (include/spt.h): the same functions over the caller's arrays; no device call ----
-using namespace spt;
-
-int spt_noise_params_default(spt_noise_params* out) {
-    if (!out) return SPT_ERR_INVALID;
-    *out = kNoiseDefaults;
-    return SPT_OK;
-}
-
-int spt_noise_update_host(const float* accum_rgba, uint64_t n_pixels, float batch_frames, float frames_before, float* moments) {
-    if (!accum_rgba || !moments || n_pixels == 0) return SPT_ERR_INVALID;
-    if (!noise_count_ok(batch_frames) || !(frames_before == 0.0f || noise_count_ok(frames_before))) return SPT_ERR_INVALID;
-    if ((double)frames_before + (double)batch_frames > (double)kNoiseMaxFrames) return SPT_ERR_INVALID;
-    const NoiseBatch b = noise_batch(batch_frames, frames_before);
-    for (uint64_t i = 0; i < n_pixels; ++i) {
-        const float* a = accum_rgba + 4 * i;
-        float* m = moments + 4 * i;
-        const float4 s = frames_before == 0.0f ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(m[0], m[1], m[2], m[3]);
-        const float4 o = noise_update_pixel(make_float4(a[0], a[1], a[2], a[3]), s, b);
-        m[0] = o.x;
-        m[1] = o.y;
-        m[2] = o.z;
-        m[3] = o.w;
-    }
-    return SPT_OK;
-}
-
-int spt_noise_meter_host(const float* moments, uint32_t width, uint32_t height, uint32_t batches, float frames,
-                         const spt_noise_params* params, uint32_t counts[SPT_NOISE_BINS], float* e2) {
-    if (!moments || !counts) return SPT_ERR_INVALID;
-    const spt_noise_params p = params ? *params : kNoiseDefaults;
-    if (noise_params_error(p) || noise_image_error(width, height, batches, frames)) return SPT_ERR_INVALID;
-    const float inv = noise_inv(batches, frames);
-    const int w = (int)width, h = (int)height, radius = (int)p.radius;
-    for (int b = 0; b < SPT_NOISE_BINS; ++b) counts[b] = 0u;
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x) {
-            const size_t i = (size_t)y * width + x;
-            const float e = radius == 0 ? noise_e2(moments[4 * i], moments[4 * i + 1], inv, p.dark_floor)
-                                        : noise_pooled_e2(x, y, w, h, radius, inv, p.dark_floor, [&](int tx, int ty) {
-                                              const size_t t = (size_t)ty * width + tx;
-                                              return make_float2(moments[4 * t], moments[4 * t + 1]);
-                                          });
-            if (e2) e2[i] = e;
-            counts[noise_bin(e)] += 1u;
-        }
-    return SPT_OK;
-}
-
-int spt_noise_from_histogram(const uint32_t counts[SPT_NOISE_BINS], double quantile, double* rel_error) {
-    if (!counts || !rel_error || !(quantile > 0.0 && quantile <= 1.0)) return SPT_ERR_INVALID;
-    uint64_t total = 0;
-    for (int b = 0; b < SPT_NOISE_BINS; ++b) total += counts[b];
-    *rel_error = 0.0;
-    if (total == 0) return SPT_OK;
-    const double need = quantile * (double)total;
-    uint64_t cum = 0;
-    int bin = SPT_NOISE_BINS - 1;
-    for (int b = 0; b < SPT_NOISE_BINS; ++b) {
-        cum += counts[b];
-        if ((double)cum >= need) {
-            bin = b;
-            break;
-        }
-    }
-    if (bin == 0) return SPT_OK;
-    if (bin == SPT_NOISE_BINS - 1) {
-        *rel_error = HUGE_VAL;
-        return SPT_OK;
-    }
-    const uint32_t bits = (uint32_t)(kNoiseKeyBase + bin + 1) << 20;
-    float edge;
-    __builtin_memcpy(&edge, &bits, sizeof(edge));
-    *rel_error = std::sqrt((double)edge);
-    return SPT_OK;
-}

@@ -1,5 +1,5 @@
-// adaptive_host_check.cpp — csrc/spt_adaptive.h's functions on the host, in a program of its own: compiled as HIP
-// (the header's functions are __host__ __device__) with AddressSanitizer and UndefinedBehaviorSanitizer by
+// adaptive_host_check.cpp — csrc/spt_adaptive.h's functions on the host, in a program of its own: compiled as plain
+// C++ (the header alone, tests/host_program.py) with AddressSanitizer and UndefinedBehaviorSanitizer by
 // tests/test_adaptive_host.py, which compares what it writes with tests/adaptive_ref.py. No device call: it runs
 // without a GPU.
 //

@@ -1,5 +1,5 @@
 // guided_host_check.cpp — the variance-guided denoiser's host function (spt_atrous_guided_host) in a program of
-// its own, compiled with csrc/spt_denoise_guided.hip under AddressSanitizer and UndefinedBehaviorSanitizer by
+// its own, compiled with csrc/spt_host.cpp under AddressSanitizer and UndefinedBehaviorSanitizer by
 // tests/test_guided_host.py. No device call: it runs without a GPU.
 //
 // IN:  u32 W, H, B, F (batches, frame count); then the mean colour, the moments, feat_a and feat_b, W*H*4 floats each.

@@ -1,5 +1,5 @@
 // noise_host_check.cpp — the noise estimate's host functions (spt_noise_update_host, spt_noise_meter_host,
-// spt_noise_from_histogram) in a program of its own, compiled with csrc/spt_noise.hip under AddressSanitizer and
+// spt_noise_from_histogram) in a program of its own, compiled with csrc/spt_host.cpp under AddressSanitizer and
 // UndefinedBehaviorSanitizer by tests/test_noise_host.py. No device call: it runs without a GPU.
 //
 // IN:  u32 W, H, K; K rising frame counts; K accumulations of W*H*4 floats.

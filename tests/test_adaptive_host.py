@@ -1,5 +1,5 @@
-"""Adaptive sampling's per-pixel definition on the host (no GPU): csrc/spt_adaptive.h's functions, compiled as HIP host
-code with AddressSanitizer and UndefinedBehaviorSanitizer into a program of its own (tests/cpp/adaptive_host_check.cpp),
+"""Adaptive sampling's per-pixel definition on the host (no GPU): csrc/spt_adaptive.h's functions, compiled as plain
+C++ with AddressSanitizer and UndefinedBehaviorSanitizer into a program of its own (tests/cpp/adaptive_host_check.cpp),
 against the numpy restatement (tests/adaptive_ref.py) on crafted images; then a whole run emulated on the CPU oracle's
 frames with that program's selections, whose invariant — a pixel that stopped at n frames holds, bit for bit, the
 oracle's accumulation of its first n frames — is what kernels built on the header will be tested by.
@@ -12,15 +12,14 @@ the adaptive run's paths pay for on every live pixel):
   Cornell 96 x 54, 8 bounces, rel_error 0.4:  48.5 % retired, 78.6 % of the paths;
                                               RMS adaptive 0.1894, uniform at equal paths (50 frames) 0.2030
 The adaptive image is the better of the two at equal paths on both scenes, by 7 to 8 %."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import adaptive_ref as ar
+import host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 RADII = [0, 1, 2]
 NAN, INF = float("nan"), float("inf")
@@ -30,15 +29,8 @@ NAN, INF = float("nan"), float("inf")
 def program(tmp_path_factory):
     """The header's functions under the sanitizers: run(e2, stop, batches, frames, rel_error, radius, min_batches,
     accum, exposure) -> (keep, mean, words), or None where the program refuses the parameters."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = os.path.join(ROOT, "software-path-tracer_amd", "csrc")
     tmp = tmp_path_factory.mktemp("adaptive")
-    exe = tmp / "adaptive_host_check"
-    subprocess.run([hipcc, "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "--offload-arch=gfx950",
-                    "-fno-gpu-rdc", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", str(exe),
-                    "-x", "hip", os.path.join(ROOT, "tests", "cpp", "adaptive_host_check.cpp")], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the program links keeps its own allocations)
+    exe = host_program.build("adaptive_host_check", tmp, with_host=False)  # (the header alone)
 
     def run(e2, stop, batches, frames, rel_error=0.1, radius=1, min_batches=4, accum=None, exposure=1.0):
         e2 = np.ascontiguousarray(e2, dtype=F)
@@ -53,7 +45,7 @@ def program(tmp_path_factory):
             e2.tofile(f)
             stop.tofile(f)
             accum.tofile(f)
-        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, env=env, timeout=300)
+        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, timeout=300)
         if r.returncode == 3:
             return None
         assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr

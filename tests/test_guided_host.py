@@ -15,6 +15,7 @@ import pytest
 
 import denoise_ref as dr
 import guided_ref as gr
+import host_program
 import noise_ref as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,19 +228,12 @@ def test_declared_functions_are_exported(spt):
 
 # ---- the host function under the sanitizers -----------------------------------------------------------------
 def test_host_function_under_sanitizers(spt, ref, tmp_path):
-    """tests/cpp/guided_host_check.cpp with csrc/spt_denoise_guided.hip's host side, built with AddressSanitizer and
-    UndefinedBehaviorSanitizer into a program of its own (no device call in it), over the 20 x 12 and the 1 x 1
+    """tests/cpp/guided_host_check.cpp with csrc/spt_host.cpp, built with AddressSanitizer and
+    UndefinedBehaviorSanitizer into a program of its own (tests/host_program.py), over the 20 x 12 and the 1 x 1
     inputs; its results are the library's."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = os.path.join(ROOT, "software-path-tracer_amd", "csrc")
-    exe = tmp_path / "guided_host_check"
-    subprocess.run([hipcc, "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "--offload-arch=gfx950",
-                    "-fno-gpu-rdc", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", str(exe), os.path.join(csrc, "spt_denoise_guided.hip"),
-                    "-x", "hip", os.path.join(ROOT, "tests", "cpp", "guided_host_check.cpp")], check=True)
+    exe = host_program.build("guided_host_check", tmp_path)
     cases = [("small", inputs(spt, ref, "cornell", 20, 12, 8, FOUR_BY_TWO)),
              ("pixel", inputs(spt, ref, "one_sphere", 1, 1, 4, (1, 2)))]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the program links keeps its own allocations)
     for name, (c, m, a, b, B, f) in cases:
         h, w = c.shape[:2]
         inp, out = tmp_path / f"{name}.in", tmp_path / f"{name}.out"
@@ -247,7 +241,7 @@ def test_host_function_under_sanitizers(spt, ref, tmp_path):
             np.array([w, h, B, f], dtype=np.uint32).tofile(fh)
             for arr in (c, m, a, b):
                 np.ascontiguousarray(arr, dtype=F).tofile(fh)
-        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, env=env, timeout=300)
+        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
         raw = np.fromfile(out, dtype=np.uint32)
         want, want_v = spt.atrous_guided_host(c, m, a, b, B, f)

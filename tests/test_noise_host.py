@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_program
 import noise_ref as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -279,21 +280,14 @@ def test_quality_cornell(spt, ref):
 
 # ---- the host functions under the sanitizers --------------------------------------------------------------
 def test_host_functions_under_sanitizers(spt, ref, tmp_path):
-    """tests/cpp/noise_host_check.cpp with csrc/spt_noise.hip's host side, built with AddressSanitizer and
-    UndefinedBehaviorSanitizer into a program of its own (no device call in it), over a 2 x 2 image and a
+    """tests/cpp/noise_host_check.cpp with csrc/spt_host.cpp, built with AddressSanitizer and
+    UndefinedBehaviorSanitizer into a program of its own (tests/host_program.py), over a 2 x 2 image and a
     97 x 53 sequence of the oracle's; its results are the library's."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = os.path.join(ROOT, "software-path-tracer_amd", "csrc")
-    exe = tmp_path / "noise_host_check"
-    subprocess.run([hipcc, "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "--offload-arch=gfx950",
-                    "-fno-gpu-rdc", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", str(exe), os.path.join(csrc, "spt_noise.hip"),
-                    "-x", "hip", os.path.join(ROOT, "tests", "cpp", "noise_host_check.cpp")], check=True)
+    exe = host_program.build("noise_host_check", tmp_path)
     rng = np.random.default_rng(1)
     small = [np.cumsum(rng.uniform(0.0, 1.0, (2, 2, 4)).astype(F), axis=0, dtype=F) * F(k + 1) for k in range(3)]
     cases = [("small", small, (1, 2, 3)),
              ("cornell", accumulations(spt, ref, "cornell", 97, 53, 8, (1, 4, 8)), (1, 4, 8))]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the program links keeps its own allocations)
     for name, accums, fcs in cases:
         h, w = accums[0].shape[:2]
         inp, out = tmp_path / f"{name}.in", tmp_path / f"{name}.out"
@@ -301,7 +295,7 @@ def test_host_functions_under_sanitizers(spt, ref, tmp_path):
             np.array([w, h, len(fcs)] + list(fcs), dtype=np.uint32).tofile(f)
             for a in accums:
                 np.ascontiguousarray(a, dtype=F).tofile(f)
-        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, env=env, timeout=300)
+        r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
         raw = np.fromfile(out, dtype=np.uint32)
         m = lib_fold(spt, accums, fcs)
